@@ -9,8 +9,14 @@ Workload = BASELINE configs[1]: Homography 4-pt DLT + Uniform sampling, 10k synt
 correspondences, 65536-hypothesis batches, 1 MI355X per rank (hypothesis-sharded:
 scaling "weak", each rank owns disjoint hypothesis index ranges).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline fields (value,
+ms_per_step, ...).  --full adds what takes runs of its own: the roofline, the parity checks
+against the CPU oracle and the CPU baseline.  --dump-outputs DIR writes what the last timed step
+returned as DIR/<name>.npy; the inputs depend on the arguments alone, so two builds can be compared
+output for output.
 
 Without a launcher, --gpus N > 1 starts the N rank processes itself (launch_ranks: one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rank 0's line relayed, non-zero exit when any
@@ -56,7 +62,16 @@ def parse():
                     help="device sampler of the batches (default prosac for fundamental = cfg3, else uniform); "
                          "napsac = grid neighbours built on the device (cell 50), homography on the cfg5 "
                          "generator's clustered points (100k by default)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the roofline (its one-batch-at-a-time kernel pass included), "
+                         "the parity checks against the CPU oracle and the CPU baseline; without it a run sets up, "
+                         "warms up, times the steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all): the batch's record and per-slot inlier counts and score "
+                         "sums, or the run's model and inliers (--cfg5, --sprt-exact); rank 0's with N > 1")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0,
+                    help="--full: bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--cfg5", action="store_true",
                     help="BASELINE configs[4]: full USAC runs (homography + NAPSAC grid sampler + LO-RANSAC) "
@@ -626,6 +641,45 @@ def usac_device():
     return _DEV
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # of array data: with the .npy headers the files stay under 64 MB in all
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each array as <directory>/<name>.npy, float32 stays float32 and everything
+    else becomes float64.  When the arrays together exceed DUMP_LIMIT_BYTES, each one larger than
+    its equal share is cut to a fixed sample of its leading axis (seeded, ascending indices)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.atleast_1d(np.asarray(a)) for k, a in arrays.items()}
+    arrays = {k: a if a.dtype == np.float32 else a.astype(np.float64) for k, a in arrays.items()}
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        if over and a.nbytes > share:
+            keep = max(1, share // max(1, a.nbytes // len(a)))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def record_array(rec):
+    """A batch record as numbers: hyp_index, inliers, score, valid, then the model's 9 entries."""
+    return np.array([int(rec.hyp_index), int(rec.inliers), float(rec.score), int(rec.valid)] +
+                    [float(v) for v in rec.model], dtype=np.float64)
+
+
+def run_arrays(out):
+    """A whole run's result (RansacOutput) as arrays: model, inlier indices, main-loop iterations."""
+    return {"model": np.asarray(out.getModel(), np.float32), "inliers": np.asarray(out.getInliers()),
+            "iterations": np.array([out.getNumberOfMainIterations()])}
+
+
+def headline(args, world, value, elapsed, scaling, config):
+    """The fields every line carries; a run without --full prints these alone."""
+    return {"metric": "model hypotheses/sec (sample+solve+score) and inlier-count match vs ref",
+            "value": value, "unit": "hypotheses/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": scaling,
+            "vs_baseline": None, "dtype": "f32", "config": config}
+
+
 def cfg5_main(args, usac, synthetic, dist, torch, world, rank, local_rank):
     """Full-run mode (BASELINE configs[4]): whole USAC loops -- batched device solve + score of
     the NAPSAC samples, exact host replay of the sequential loop, LO-RANSAC (every LSQ fit and
@@ -684,7 +738,8 @@ def cfg5_main(args, usac, synthetic, dist, torch, world, rank, local_rank):
     t0 = time.perf_counter()
     for step in range(args.steps):
         seed = args.seed + step if sharded else args.seed + step * world + rank
-        iters += one_run(seed).getNumberOfMainIterations()
+        last = one_run(seed)
+        iters += last.getNumberOfMainIterations()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
@@ -694,6 +749,15 @@ def cfg5_main(args, usac, synthetic, dist, torch, world, rank, local_rank):
         if not sharded:  # replicas: every rank's runs are distinct work
             dist.all_reduce(tt[1:], op=dist.ReduceOp.SUM)
         elapsed, iters = float(tt[0]), int(tt[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run_arrays(last))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, iters / elapsed, elapsed, "strong" if sharded else "weak", {
+                "workload": "cfg5", "n_points": args.points, "threshold": args.threshold, "lo": args.lo,
+                "max_iterations": max_iters, "parallelism": "hypothesis-sharded runs x%d" % world if sharded else
+                "replicas x%d" % world})))
+        return
     # parity: one run against the oracle (same seed) -- every rank takes part in a sharded run
     out = one_run(args.seed)
     if rank != 0:
@@ -821,6 +885,14 @@ def cfg3_exact_main(args, usac, synthetic, dist, torch, world, rank, local_rank)
         dist.all_reduce(tt[1:], op=dist.ReduceOp.SUM)
         elapsed, iters = float(tt[0]), int(tt[1])
     if rank != 0:
+        ctx.close()
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, run_arrays(out))
+    if not args.full:
+        print(json.dumps(headline(args, world, iters / elapsed, elapsed, "weak", {
+            "workload": "cfg3 exact", "n_points": n, "threshold": args.threshold,
+            "parallelism": "replicas x%d" % world})))
         ctx.close()
         return
     # parity: the first runs of the timed seeds against the oracle
@@ -1121,7 +1193,7 @@ def main():
             c.set_sprt(True, seed=args.seed)
     models_per_hyp = 1.0
     timed_first = (args.warmup * world + rank) * B  # the first timed batch's first hypothesis
-    if fund or ess:  # occupied model slots per sample of the first timed batch (the device stream)
+    if args.full and (fund or ess):  # occupied model slots per sample of the first timed batch (the device stream)
         ctx.set_sprt(False)
         c0, _, _ = ctx.hypothesize_score(B=B, seed=args.seed, first_hyp=timed_first, thr=args.threshold)
         models_per_hyp = float((c0 >= 0).sum()) / B
@@ -1208,10 +1280,14 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     tested_per_batch = ctxs[(args.warmup + args.steps - 1) % P].sprt_tested() if args.sprt else None
-    # roofline pass: the same batches one at a time (no overlap), so the per-kernel durations
+    if args.dump_outputs and rank == 0:  # the last timed batch, still in its context's buffers
+        c = ctxs[(args.warmup + args.steps - 1) % P]
+        counts, sums = c.last_counts(B * (3 if fund else 1))
+        dump_outputs(args.dump_outputs, {"best_record": record_array(c.fetch_best()), "counts": counts, "sums": sums})
+    # roofline pass (--full): the same batches one at a time (no overlap), so the per-kernel durations
     # are the kernels' own (what rocprofv3 reports for `bench.py --pipeline 1`)
     solo_score, solo_solve = [], []
-    for i in range(max(5, min(args.steps, 20))):
+    for i in range(max(5, min(args.steps, 20)) if args.full else 0):
         ctx.hypothesize_async(B, args.seed, ((args.warmup + args.steps + i) * world + rank) * B, args.threshold)
         ctx.fetch_best()
         t = ctx.last_timings()
@@ -1221,10 +1297,16 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if rank == 0 and not args.full:
+        print(json.dumps(headline(args, world, world * args.steps * B / elapsed, elapsed, "weak", {
+            "estimator": args.estimator, "sampler": args.sampler, "sprt": bool(args.sprt), "dlt": args.dlt,
+            "n_points": args.points, "batch_per_gpu": B, "threshold": args.threshold, "score_chunks": args.chunks,
+            "batches_in_flight": P, "prewarm_ms": args.prewarm_ms, "parallelism": "hypothesis-sharded x%d" % world,
+            "exchange": exchange})), flush=True)
     # parity of the timed configuration on every rank (N > 1: each rank's own 256-sample slice, its
     # record also through the line's exchange), gathered to rank 0
     tk_all = None
-    if world > 1:
+    if world > 1 and args.full:
         tk_first = rank * 256  # the stream's head, as at N = 1 (PROSAC's early subsets: SPRT accepts models there)
         own = timed_kernel_parity(usac, ctx, args.estimator, pts, args.threshold, dlt_mode, args.seed,
                                   bool(args.sprt), first_hyp=tk_first,
@@ -1232,7 +1314,7 @@ def main():
         tk_all = [None] * world
         dist.all_gather_object(tk_all, own)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         total = world * args.steps * B
         value = total / elapsed
         n = args.points

@@ -5,7 +5,7 @@ OUT=gpurun_out/bench_all
 mkdir -p $OUT
 run() {  # name, args...
   local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" > $OUT/$name.log 2>&1 || { echo "FAIL $name"; tail -5 $OUT/$name.log; exit 1; }
+  timeout -k 10 300 python bench.py --full "$@" > $OUT/$name.log 2>&1 || { echo "FAIL $name"; tail -5 $OUT/$name.log; exit 1; }
   tail -1 $OUT/$name.log > $OUT/$name.json
   python3 -c "import json; d=json.load(open('$OUT/$name.json')); r=d['roofline']; print('%-16s %8.2f M hyp/s  ms/step %.3f  score %.3f  solve %.3f  parity %s' % ('$name', d['value']/1e6, d['ms_per_step'], r['kernel_ms'], r['solve_kernel_ms'], d.get('parity',{}).get('inlier_counts_equal')))"
 }

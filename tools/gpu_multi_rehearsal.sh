@@ -11,7 +11,7 @@ O=gpurun_out/${1:-multi}; mkdir -p $O
 export USAC_BENCH_SAME_DEVICE=1
 run() {  # name, args...
   local n=$1; shift
-  timeout -k 10 300 python bench.py --gpus 2 "$@" > $O/$n.json 2> $O/$n.err || { tail -20 $O/$n.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --gpus 2 "$@" > $O/$n.json 2> $O/$n.err || { tail -20 $O/$n.err; exit 1; }
   python3 - $O/$n.json <<'EOF'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

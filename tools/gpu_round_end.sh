@@ -13,18 +13,18 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 rc=$?; tail -4 $O/tests.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 rc=$?; cat $O/smoke.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+timeout -k 10 300 python bench.py --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err
 rc=$?; cat $O/bench_cfg2.json; [ $rc -eq 0 ] || exit $rc
 for e in fundamental essential; do
-  timeout -k 10 300 python bench.py --estimator $e > $O/bench_$e.json 2> $O/bench_$e.err
+  timeout -k 10 300 python bench.py --full --estimator $e > $O/bench_$e.json 2> $O/bench_$e.err
   rc=$?; [ $rc -eq 0 ] || { tail -5 $O/bench_$e.err; exit $rc; }
 done
-timeout -k 10 300 python bench.py --cfg5 > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+timeout -k 10 300 python bench.py --full --cfg5 > $O/bench_cfg5.json 2> $O/bench_cfg5.err
 rc=$?; [ $rc -eq 0 ] || { tail -5 $O/bench_cfg5.err; exit $rc; }
-timeout -k 10 300 python bench.py --sprt-exact > $O/bench_cfg3_exact.json 2> $O/bench_cfg3_exact.err
+timeout -k 10 300 python bench.py --full --sprt-exact > $O/bench_cfg3_exact.json 2> $O/bench_cfg3_exact.err
 rc=$?; [ $rc -eq 0 ] || { tail -5 $O/bench_cfg3_exact.err; exit $rc; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $PWD/$O/trace_cfg2 -o run --output-format csv -- \
-    python3 bench.py --steps 20 --warmup 3 > $O/bench_cfg2_traced.json 2> $O/trace_cfg2.err
+    python3 bench.py --full --steps 20 --warmup 3 > $O/bench_cfg2_traced.json 2> $O/trace_cfg2.err
 rc=$?; [ $rc -eq 0 ] || { tail -5 $O/trace_cfg2.err; exit $rc; }
 python3 - $O <<'EOF'
 import json, sys

@@ -29,7 +29,7 @@ for w in $WORKLOADS; do
   esac
   D=$OUT/$w; mkdir -p $D
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $PWD/$D/trace -o run --output-format csv -- \
-      python3 bench.py $STEPS --cpu-seconds 0 --pipeline 1 $ARGS > $D/bench_trace.json 2> $D/trace.err
+      python3 bench.py --full $STEPS --cpu-seconds 0 --pipeline 1 $ARGS > $D/bench_trace.json 2> $D/trace.err
   rc=$?; echo "== $w trace rc=$rc"; [ $rc -eq 0 ] || { tail -5 $D/trace.err; exit $rc; }
   PASSES=(FETCH_SIZE WRITE_SIZE "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
           "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES")
@@ -43,7 +43,7 @@ for w in $WORKLOADS; do
   for ctr in "${PASSES[@]}"; do
     name=$(echo $ctr | tr ' ' '_')
     timeout -k 10 -s KILL 240 rocprofv3 --pmc $ctr -d $PWD/$D/pmc_$name -o run --output-format csv -- \
-        python3 bench.py $PSTEPS --cpu-seconds 0 --pipeline 1 $ARGS > $D/bench_pmc_$name.json 2> $D/pmc_$name.err
+        python3 bench.py --full $PSTEPS --cpu-seconds 0 --pipeline 1 $ARGS > $D/bench_pmc_$name.json 2> $D/pmc_$name.err
     rc=$?; echo "== $w pmc $ctr rc=$rc"; [ $rc -eq 0 ] || { tail -5 $D/pmc_$name.err; exit $rc; }
   done
   python3 tools/summarize_profile.py $D ${TAG}_$w $NPTS $BATCH $OUT/summaries $GRIDS $RUNS > /dev/null || exit 1
