@@ -45,6 +45,9 @@
  *                                  148-201), SPRT (sprt.hpp:191-393, + the batch replay
  *                                  usac_sprt_replay), LocalOptimization::GetModelScore
  *                                  (local_optimization.hpp:19)
+ *   usac_multi_*                   new (ABI 15): P independent two-view problems per launch -- the
+ *                                  usac_hypothesize_score round and a batch-granular RANSAC with the
+ *                                  standard termination criterion over a ragged set of point sets
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -59,7 +62,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 14
+#define USAC_ABI_VERSION 15
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -462,6 +465,67 @@ int usac_exchange_best_async(usac_ctx *ctx, usac_ctx *batch, uint32_t slot);
 int usac_exchange_best_wait(usac_ctx *ctx, uint32_t slot, usac_record *all);
 /* Merge n records by Score::bigger, earliest hyp_index on exact ties. */
 int usac_merge_records(const usac_record *recs, uint32_t n, usac_record *best);
+
+/* ---- multi-problem batches (ABI 15) ------------------------------------------------------
+ * A multi context holds P independent two-view problems of one estimator (USAC_HOMOGRAPHY or
+ * USAC_FUNDAMENTAL; line and essential: USAC_ERR_UNSUPPORTED) and runs them together: one launch
+ * whose grid covers (problem, 64-hypothesis tile).  Points are one concatenated N_total x 4 fp32
+ * array and offsets[P + 1] with offsets[0] = 0: problem p owns rows offsets[p] .. offsets[p + 1] - 1,
+ * n_p >= the sample size.  Sample, hypothesis and inlier indices are local to the problem.
+ *
+ * Per problem every result equals the single-context path bit for bit: problem p with seed s and
+ * global hypothesis index h draws the sample a usac_ctx over its points draws (device uniform sampler
+ * keyed by (s, h) over n_p), the solvers are the same (H: thin QR with the row-Jacobi fall-back,
+ * honouring dlt_mode; F: up to 3 slots, oriented filter, compaction order), and scoring is the
+ * one-chunk exact form: exact counts, the sequential fp32 sum in point order, count -1 (sum 0) on an
+ * empty F slot -- what usac_hypothesize_score returns when per-hypothesis outputs are requested.
+ *
+ * A problem's points are walked by one wave per 64 hypotheses, without point chunking: any n_p is
+ * correct, but the design targets n_p up to a few thousand (many small problems fill the device,
+ * one large problem does not).  P <= 65535.  One device, one HIP stream, not thread-safe. */
+typedef struct usac_multi usac_multi;
+
+/* One problem's result of usac_multi_run. */
+typedef struct usac_multi_output {
+    usac_record best;     /* the run's best under usac_merge_records' order */
+    uint32_t hypotheses;  /* hypotheses evaluated: rounds x R */
+    uint32_t rounds;
+    uint32_t bound;       /* usac_std_termination(best.inliers, n_p, m, desired_prob, max_iterations) */
+    int32_t status;       /* USAC_OK, or USAC_ERR_NO_MODEL when the best count is 0 */
+} usac_multi_output;
+
+/* USAC_ERR_ARG for P == 0 or P > 65535, offsets[0] != 0, non-monotonic offsets or any n_p < m, and
+ * USAC_ERR_UNSUPPORTED for the line and essential estimators -- all before any device call. */
+int usac_multi_create(usac_multi **out, int device, int estimator, const float *pts, const uint32_t *offsets,
+                      uint32_t P);
+void usac_multi_destroy(usac_multi *mc);
+const char *usac_multi_last_error(const usac_multi *mc);
+uint32_t usac_multi_num_problems(const usac_multi *mc);
+/* One round.  problems: the active list, n_problems problem ids in any order (NULL: all P in order,
+ * n_problems = P or 0).  samples: host n_problems x R x m indices local to each problem (out of
+ * range: USAC_ERR_ARG), or NULL for the device sampler with seeds[i] for problems[i].  R: a multiple
+ * of 64 in 64..8192 (a wave never spans two problems).  counts / sums (nullable): n_problems x R x S,
+ * S = 3 for the fundamental solver, else 1.  best (nullable): n_problems records, each the round's
+ * best of its problem under Score::bigger with the earliest (sample, slot) on exact ties,
+ * hyp_index = first_hyp + sample. */
+int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint32_t n_problems,
+                                 const int32_t *samples, uint32_t R, const uint64_t *seeds, uint64_t first_hyp,
+                                 float thr, int dlt_mode, int32_t *counts, float *sums, usac_record *best);
+/* Batch-granular RANSAC with the standard termination criterion, all problems together: in round
+ * r = 0, 1, ... every still-active problem evaluates hypotheses [r R, (r + 1) R) (device sampler,
+ * seeds[p]; seeds == NULL: params->seed + p), its running best is merged by usac_merge_records'
+ * order, bound_p = usac_std_termination(best.inliers, n_p, m, desired_prob, max_iterations), and the
+ * problem is finished once (r + 1) R >= min(max_iterations, bound_p).  The clamp to max_iterations is
+ * a deviation from ransac.cpp, which lets the bound exceed it: a batch call must stay bounded.  A run
+ * evaluates at least as many hypotheses as the bound asks for, so the confidence guarantee holds.
+ * This is NOT the glibc-stream Ransac::run (usac_ransac_run): no SPRT, LO, PROSAC, NAPSAC or polish
+ * -- params->sprt, ->lo or a sampler other than USAC_SAMPLER_UNIFORM return USAC_ERR_UNSUPPORTED.
+ * Reads threshold, desired_prob, max_iterations, dlt_mode, seed and batch (= R, 0 = 256).
+ * out: P results. */
+int usac_multi_run(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out);
+/* Per-point inlier flags of each problem's model (models P x 9, mask N_total bytes of 0 / 1, counts
+ * P, nullable) from the residual of usac_get_inliers; for H, H^-1 is the device inv3x3 of the given H. */
+int usac_multi_inliers(usac_multi *mc, const float *models, float thr, uint8_t *mask, int32_t *counts);
 
 /* ---- self-test hooks (ABI 13) ------------------------------------------------------- */
 /* The essential 5-point solver's root step alone (five_points.cpp:139-157: rpoly_ak1's real zeros

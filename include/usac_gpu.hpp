@@ -527,6 +527,90 @@ private:
     RansacOutput *out_ = nullptr;
 };
 
+// P independent two-view problems of one estimator (Homography / Fundamental) run together
+// (usac_multi_*, ABI 15): points concatenated, offsets[P + 1]; sample, hypothesis and inlier indices
+// are local to each problem, and every per-problem result equals a Context over that problem's
+// points bit for bit.  Not copyable.
+class MultiContext {
+public:
+    // one problem's round outputs: counts / sums of R * modelSlots() slots, and the round's best
+    struct Round {
+        std::vector<int32_t> counts;
+        std::vector<float> sums;
+        std::vector<usac_record> best;
+    };
+
+    MultiContext(ESTIMATOR est, const float *points, const std::vector<uint32_t> &offsets, int device = 0)
+        : est_(est), offsets_(offsets) {
+        const uint32_t P = offsets.empty() ? 0u : (uint32_t)(offsets.size() - 1);
+        const int rc = usac_multi_create(&mc_, device, (int)est, points, offsets.data(), P);
+        if (rc != USAC_OK) throw Error(rc, "usac_multi_create failed");
+    }
+    ~MultiContext() {
+        if (mc_) usac_multi_destroy(mc_);
+    }
+    MultiContext(const MultiContext &) = delete;
+    MultiContext &operator=(const MultiContext &) = delete;
+
+    usac_multi *get() const { return mc_; }
+    unsigned int problems() const { return usac_multi_num_problems(mc_); }
+    unsigned int sampleSize() const { return est_ == Fundamental ? 7u : 4u; }
+    unsigned int modelSlots() const { return est_ == Fundamental ? 3u : 1u; }
+    unsigned int pointsSize(unsigned int p) const { return offsets_[p + 1] - offsets_[p]; }
+    void check(int rc, const char *what) const {
+        if (rc != USAC_OK) throw Error(rc, std::string(what) + ": " + usac_multi_last_error(mc_));
+    }
+
+    // one round of R hypotheses (a multiple of 64 in 64..8192) for the listed problems (empty: all,
+    // in order), device sampler keyed by seeds[i] for problems[i]; with per_hypothesis the counts
+    // and sums of every slot come back too
+    Round hypothesizeScore(uint32_t R, const std::vector<uint64_t> &seeds, uint64_t first_hyp, float thr,
+                           const std::vector<uint32_t> &active = std::vector<uint32_t>(),
+                           int dlt_mode = USAC_DLT_THIN, bool per_hypothesis = true) const {
+        const uint32_t A = active.empty() ? problems() : (uint32_t)active.size();
+        if (seeds.size() != A) throw Error(USAC_ERR_ARG, "hypothesizeScore: one seed per listed problem");
+        Round out;
+        out.best.resize(A);
+        if (per_hypothesis) {
+            out.counts.resize((size_t)A * R * modelSlots());
+            out.sums.resize(out.counts.size());
+        }
+        check(usac_multi_hypothesize_score(mc_, active.empty() ? nullptr : active.data(), A, nullptr, R, seeds.data(),
+                                           first_hyp, thr, dlt_mode, per_hypothesis ? out.counts.data() : nullptr,
+                                           per_hypothesis ? out.sums.data() : nullptr, out.best.data()),
+              "MultiContext::hypothesizeScore");
+        return out;
+    }
+
+    // usac_multi_run: batch-granular RANSAC with the standard termination criterion (uniform device
+    // sampler; no SPRT / LO / polish); seeds empty: model.seed + p
+    std::vector<usac_multi_output> run(const Model &model, const std::vector<uint64_t> &seeds = std::vector<uint64_t>()) const {
+        usac_params p = model.params();
+        p.seed = model.seed;
+        if (!seeds.empty() && seeds.size() != problems()) throw Error(USAC_ERR_ARG, "run: one seed per problem");
+        std::vector<usac_multi_output> out(problems());
+        check(usac_multi_run(mc_, &p, seeds.empty() ? nullptr : seeds.data(), out.data()), "MultiContext::run");
+        return out;
+    }
+
+    // ascending inlier indices (local to each problem) of each problem's model (P x 9 floats)
+    std::vector<std::vector<int> > inliers(const float *models, float thr) const {
+        const unsigned int P = problems();
+        std::vector<uint8_t> mask(offsets_[P]);
+        check(usac_multi_inliers(mc_, models, thr, mask.data(), nullptr), "MultiContext::inliers");
+        std::vector<std::vector<int> > out(P);
+        for (unsigned int p = 0; p < P; p++)
+            for (uint32_t i = offsets_[p]; i < offsets_[p + 1]; i++)
+                if (mask[i]) out[p].push_back((int)(i - offsets_[p]));
+        return out;
+    }
+
+private:
+    usac_multi *mc_ = nullptr;
+    ESTIMATOR est_;
+    std::vector<uint32_t> offsets_;
+};
+
 }  // namespace usac_gpu
 
 #endif  // USAC_GPU_HPP

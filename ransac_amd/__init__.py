@@ -16,7 +16,7 @@ import subprocess
 import numpy as np
 
 __all__ = ["ESTIMATOR", "SAMPLER", "LocOpt", "NeighborsSearch", "DLT", "Model", "Ransac", "RansacOutput", "Score", "Context", "Record",
-           "RandomGenerator", "Sampler", "TerminationCriteria", "SPRT", "LocalOptimization", "SprtState",
+           "RandomGenerator", "Sampler", "TerminationCriteria", "SPRT", "LocalOptimization", "SprtState", "MultiContext",
            "build", "lib", "std_termination", "uniform_samples", "prosac_samples", "sprt_pool", "UsacError"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -104,6 +104,12 @@ class _RunOutput(ctypes.Structure):
                 ("spec_wasted", ctypes.c_uint32)]
 
 
+class _MultiOutput(ctypes.Structure):
+    """usac_multi_output (include/usac_gpu.h): one problem's result of usac_multi_run."""
+    _fields_ = [("best", Record), ("hypotheses", ctypes.c_uint32), ("rounds", ctypes.c_uint32),
+                ("bound", ctypes.c_uint32), ("status", ctypes.c_int32)]
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -121,6 +127,8 @@ ABI_SYMBOLS = [
     "usac_sprt_verify", "usac_sprt_upper_bound", "usac_sprt_stats", "usac_sprt_replay", "usac_sprt_destroy",
     "usac_lo_create", "usac_lo_get_model_score", "usac_lo_iters", "usac_lo_destroy", "usac_batch_sprt_info",
     "usac_selftest_rpoly", "usac_selftest_logexp", "usac_set_timing",
+    "usac_multi_create", "usac_multi_destroy", "usac_multi_last_error", "usac_multi_num_problems",
+    "usac_multi_hypothesize_score", "usac_multi_run", "usac_multi_inliers",
 ]
 
 
@@ -217,6 +225,15 @@ def lib():
         "usac_lo_get_model_score": (ctypes.c_int, [_vp, f32p, i32p, f32p]),
         "usac_lo_iters": (ctypes.c_int, [_vp, u32p, u32p]),
         "usac_lo_destroy": (None, [_vp]),
+        "usac_multi_create": (ctypes.c_int, [_P(_vp), ctypes.c_int, ctypes.c_int, f32p, u32p, ctypes.c_uint32]),
+        "usac_multi_destroy": (None, [_vp]),
+        "usac_multi_last_error": (ctypes.c_char_p, [_vp]),
+        "usac_multi_num_problems": (ctypes.c_uint32, [_vp]),
+        "usac_multi_hypothesize_score": (ctypes.c_int, [_vp, u32p, ctypes.c_uint32, i32p, ctypes.c_uint32,
+                                                        _P(ctypes.c_uint64), ctypes.c_uint64, ctypes.c_float,
+                                                        ctypes.c_int, i32p, f32p, _P(Record)]),
+        "usac_multi_run": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput)]),
+        "usac_multi_inliers": (ctypes.c_int, [_vp, f32p, ctypes.c_float, u8p, i32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -559,6 +576,117 @@ class Context:
         allr = (Record * self.nranks)()
         self._check(lib().usac_exchange_best_wait(self._h, slot, allr), "exchange_best_wait")
         return list(allr)
+
+
+class MultiContext:
+    """P independent two-view problems of one estimator (Homography or Fundamental) on one device,
+    run together (include/usac_gpu.h usac_multi_*): point_sets is a list of n_p x 4 arrays, stored as
+    one concatenated array plus offsets.  Sample, hypothesis and inlier indices are local to each
+    problem, and every per-problem result equals a Context over that problem's points bit for bit."""
+
+    def __init__(self, estimator, point_sets, device=0):
+        L = lib()
+        self.estimator = ESTIMATOR(estimator)
+        sets = [np.ascontiguousarray(p, dtype=np.float32) for p in point_sets]
+        for p in sets:
+            if p.ndim != 2 or p.shape[1] != 4:
+                raise ValueError("every point set must be n x 4")
+        self.P = len(sets)
+        self.sizes = np.array([len(p) for p in sets], dtype=np.int64)
+        self.offsets = np.zeros(self.P + 1, dtype=np.uint32)
+        self.offsets[1:] = np.cumsum(self.sizes)
+        self.points = np.concatenate(sets, axis=0) if sets else np.zeros((0, 4), np.float32)
+        self.points = np.ascontiguousarray(self.points, dtype=np.float32)
+        self.dlt_mode = DLT.THIN
+        self._h = None
+        h = _vp()
+        rc = L.usac_multi_create(ctypes.byref(h), device, int(self.estimator), _ptr(self.points, ctypes.c_float),
+                                 _ptr(self.offsets, ctypes.c_uint32), self.P)
+        if rc != 0:
+            raise UsacError(rc, "usac_multi_create(device=%d, estimator=%s, P=%d) failed (bad arguments, or no "
+                                "usable GPU)" % (device, self.estimator.name, self.P))
+        self._h = h
+        self.m = 7 if self.estimator == ESTIMATOR.Fundamental else 4
+        self.spk = 3 if self.estimator == ESTIMATOR.Fundamental else 1
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().usac_multi_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = lib().usac_multi_last_error(self._h)
+            raise UsacError(rc, "%s: %s" % (what, msg.decode() if msg else ""))
+
+    def set_dlt_mode(self, mode):
+        self.dlt_mode = DLT(mode)
+
+    def hypothesize_score(self, R, seeds=None, first_hyp=0, thr=2.0, problems=None, samples=None,
+                          per_hypothesis=True):
+        """One round of R hypotheses (a multiple of 64 in 64..8192) for the listed problems (None:
+        all, in order): seeds[i] keys the device sampler of problems[i]; samples (A x R x m, indices
+        local to each problem) replace it.  Returns (counts A x R*spk, sums, list of A best-record
+        dicts); counts and sums are None without per_hypothesis."""
+        A = self.P if problems is None else len(problems)
+        pr = None if problems is None else np.ascontiguousarray(problems, dtype=np.uint32)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != A:
+            raise ValueError("seeds: one per listed problem (%d), got %d" % (A, sd.size))
+        sm = None
+        if samples is not None:
+            sm = np.ascontiguousarray(samples, dtype=np.int32)
+            if sm.size != A * R * self.m:
+                raise ValueError("samples must be %d x %d x %d" % (A, R, self.m))
+        c = np.zeros((A, R * self.spk), dtype=np.int32) if per_hypothesis else None
+        s = np.zeros((A, R * self.spk), dtype=np.float32) if per_hypothesis else None
+        best = (Record * max(A, 1))()
+        self._check(lib().usac_multi_hypothesize_score(
+            self._h, _ptr(pr, ctypes.c_uint32), A, _ptr(sm, ctypes.c_int32), R, _ptr(sd, ctypes.c_uint64), first_hyp,
+            ctypes.c_float(thr), int(self.dlt_mode), _ptr(c, ctypes.c_int32), _ptr(s, ctypes.c_float), best),
+            "multi_hypothesize_score")
+        return c, s, [best[i].as_dict() for i in range(A)]
+
+    def run(self, model_or_params, seeds=None):
+        """usac_multi_run: batch-granular RANSAC with the standard termination criterion over all
+        problems (uniform device sampler; no SPRT / LO / polish).  model_or_params: a Model or a
+        usac_params structure; seeds default to model.seed + p.  Returns a list of P dicts: best
+        (record dict), hypotheses, rounds, bound, status."""
+        if isinstance(model_or_params, _Params):
+            p = model_or_params
+        else:
+            p = _params(model_or_params)
+            p.seed = model_or_params.seed  # the default seeds are seed + p, never a random one
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != self.P:
+            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
+        out = (_MultiOutput * self.P)()
+        self._check(lib().usac_multi_run(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out), "multi_run")
+        return [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
+                 "bound": int(o.bound), "status": int(o.status)} for o in out]
+
+    def inliers(self, models, thr):
+        """Ascending inlier indices (local to each problem) of each problem's model (P x 9), by the
+        residual of Context.get_inliers: a list of P int32 arrays."""
+        m = np.ascontiguousarray(models, dtype=np.float32).reshape(self.P, 9)
+        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8)
+        cnt = np.zeros(self.P, dtype=np.int32)
+        self._check(lib().usac_multi_inliers(self._h, _ptr(m, ctypes.c_float), ctypes.c_float(thr),
+                                             _ptr(mask, ctypes.c_uint8), _ptr(cnt, ctypes.c_int32)), "multi_inliers")
+        o = self.offsets
+        return [np.flatnonzero(mask[int(o[p]):int(o[p + 1])]).astype(np.int32) for p in range(self.P)]
 
 
 def record_better(a, b):

@@ -3975,3 +3975,264 @@ void usac_lo_destroy(usac_lo *h) {
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- multi-problem batches (ABI 15)
+// P independent two-view problems in one context (kernels_multi.hip): the usac_hypothesize_score
+// round over (active problem, hypothesis tile), and a batch-granular RANSAC whose host loop only
+// reads the active problems' records once per round, evaluates the standard termination criterion
+// and uploads the compacted active list.  One stream; every buffer is sized once per call, for
+// (active problems) x R, none inside the round loop.
+
+struct usac_multi {
+    int device = 0;
+    int estimator = 0;
+    uint32_t P = 0, m = 0, spk = 1, n_total = 0;
+    hipStream_t stream = nullptr;
+    std::vector<uint32_t> offsets;  // host copy, P + 1
+    DevBuf pts, offs, items, samples, models, counts, sums, list, list_n, out, running, mmodels, m18, mask;
+    void *pin = nullptr;  // pinned staging: the active list up, the records down
+    size_t pin_bytes = 0;
+    std::string err;
+};
+
+namespace {
+
+int fail(usac_multi *mc, int code, const std::string &msg) {
+    if (mc) mc->err = msg;
+    return code;
+}
+
+bool multi_round_ok(uint32_t R) { return R >= 64 && R <= 8192 && R % 64 == 0; }
+
+// device buffers and pinned staging for a round of A active problems x R hypotheses
+int multi_ensure(usac_multi *mc, uint32_t A, uint32_t R, bool host_samples) {
+    const size_t G = (size_t)A * R, S = G * mc->spk;
+    HIP_TRY(mc, mc->items.reserve(sizeof(usac::MultiItem) * (size_t)A));
+    if (host_samples) HIP_TRY(mc, mc->samples.reserve(sizeof(int32_t) * G * mc->m));
+    HIP_TRY(mc, mc->models.reserve(sizeof(float) * S * (mc->estimator == USAC_HOMOGRAPHY ? 18 : 9)));
+    HIP_TRY(mc, mc->counts.reserve(sizeof(int32_t) * S));
+    HIP_TRY(mc, mc->sums.reserve(sizeof(float) * S));
+    HIP_TRY(mc, mc->out.reserve(sizeof(usac_record) * (size_t)A));
+    if (mc->estimator == USAC_FUNDAMENTAL) {
+        HIP_TRY(mc, mc->list.reserve(sizeof(uint32_t) * S));
+        HIP_TRY(mc, mc->list_n.reserve(sizeof(uint32_t) * (size_t)A));
+    }
+    const size_t need = (sizeof(usac::MultiItem) + sizeof(usac_record)) * (size_t)A;
+    if (need > mc->pin_bytes) {
+        if (mc->pin) PinnedPool::get().give_back(mc->pin, mc->pin_bytes);
+        mc->pin_bytes = 0;
+        mc->pin = PinnedPool::get().take(need, &mc->pin_bytes);
+        if (!mc->pin) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
+    }
+    return USAC_OK;
+}
+
+usac::MultiItem *multi_items_pin(usac_multi *mc) { return static_cast<usac::MultiItem *>(mc->pin); }
+usac_record *multi_records_pin(usac_multi *mc, uint32_t A_cap) {
+    return reinterpret_cast<usac_record *>(multi_items_pin(mc) + A_cap);
+}
+
+usac::MultiRound multi_round(usac_multi *mc, uint32_t A, uint32_t R, uint64_t first_hyp, float thr, int dlt_mode) {
+    usac::MultiRound r{};
+    r.estimator = mc->estimator;
+    r.nullspace = dlt_mode == USAC_DLT_NULLSPACE;
+    r.pts = mc->pts.as<float4>();
+    r.offsets = mc->offs.as<uint32_t>();
+    r.items = mc->items.as<usac::MultiItem>();
+    r.A = A;
+    r.R = R;
+    r.first_hyp = first_hyp;
+    r.thr = thr;
+    r.models = mc->models.as<float>();
+    r.counts = mc->counts.as<int32_t>();
+    r.sums = mc->sums.as<float>();
+    r.list = mc->list.as<uint32_t>();
+    r.list_n = mc->list_n.as<uint32_t>();
+    r.out = mc->out.as<usac_record>();
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int usac_multi_create(usac_multi **out, int device, int estimator, const float *pts, const uint32_t *offsets,
+                      uint32_t P) {
+    if (!out) return USAC_ERR_ARG;
+    *out = nullptr;
+    if (estimator != USAC_HOMOGRAPHY && estimator != USAC_FUNDAMENTAL) return USAC_ERR_UNSUPPORTED;
+    const uint32_t m = estimator == USAC_FUNDAMENTAL ? 7 : 4;
+    if (P == 0 || P > usac::kMultiMaxActive || !pts || !offsets || offsets[0] != 0) return USAC_ERR_ARG;
+    for (uint32_t p = 0; p < P; p++)
+        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] < m) return USAC_ERR_ARG;
+    usac_multi *mc = new usac_multi();
+    mc->device = device;
+    mc->estimator = estimator;
+    mc->P = P;
+    mc->m = m;
+    mc->spk = estimator == USAC_FUNDAMENTAL ? 3 : 1;
+    mc->n_total = offsets[P];
+    mc->offsets.assign(offsets, offsets + P + 1);
+    hipError_t e = hipSetDevice(device);
+    const char *what = "hipSetDevice";
+    if (e == hipSuccess) {
+        e = StreamPool::get().stream(&mc->stream);
+        what = "hipStreamCreate";
+    }
+    if (e == hipSuccess) {
+        e = mc->pts.reserve(sizeof(float) * 4 * (size_t)mc->n_total);
+        what = "hipMalloc points";
+    }
+    if (e == hipSuccess) e = mc->offs.reserve(sizeof(uint32_t) * ((size_t)P + 1));
+    if (e == hipSuccess) e = mc->running.reserve(sizeof(usac_record) * (size_t)P);
+    if (e == hipSuccess) {
+        e = hipMemcpy(mc->pts.p, pts, sizeof(float) * 4 * (size_t)mc->n_total, hipMemcpyHostToDevice);
+        what = "hipMemcpy";
+    }
+    if (e == hipSuccess) e = hipMemcpy(mc->offs.p, offsets, sizeof(uint32_t) * ((size_t)P + 1), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        fprintf(stderr, "usac_multi_create: %s: %s\n", what, hipGetErrorString(e));
+        usac_multi_destroy(mc);
+        return USAC_ERR_HIP;
+    }
+    *out = mc;
+    return USAC_OK;
+}
+
+void usac_multi_destroy(usac_multi *mc) {
+    if (!mc) return;
+    (void)hipSetDevice(mc->device);
+    if (mc->stream) (void)hipStreamSynchronize(mc->stream);
+    if (mc->pin) PinnedPool::get().give_back(mc->pin, mc->pin_bytes);
+    for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
+                      &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask})
+        b->release();
+    if (mc->stream) StreamPool::get().give_back(mc->stream);
+    delete mc;
+}
+
+const char *usac_multi_last_error(const usac_multi *mc) { return mc ? mc->err.c_str() : "null context"; }
+uint32_t usac_multi_num_problems(const usac_multi *mc) { return mc ? mc->P : 0; }
+
+int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint32_t n_problems,
+                                 const int32_t *samples, uint32_t R, const uint64_t *seeds, uint64_t first_hyp,
+                                 float thr, int dlt_mode, int32_t *counts, float *sums, usac_record *best) {
+    if (!mc) return USAC_ERR_ARG;
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
+    if (dlt_mode != USAC_DLT_THIN && dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    if (!problems && n_problems != 0 && n_problems != mc->P)
+        return fail(mc, USAC_ERR_ARG, "problems == NULL means all problems: n_problems must be P or 0");
+    const uint32_t A = problems ? n_problems : mc->P;
+    if (A == 0 || A > usac::kMultiMaxActive) return fail(mc, USAC_ERR_ARG, "n_problems out of range");
+    if (!samples && !seeds) return fail(mc, USAC_ERR_ARG, "seeds are required with the device sampler");
+    for (uint32_t a = 0; a < A; a++) {
+        const uint32_t p = problems ? problems[a] : a;
+        if (p >= mc->P) return fail(mc, USAC_ERR_ARG, "problem index out of range");
+        if (!samples) continue;
+        const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
+        const int32_t *s = samples + (size_t)a * R * mc->m;
+        for (size_t i = 0; i < (size_t)R * mc->m; i++)
+            if (s[i] < 0 || (uint32_t)s[i] >= n) return fail(mc, USAC_ERR_ARG, "sample index out of range");
+    }
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    int rc = multi_ensure(mc, A, R, samples != nullptr);
+    if (rc) return rc;
+    usac::MultiItem *items = multi_items_pin(mc);
+    for (uint32_t a = 0; a < A; a++) items[a] = usac::MultiItem{problems ? problems[a] : a, 0u, seeds ? seeds[a] : 0ull};
+    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
+                               mc->stream));
+    const size_t G = (size_t)A * R, S = G * mc->spk;
+    if (samples)
+        HIP_TRY(mc, hipMemcpyAsync(mc->samples.p, samples, sizeof(int32_t) * G * mc->m, hipMemcpyHostToDevice,
+                                   mc->stream));
+    usac::MultiRound r = multi_round(mc, A, R, first_hyp, thr, dlt_mode);
+    r.samples_in = samples ? mc->samples.as<int32_t>() : nullptr;
+    HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
+    if (counts) HIP_TRY(mc, hipMemcpyAsync(counts, mc->counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, mc->stream));
+    if (sums) HIP_TRY(mc, hipMemcpyAsync(sums, mc->sums.p, sizeof(float) * S, hipMemcpyDeviceToHost, mc->stream));
+    if (best)
+        HIP_TRY(mc, hipMemcpyAsync(best, mc->out.p, sizeof(usac_record) * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return USAC_OK;
+}
+
+int usac_multi_run(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out) {
+    if (!mc || !prm || !out) return USAC_ERR_ARG;
+    if (prm->sprt || prm->lo != USAC_LO_NONE || prm->sampler != USAC_SAMPLER_UNIFORM)
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run: uniform sampler only, no SPRT, no LO");
+    const uint32_t R = prm->batch ? prm->batch : 256u;
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
+    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    const uint32_t P = mc->P;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    int rc = multi_ensure(mc, P, R, false);
+    if (rc) return rc;
+    // every problem's running record starts invalid (all zero), as a round without a model leaves it
+    HIP_TRY(mc, hipMemsetAsync(mc->running.p, 0, sizeof(usac_record) * (size_t)P, mc->stream));
+    usac::MultiItem *items = multi_items_pin(mc);
+    usac_record *recs = multi_records_pin(mc, P);
+    for (uint32_t p = 0; p < P; p++) {
+        items[p] = usac::MultiItem{p, 0u, seeds ? seeds[p] : (uint64_t)prm->seed + p};
+        out[p] = usac_multi_output{};
+    }
+    const usac::StandardTerminationCriteria term(prm->desired_prob, mc->m, 0, prm->max_iterations);
+    uint32_t A = P;
+    for (uint32_t round = 0; A > 0; round++) {
+        HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
+                                   mc->stream));
+        usac::MultiRound r = multi_round(mc, A, R, (uint64_t)round * R, prm->threshold, prm->dlt_mode);
+        r.running = mc->running.as<usac_record>();
+        HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
+        HIP_TRY(mc, hipMemcpyAsync(recs, mc->out.p, sizeof(usac_record) * (size_t)A,
+                                   hipMemcpyDeviceToHost, mc->stream));
+        HIP_TRY(mc, stream_wait(mc->stream));
+        const uint64_t done = ((uint64_t)round + 1) * R;
+        uint32_t keep = 0;
+        for (uint32_t a = 0; a < A; a++) {
+            const uint32_t p = items[a].problem;
+            const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
+            const uint32_t bound = term.getUpBoundIterations((uint32_t)recs[a].inliers, n);
+            if (done >= std::min(prm->max_iterations, bound)) {
+                usac_multi_output &o = out[p];
+                o.best = recs[a];
+                o.hypotheses = (uint32_t)done;
+                o.rounds = round + 1;
+                o.bound = bound;
+                o.status = recs[a].inliers > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
+            } else {
+                items[keep++] = items[a];  // the compacted active list of the next round
+            }
+        }
+        A = keep;
+    }
+    return USAC_OK;
+}
+
+int usac_multi_inliers(usac_multi *mc, const float *models, float thr, uint8_t *mask, int32_t *counts) {
+    if (!mc || !models || (!mask && !counts)) return USAC_ERR_ARG;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    HIP_TRY(mc, mc->mmodels.reserve(sizeof(float) * 9 * (size_t)mc->P));
+    HIP_TRY(mc, mc->m18.reserve(sizeof(float) * 18 * (size_t)mc->P));
+    HIP_TRY(mc, mc->mask.reserve(mc->n_total));
+    HIP_TRY(mc, hipMemcpyAsync(mc->mmodels.p, models, sizeof(float) * 9 * (size_t)mc->P, hipMemcpyHostToDevice,
+                               mc->stream));
+    HIP_TRY(mc, usac::launch_multi_mask(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), mc->P,
+                                        mc->n_total, mc->mmodels.as<float>(), thr, mc->m18.as<float>(),
+                                        mc->mask.as<uint8_t>()));
+    std::vector<uint8_t> tmp;
+    if (!mask) {
+        tmp.resize(mc->n_total);
+        mask = tmp.data();
+    }
+    HIP_TRY(mc, hipMemcpyAsync(mask, mc->mask.p, mc->n_total, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    if (counts)
+        for (uint32_t p = 0; p < mc->P; p++) {
+            int32_t c = 0;
+            for (uint32_t i = mc->offsets[p]; i < mc->offsets[p + 1]; i++) c += mask[i];
+            counts[p] = c;
+        }
+    return USAC_OK;
+}
+
+}  // extern "C"

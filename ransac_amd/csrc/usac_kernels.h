@@ -329,6 +329,37 @@ hipError_t launch_nonminimal_batch(hipStream_t st, int estimator, const void *pt
 size_t nonminimal_partial_stride(uint32_t nmax);
 size_t nonminimal_seq_bytes(uint32_t nmax, uint32_t W);
 
+// Multi-problem batches (kernels_multi.hip): P problems' points concatenated (offsets[P + 1]), one
+// round = solve + one-chunk exact score + per-problem argmax over the A active entries x R
+// hypotheses (R a multiple of 64, A <= kMultiMaxActive: the launch grid's y extent).
+constexpr uint32_t kMultiMaxActive = 65535;
+struct MultiItem {
+    uint32_t problem, pad;
+    uint64_t seed;  // the problem's device-sampler seed (draw_sample's key with the hypothesis index)
+};
+struct MultiRound {
+    int estimator;  // USAC_HOMOGRAPHY | USAC_FUNDAMENTAL
+    int nullspace;  // H: USAC_DLT_NULLSPACE
+    const float4 *pts;
+    const uint32_t *offsets;
+    const MultiItem *items;
+    uint32_t A, R;
+    const int32_t *samples_in;  // nullable: A x R x m indices local to each problem; else the device sampler
+    uint64_t first_hyp;
+    float thr;
+    float *models;              // SoA slab over the launch: H [18][A R], F [9][3 A R]
+    int32_t *counts;            // A x R x spk
+    float *sums;
+    uint32_t *list, *list_n;    // F: occupied slots, 3 R per entry, and their numbers [A]
+    usac_record *running;       // nullable, indexed by problem: the round's best is folded into it
+    usac_record *out;           // [A]: the merged record (running given) or the round's record
+};
+hipError_t launch_multi_round(hipStream_t st, const MultiRound &r);
+// per-point inlier flags of each problem's model (models P x 9 row-major, device; m18 = P x 18
+// floats of scratch): the residual of launch_inliers, H^-1 by inv3x3
+hipError_t launch_multi_mask(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,
+                             uint32_t n_total, const float *models, float thr, float *m18, uint8_t *mask);
+
 // k nearest neighbours of every point (kernels_knn.hip, nearest_neighbors.cpp:69-128):
 // idx / d2 (nullable) n x k, self excluded, ascending distance, ties by index; 1 <= k <= 32
 constexpr uint32_t kKnnMax = 32;

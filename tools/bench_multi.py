@@ -1,0 +1,127 @@
+#!/usr/bin/env python
+"""Multi-problem batches against a loop over single contexts, same box, same process, same inputs.
+
+  python tools/bench_multi.py --pairs 512 --points 1000 --round 256 --estimator homography
+
+(a) MultiContext.run: batch-granular RANSAC over all pairs, one launch chain per round.
+(b) the same schedule -- per pair, rounds of R hypotheses until min(max_iterations, standard bound)
+    is reached -- as a loop over one Context per pair with hypothesize_score(per_hypothesis=False),
+    the fastest existing way.  The contexts are created outside the timed window.
+
+Both are warmed up, then alternated for --reps repetitions each; a repetition is timed with a host
+clock around work that ends in a device synchronise (both calls return after their last copy).
+The per-pair best inlier counts of (a) and (b) must agree.  Prints one JSON line (and writes it to
+--out): median and spread (max - min) of each, and the ratio of the medians.  The baseline is (b)
+in the same job, never (a) itself; (a) counts as faster only beyond the larger of the two spreads.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import ransac_amd as usac  # noqa: E402
+from ransac_amd import synthetic  # noqa: E402
+
+
+def make_pairs(estimator, pairs, points, ratio):
+    if estimator == "homography":
+        return [synthetic.homography_points(n=points, inlier_ratio=ratio, seed=1000 + p)[0] for p in range(pairs)]
+    return [synthetic.fundamental_points(n=points, inlier_ratio=ratio, seed=1000 + p, prosac_order=False)[0]
+            for p in range(pairs)]
+
+
+def loop_run(ctxs, m, seeds, R, thr, prob, max_iters):
+    """method (b): usac_multi_run's schedule, one pair at a time"""
+    best = []
+    for ctx, seed in zip(ctxs, seeds):
+        inl, r = 0, 0
+        while True:
+            rec = ctx.hypothesize_score(B=R, seed=seed, first_hyp=r * R, thr=thr, per_hypothesis=False)[2]
+            if rec["valid"] and rec["inliers"] > inl:
+                inl = rec["inliers"]
+            r += 1
+            if r * R >= min(max_iters, usac.std_termination(inl, ctx.n, m, prob, max_iters)):
+                break
+        best.append((inl, r))
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=512)
+    ap.add_argument("--points", type=int, default=1000)
+    ap.add_argument("--round", type=int, default=256, dest="R")
+    ap.add_argument("--estimator", choices=["homography", "fundamental"], default="homography")
+    ap.add_argument("--inlier-ratio", type=float, default=0.3)
+    ap.add_argument("--max-iterations", type=int, default=2048)
+    ap.add_argument("--dlt", choices=["thin", "nullspace"], default="nullspace")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.reps < 5:
+        ap.error("--reps must be at least 5")
+
+    est = usac.ESTIMATOR.Homography if a.estimator == "homography" else usac.ESTIMATOR.Fundamental
+    thr, prob = 2.0, 0.95
+    sets = make_pairs(a.estimator, a.pairs, a.points, a.inlier_ratio)
+    model = usac.Model(thr, 4 if a.estimator == "homography" else 7, prob, 5, est, usac.SAMPLER.Uniform)
+    model.max_iterations, model.batch, model.seed = a.max_iterations, a.R, 1
+    model.setDLTMode(usac.DLT.NULLSPACE if a.dlt == "nullspace" else usac.DLT.THIN)
+    seeds = [model.seed + p for p in range(a.pairs)]
+
+    mc = usac.MultiContext(est, sets)
+    ctxs = [usac.Context(est, p) for p in sets]
+    for c in ctxs:
+        c.set_dlt_mode(model.dlt_mode)
+        c.set_timing(False)
+
+    def run_a():
+        return [(r["best"]["inliers"], r["rounds"]) for r in mc.run(model)]
+
+    def run_b():
+        return loop_run(ctxs, mc.m, seeds, a.R, thr, prob, a.max_iterations)
+
+    for _ in range(a.warmup):
+        ra, rb = run_a(), run_b()
+    ta, tb = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        ra = run_a()
+        t1 = time.perf_counter()
+        rb = run_b()
+        t2 = time.perf_counter()
+        ta.append((t1 - t0) * 1e3)
+        tb.append((t2 - t1) * 1e3)
+    agree = [x[0] for x in ra] == [x[0] for x in rb]
+    ma, mb = statistics.median(ta), statistics.median(tb)
+    sa, sb = max(ta) - min(ta), max(tb) - min(tb)
+    line = {"bench": "multi", "estimator": a.estimator, "pairs": a.pairs, "points": a.points, "round": a.R,
+            "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio, "dlt": a.dlt, "reps": a.reps,
+            "multi_ms": round(ma, 3), "multi_spread_ms": round(sa, 3), "loop_ms": round(mb, 3),
+            "loop_spread_ms": round(sb, 3), "ratio_loop_over_multi": round(mb / ma, 2),
+            "multi_faster_beyond_spread": bool(mb - ma > max(sa, sb)),
+            "hypotheses": int(sum(x[1] for x in ra)) * a.R, "mean_rounds": round(float(np.mean([x[1] for x in ra])), 2),
+            "best_inliers_agree": bool(agree)}
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    mc.close()
+    for c in ctxs:
+        c.close()
+    return 0 if agree else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
