@@ -28,7 +28,8 @@
 //
 // A kept pair goes to the exact stage B of k_score_hf (stage_b: v_rcp / v_sqrt with the guard band,
 // the reference's own expression inside it) through a per-wave LDS queue of (hypothesis, point)
-// entries, drained 64 at a time so every lane of the drain works (kept pairs are ~0.1 % of all).
+// entries (a 1024-entry ring for two tiles per wave), drained 64 at a time so every lane of the
+// drain works (kept pairs are ~0.1 % of all); a drain lane reads its model from the batch's table.
 // Counts are exact; Σ adds stage B's terms as 2^-k fixed point (integer adds: deterministic, an
 // error of one unit per term), per point chunk, the chunks summed by k_h16_finish.
 #include <hip/hip_runtime.h>
@@ -47,9 +48,15 @@ namespace usac {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// queue entries per wave: a ring of < 64 waiting entries plus one iteration's appends (<= 64 per row)
-template <int NA, int U>
-constexpr uint32_t h16_queue() { return 64u * 5u * NA * U + 64u; }
+// queue entries per wave: a power-of-two ring (the wrap is one AND) that holds the < 64 entries
+// waiting for a full drain plus one 32-point block's appends (<= 64 per mask, 5 NA masks per block;
+// full groups are drained after every block)
+template <int NA>
+constexpr uint32_t h16_queue() {
+    uint32_t q = 64;
+    while (q < 64u * 5u * NA + 64u) q *= 2;
+    return q;
+}
 
 // ------------------------------------------------------------------------ dataset constants
 // One workgroup (once per context, at its first h16 batch; no host pass over the points): the
@@ -213,7 +220,7 @@ hipError_t launch_h16_rows(hipStream_t st, const float *models, uint32_t B, cons
 }
 
 // ------------------------------------------------------------------------ the scorer
-// LDS ordering inside one wave (the queue, the model table, the counters): a workgroup-scope fence
+// LDS ordering inside one wave (the queue, the counters): a workgroup-scope fence
 // waits for the wave's LDS operations and keeps the compiler from moving them across
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -222,23 +229,26 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 // Drain `cnt` (<= 64) queue entries from `head`: lane i evaluates entry head + i exactly (stage_b,
 // throughput mode: S ~ 2 err, or the exact 2 err inside the band) and adds its inlier to the
-// hypothesis' LDS counters (count, Σ in 2^-fxs fixed point).
+// hypothesis' LDS counters (count, Σ in 2^-fxs fixed point).  The lane reads its hypothesis' 18
+// coefficients (H, H^-1) straight from the batch's model table -- `mw` = the wave's first column of
+// it, L2-resident, and a wave drains only a few times -- the loads and the point's issued together.
 template <uint32_t Q>
-__device__ __forceinline__ void h16_drain(uint32_t cnt, uint32_t head, uint32_t *q, const float (*sh)[20],
-                                          uint32_t *sc, unsigned long long *ss, const float4 *__restrict__ pts,
-                                          float T, float thr, double fxs) {
+__device__ __forceinline__ void h16_drain(uint32_t cnt, uint32_t head, const uint32_t *q,
+                                          const float *__restrict__ mw, uint32_t B, uint32_t hlast, uint32_t *sc,
+                                          unsigned long long *ss, const float4 *__restrict__ pts, float T, float thr,
+                                          double fxs) {
     const uint32_t lane = threadIdx.x & 63;
     wave_lds_sync();
     if (lane < cnt) {
-        const uint32_t qi = head + lane;  // head < Q
-        const uint32_t e = q[qi >= Q ? qi - Q : qi];
+        const uint32_t e = q[(head + lane) & (Q - 1)];
         const uint32_t hk = e >> 25, p = e & 0x1FFFFFFu;
+        const uint32_t hc = hk < hlast ? hk : hlast;  // entries exist for hypotheses < B only; stays in the table
         const float4 pt = pts[p];
         HModel M;
 #pragma unroll
         for (int c = 0; c < 9; c++) {
-            M.h[c] = sh[hk][c];
-            M.hi[c] = sh[hk][9 + c];
+            M.h[c] = mw[(size_t)c * B + hc];
+            M.hi[c] = mw[(size_t)(9 + c) * B + hc];
         }
         // the point's guard band, as k_prepare_rec writes it
         const float mp = fabsf(pt.x) + fabsf(pt.y) + fabsf(pt.z) + fabsf(pt.w);
@@ -267,52 +277,70 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                                                    uint32_t B, float thr, double fxs, uint32_t *__restrict__ cpart,
                                                    unsigned long long *__restrict__ spart) {
     constexpr int HW = 10 * NA;
-    __shared__ float sH[4][HW][20];
+    constexpr uint32_t Q = h16_queue<NA>();
+    __shared__ uint32_t sQ[4][Q];
     __shared__ uint32_t sC[4][HW];
     __shared__ unsigned long long sS[4][HW];
-    constexpr uint32_t Q = h16_queue<NA, U>();
-    __shared__ uint32_t sQ[4][Q];
     const uint32_t lane = threadIdx.x & 63, hf = lane >> 5;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t hb = (blockIdx.x * 4 + wave) * HW;
     const float T = 2.0f * thr;
-    if (lane < HW) {
-        const uint32_t h = hb + lane;
-#pragma unroll
-        for (int c = 0; c < 18; c++) sH[wave][lane][c] = h < B ? models[(size_t)c * B + h] : 0.f;
-        sC[wave][lane] = 0;
-        sS[wave][lane] = 0;
-    }
+    const uint32_t nblk = (n + 31) / 32, nch = gridDim.y, ch = blockIdx.y;
+    const uint32_t per = (nblk + nch - 1) / nch;
+    const uint32_t b0 = ch * per < nblk ? ch * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
+    // The prologue's loads are unconditional -- a clamped index, the value masked afterwards -- so that all of them
+    // (the A rows, the slacks, the first feature blocks) are in flight before the first wait.
     half8 A[NA];
     float F[NA][5];
     {
         const uint32_t rho = lane & 31, rh = (rho >> 2) & 1, i = (rho & 3) + 4 * (rho >> 3);
         const uint32_t t = 5 * rh + i / 3, r = i % 3;
+        half8 ld[NA];
+        float fl[NA][5];
 #pragma unroll
         for (int a = 0; a < NA; a++) {
             const uint32_t h = hb + 10 * a + t;
-            half8 z;
-#pragma unroll
-            for (int j = 0; j < 8; j++) z[j] = (_Float16)0.0f;
-            A[a] = (i < 15 && h < B) ? rows[((size_t)h * 3 + r) * 2 + hf] : z;
+            ld[a] = rows[((size_t)(h < B ? h : B - 1) * 3 + r) * 2 + hf];
 #pragma unroll
             for (int j = 0; j < 5; j++) {
                 const uint32_t hj = hb + 10 * a + 5 * hf + j;
-                F[a][j] = hj < B ? fm[hj] : -1.0f;  // a missing hypothesis keeps nothing (0 <= -1 is false)
+                fl[a][j] = fm[hj < B ? hj : B - 1];
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < NA; a++) {
+            const uint32_t h = hb + 10 * a + t;
+            // zero rows by a bit mask, not a select of the load (which the compiler turns back into a branch)
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            const uint32_t on = (i < 15 && h < B) ? ~0u : 0u;
+            A[a] = __builtin_bit_cast(half8, __builtin_bit_cast(u32x4, ld[a]) & on);
+#pragma unroll
+            for (int j = 0; j < 5; j++) {
+                const uint32_t hj = hb + 10 * a + 5 * hf + j;
+                // a missing hypothesis keeps nothing: its slack is -inf (or NaN), and 0 <= -inf is false.
+                // An add, not a select of the load (same reason); F + 0 compares as F does (F >= 0).
+                F[a][j] = fl[a][j] + (hj < B ? 0.0f : -INFINITY);
             }
         }
     }
-    const uint32_t nblk = (n + 31) / 32, nch = gridDim.y, ch = blockIdx.y;
-    const uint32_t per = (nblk + nch - 1) / nch;
-    const uint32_t b0 = ch * per < nblk ? ch * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
-    uint32_t qn = 0, qh = 0;
-    const f32x16 zero = {};
-    wave_lds_sync();
     // U 32-point blocks per iteration (their MFMAs issue back to back, then all the tests), the next
     // iteration's blocks' features loaded while this iteration's tiles are tested
     half8 bn[U];
 #pragma unroll
-    for (int u = 0; u < U; u++) bn[u] = b0 + u < b1 ? feat[(size_t)(b0 + u) * 64 + lane] : half8{};
+    for (int u = 0; u < U; u++) {
+        const uint32_t bu = b0 + u < nblk ? b0 + u : nblk - 1;  // used only when b0 + u < b1 <= nblk
+        bn[u] = feat[(size_t)bu * 64 + lane];
+    }
+    if (lane < HW) {
+        sC[wave][lane] = 0;
+        sS[wave][lane] = 0;
+    }
+    // the drains' view of the model table: the wave's first column, and its last hypothesis' slot
+    const uint32_t hbc = hb < B ? hb : B - 1, hlast = B - 1 - hbc;
+    const float *__restrict__ mw = models + hbc;
+    uint32_t qn = 0, qh = 0;
+    const f32x16 zero = {};
+    wave_lds_sync();
     for (uint32_t blk = b0; blk < b1; blk += U) {
         half8 bf[U];
 #pragma unroll
@@ -326,6 +354,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
 #pragma unroll
             for (int a = 0; a < NA; a++) acc[u][a] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[a], bf[u], zero, 0, 0, 0);
         uint64_t msk[U][NA][5], any = 0;
+        bool keep[U][NA][5];
 #pragma unroll
         for (int u = 0; u < U; u++)
 #pragma unroll
@@ -334,35 +363,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 for (int j = 0; j < 5; j++) {
                     // keep iff |ex| <= R and |ey| <= R, R = |zr| + F: two compares with |.| source
                     // modifiers (a max would first canonicalise both operands in IEEE mode); a block
-                    // past the chunk's end keeps nothing
+                    // past the chunk's end keeps nothing.  The lane's own predicate stays beside the
+                    // ballot (the same lane mask): the append runs under it as its exec mask.
                     const float R = fabsf(acc[u][a][3 * j + 2]) + F[a][j];
-                    msk[u][a][j] = blk + u < b1 ? __builtin_amdgcn_ballot_w64(fabsf(acc[u][a][3 * j]) <= R) &
-                                                      __builtin_amdgcn_ballot_w64(fabsf(acc[u][a][3 * j + 1]) <= R)
-                                                : 0;
+                    const bool live = blk + u < b1, kx = fabsf(acc[u][a][3 * j]) <= R,
+                               ky = fabsf(acc[u][a][3 * j + 1]) <= R;
+                    keep[u][a][j] = live && kx && ky;
+                    // (a ballot of each compare: a ballot of the combined predicate costs two more VALU)
+                    msk[u][a][j] = live ? __builtin_amdgcn_ballot_w64(kx) & __builtin_amdgcn_ballot_w64(ky) : 0;
                     any |= msk[u][a][j];
                 }
         if (__builtin_expect(any != 0, 0)) {  // append the kept pairs, draining full groups of 64 per block
 #pragma unroll
             for (int u = 0; u < U; u++) {
-                const uint32_t point = (blk + u) * 32 + (lane & 31);
+                // the entry of slot 10 a + 5 hf + j: the lane's part once per block, (10 a + j) << 25 a literal
+                const uint32_t ent = ((5u * hf) << 25) | ((blk + u) * 32 + (lane & 31));
 #pragma unroll
                 for (int a = 0; a < NA; a++)
 #pragma unroll
                     for (int j = 0; j < 5; j++) {
                         const uint64_t mk = msk[u][a][j];
-                        if (mk) {
-                            const uint32_t below = __builtin_amdgcn_mbcnt_hi(
-                                (uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                            if ((mk >> lane) & 1) {
-                                const uint32_t qi = qh + qn + below;  // < 2 Q
-                                sQ[wave][qi >= Q ? qi - Q : qi] = ((uint32_t)(10 * a + 5 * hf + j) << 25) | point;
-                            }
-                            qn += (uint32_t)__builtin_popcountll(mk);
+                        if (!mk) continue;  // (uniform: an empty mask costs a scalar compare and a branch)
+                        if (keep[u][a][j]) {  // position = ring tail + kept lanes below (the tail seeds the count)
+                            const uint32_t qi = __builtin_amdgcn_mbcnt_hi(
+                                (uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, qh + qn));
+                            sQ[wave][qi & (Q - 1)] = ent + ((uint32_t)(10 * a + j) << 25);
                         }
+                        qn += (uint32_t)__builtin_popcountll(mk);
                     }
                 while (qn >= 64) {
-                    h16_drain<Q>(64, qh, sQ[wave], sH[wave], sC[wave], sS[wave], pts, T, thr, fxs);
-                    qh = qh + 64 >= Q ? qh + 64 - Q : qh + 64;
+                    h16_drain<Q>(64, qh, sQ[wave], mw, B, hlast, sC[wave], sS[wave], pts, T, thr, fxs);
+                    qh = (qh + 64) & (Q - 1);
                     qn -= 64;
                 }
             }
@@ -370,8 +401,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     }
     while (qn) {
         const uint32_t d = qn < 64 ? qn : 64;
-        h16_drain<Q>(d, qh, sQ[wave], sH[wave], sC[wave], sS[wave], pts, T, thr, fxs);
-        qh = qh + d >= Q ? qh + d - Q : qh + d;
+        h16_drain<Q>(d, qh, sQ[wave], mw, B, hlast, sC[wave], sS[wave], pts, T, thr, fxs);
+        qh = (qh + d) & (Q - 1);
         qn -= d;
     }
     wave_lds_sync();
