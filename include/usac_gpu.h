@@ -47,7 +47,10 @@
  *                                  (local_optimization.hpp:19)
  *   usac_multi_*                   new (ABI 15): P independent two-view problems per launch -- the
  *                                  usac_hypothesize_score round and a batch-granular RANSAC with the
- *                                  standard termination criterion over a ragged set of point sets
+ *                                  standard termination criterion over a ragged set of point sets;
+ *                                  ABI 16: usac_multi_polish / usac_multi_run_polished, the non-minimal
+ *                                  polish and final getInliers of ransac.cpp:157-214 for every
+ *                                  problem in one launch (one workgroup per problem)
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -62,7 +65,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 15
+#define USAC_ABI_VERSION 16
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -466,7 +469,7 @@ int usac_exchange_best_wait(usac_ctx *ctx, uint32_t slot, usac_record *all);
 /* Merge n records by Score::bigger, earliest hyp_index on exact ties. */
 int usac_merge_records(const usac_record *recs, uint32_t n, usac_record *best);
 
-/* ---- multi-problem batches (ABI 15) ------------------------------------------------------
+/* ---- multi-problem batches (ABI 15; polish: ABI 16) ------------------------------------------------------
  * A multi context holds P independent two-view problems of one estimator (USAC_HOMOGRAPHY or
  * USAC_FUNDAMENTAL; line and essential: USAC_ERR_UNSUPPORTED) and runs them together: one launch
  * whose grid covers (problem, 64-hypothesis tile).  Points are one concatenated N_total x 4 fp32
@@ -518,14 +521,47 @@ int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint3
  * problem is finished once (r + 1) R >= min(max_iterations, bound_p).  The clamp to max_iterations is
  * a deviation from ransac.cpp, which lets the bound exceed it: a batch call must stay bounded.  A run
  * evaluates at least as many hypotheses as the bound asks for, so the confidence guarantee holds.
- * This is NOT the glibc-stream Ransac::run (usac_ransac_run): no SPRT, LO, PROSAC, NAPSAC or polish
- * -- params->sprt, ->lo or a sampler other than USAC_SAMPLER_UNIFORM return USAC_ERR_UNSUPPORTED.
+ * This is NOT the glibc-stream Ransac::run (usac_ransac_run): no SPRT, LO, PROSAC or NAPSAC --
+ * params->sprt, ->lo or a sampler other than USAC_SAMPLER_UNIFORM return USAC_ERR_UNSUPPORTED -- and it
+ * stops at the best minimal model; usac_multi_run_polished adds the run's non-minimal polish.
  * Reads threshold, desired_prob, max_iterations, dlt_mode, seed and batch (= R, 0 = 256).
  * out: P results. */
 int usac_multi_run(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out);
 /* Per-point inlier flags of each problem's model (models P x 9, mask N_total bytes of 0 / 1, counts
  * P, nullable) from the residual of usac_get_inliers; for H, H^-1 is the device inv3x3 of the given H. */
 int usac_multi_inliers(usac_multi *mc, const float *models, float thr, uint8_t *mask, int32_t *counts);
+
+/* One problem's result of usac_multi_polish (ABI 16). */
+typedef struct usac_multi_polish_output {
+    float   model[9];          /* best model after the polish (= the start model when no pass is accepted) */
+    int32_t inliers;  float score;                  /* its count and sequential Σ at thr */
+    int32_t minimal_inliers; float minimal_score;   /* the start model's */
+    int32_t passes;            /* accepted passes, 0..4 */
+    int32_t status;            /* USAC_OK, or USAC_ERR_NO_MODEL when the start model has no inlier */
+} usac_multi_polish_output;
+
+/* The end of Ransac::run (ransac.cpp:157-214) for every problem, from its start model (models: P x 9):
+ * getInliers(start) gives the list and its count c0; then up to four passes, each a non-minimal fit
+ * (usac_nonminimal) on the first `best` entries of the current list and a getInliers of the fitted
+ * model -- stopped by a failed fit, by (float)c / (float)best < 0.8 or by c <= the last accepted
+ * count, otherwise the fitted model, its count, Σ and list are accepted -- and the final getInliers
+ * of the accepted model.  c0 = 0: status USAC_ERR_NO_MODEL, the start model returned, no fit.  Every
+ * value has the bits the same loop over usac_get_inliers / usac_nonminimal of a usac_ctx over the
+ * problem's points gives.  One launch, one workgroup per problem, for n_p <= 16384 and lists to fit of
+ * <= 4096 points; a problem past either cap is polished through a temporary single context over its
+ * points (same result, a host loop for that problem only).
+ * out: P results.  mask (nullable): N_total bytes of 0 / 1, the final getInliers of out[p].model.
+ * NULL mc, models or out: USAC_ERR_ARG before any device call. */
+int usac_multi_polish(usac_multi *mc, const float *models, float thr,
+                      usac_multi_polish_output *out, uint8_t *mask);
+
+/* usac_multi_run, then the polish of every problem's best model at params->threshold without the
+ * records leaving the device in between; out as usac_multi_run writes it (unchanged), pol / mask as
+ * usac_multi_polish (a problem without a model: USAC_ERR_NO_MODEL in both).  The remaining deviations
+ * from Ransac::run are usac_multi_run's: no SPRT, LO, PROSAC or NAPSAC, batch-granular termination.
+ * NULL mc, params, out or pol: USAC_ERR_ARG before any device call. */
+int usac_multi_run_polished(usac_multi *mc, const usac_params *params, const uint64_t *seeds,
+                            usac_multi_output *out, usac_multi_polish_output *pol, uint8_t *mask);
 
 /* ---- self-test hooks (ABI 13) ------------------------------------------------------- */
 /* The essential 5-point solver's root step alone (five_points.cpp:139-157: rpoly_ak1's real zeros

@@ -583,7 +583,7 @@ public:
     }
 
     // usac_multi_run: batch-granular RANSAC with the standard termination criterion (uniform device
-    // sampler; no SPRT / LO / polish); seeds empty: model.seed + p
+    // sampler; no SPRT / LO; the polish: runPolished); seeds empty: model.seed + p
     std::vector<usac_multi_output> run(const Model &model, const std::vector<uint64_t> &seeds = std::vector<uint64_t>()) const {
         usac_params p = model.params();
         p.seed = model.seed;
@@ -605,7 +605,53 @@ public:
         return out;
     }
 
+    // usac_multi_polish: the non-minimal polish of ransac.cpp:157-214 for every problem from its start
+    // model (P x 9 floats), one workgroup per problem; inliers (nullable): the final getInliers of
+    // each polished model, ascending indices local to the problem
+    std::vector<usac_multi_polish_output> polish(const float *models, float thr,
+                                                 std::vector<std::vector<int> > *inliers = nullptr) const {
+        const unsigned int P = problems();
+        std::vector<usac_multi_polish_output> out(P);
+        std::vector<uint8_t> mask(inliers ? offsets_[P] : 0u);
+        check(usac_multi_polish(mc_, models, thr, out.data(), inliers ? mask.data() : nullptr), "MultiContext::polish");
+        if (inliers) splitMask(mask, inliers);
+        return out;
+    }
+
+    // one problem's result of runPolished: run()'s output and polish()'s of its best model
+    struct Polished {
+        std::vector<usac_multi_output> run;
+        std::vector<usac_multi_polish_output> polished;
+        std::vector<std::vector<int> > inliers;
+    };
+
+    // usac_multi_run_polished: run(), then the polish of every best model at the model's threshold
+    // (the records stay on the device in between)
+    Polished runPolished(const Model &model, const std::vector<uint64_t> &seeds = std::vector<uint64_t>()) const {
+        usac_params p = model.params();
+        p.seed = model.seed;
+        const unsigned int P = problems();
+        if (!seeds.empty() && seeds.size() != P) throw Error(USAC_ERR_ARG, "runPolished: one seed per problem");
+        Polished out;
+        out.run.resize(P);
+        out.polished.resize(P);
+        std::vector<uint8_t> mask(offsets_[P]);
+        check(usac_multi_run_polished(mc_, &p, seeds.empty() ? nullptr : seeds.data(), out.run.data(),
+                                      out.polished.data(), mask.data()),
+              "MultiContext::runPolished");
+        splitMask(mask, &out.inliers);
+        return out;
+    }
+
 private:
+    void splitMask(const std::vector<uint8_t> &mask, std::vector<std::vector<int> > *out) const {
+        const unsigned int P = problems();
+        out->assign(P, std::vector<int>());
+        for (unsigned int p = 0; p < P; p++)
+            for (uint32_t i = offsets_[p]; i < offsets_[p + 1]; i++)
+                if (mask[i]) (*out)[p].push_back((int)(i - offsets_[p]));
+    }
+
     usac_multi *mc_ = nullptr;
     ESTIMATOR est_;
     std::vector<uint32_t> offsets_;

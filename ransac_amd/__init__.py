@@ -110,6 +110,28 @@ class _MultiOutput(ctypes.Structure):
                 ("bound", ctypes.c_uint32), ("status", ctypes.c_int32)]
 
 
+class _MultiPolishOutput(ctypes.Structure):
+    """usac_multi_polish_output (include/usac_gpu.h): one problem's result of usac_multi_polish."""
+    _fields_ = [("model", ctypes.c_float * 9), ("inliers", ctypes.c_int32), ("score", ctypes.c_float),
+                ("minimal_inliers", ctypes.c_int32), ("minimal_score", ctypes.c_float), ("passes", ctypes.c_int32),
+                ("status", ctypes.c_int32)]
+
+    DTYPE = np.dtype([("model", np.float32, (9,)), ("inliers", np.int32), ("score", np.float32),
+                      ("minimal_inliers", np.int32), ("minimal_score", np.float32), ("passes", np.int32),
+                      ("status", np.int32)])
+
+    @classmethod
+    def as_dicts(cls, arr):
+        """a ctypes array of results -> a list of dicts (model: float32[9], score / minimal_score:
+        np.float32, the rest ints), through one numpy view instead of a field read per value"""
+        a = np.frombuffer(arr, dtype=cls.DTYPE).copy()
+        models, score, mscore = np.ascontiguousarray(a["model"]), a["score"], a["minimal_score"]
+        cols = [a[k].tolist() for k in ("inliers", "minimal_inliers", "passes", "status")]
+        return [{"model": models[p], "inliers": cols[0][p], "score": score[p], "minimal_inliers": cols[1][p],
+                 "minimal_score": mscore[p], "passes": cols[2][p], "status": cols[3][p]}
+                for p in range(len(a))]
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -128,7 +150,8 @@ ABI_SYMBOLS = [
     "usac_lo_create", "usac_lo_get_model_score", "usac_lo_iters", "usac_lo_destroy", "usac_batch_sprt_info",
     "usac_selftest_rpoly", "usac_selftest_logexp", "usac_set_timing",
     "usac_multi_create", "usac_multi_destroy", "usac_multi_last_error", "usac_multi_num_problems",
-    "usac_multi_hypothesize_score", "usac_multi_run", "usac_multi_inliers",
+    "usac_multi_hypothesize_score", "usac_multi_run", "usac_multi_inliers", "usac_multi_polish",
+    "usac_multi_run_polished",
 ]
 
 
@@ -234,6 +257,9 @@ def lib():
                                                         ctypes.c_int, i32p, f32p, _P(Record)]),
         "usac_multi_run": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput)]),
         "usac_multi_inliers": (ctypes.c_int, [_vp, f32p, ctypes.c_float, u8p, i32p]),
+        "usac_multi_polish": (ctypes.c_int, [_vp, f32p, ctypes.c_float, _P(_MultiPolishOutput), u8p]),
+        "usac_multi_run_polished": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
+                                                   _P(_MultiPolishOutput), u8p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -659,11 +685,40 @@ class MultiContext:
             "multi_hypothesize_score")
         return c, s, [best[i].as_dict() for i in range(A)]
 
-    def run(self, model_or_params, seeds=None):
+    def _split_mask(self, mask):
+        """N_total mask bytes -> per problem the ascending local indices of its set bytes"""
+        o = self.offsets.astype(np.int64)
+        idx = np.flatnonzero(mask.view(np.bool_))  # the bytes are 0 / 1; nonzero is far faster on bool
+        cuts = np.searchsorted(idx, o)
+        local = (idx - np.repeat(o[:-1], np.diff(cuts))).astype(np.int32)
+        c = cuts.tolist()
+        return [local[c[p]:c[p + 1]] for p in range(self.P)]
+
+    def polish(self, models, thr, with_inliers=False):
+        """usac_multi_polish: the non-minimal polish of ransac.cpp:157-214 for every problem from its
+        start model (P x 9), one workgroup per problem.  Returns a list of P dicts: model, inliers,
+        score, minimal_inliers, minimal_score (the start model's), passes, status (-111 when the
+        start model has no inlier) -- and, with_inliers, "inlier_idx": the final getInliers of the
+        model, ascending indices local to the problem."""
+        m = np.ascontiguousarray(models, dtype=np.float32).reshape(self.P, 9)
+        out = (_MultiPolishOutput * self.P)()
+        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if with_inliers else None
+        self._check(lib().usac_multi_polish(self._h, _ptr(m, ctypes.c_float), ctypes.c_float(thr), out,
+                                            _ptr(mask, ctypes.c_uint8)), "multi_polish")
+        res = _MultiPolishOutput.as_dicts(out)
+        if with_inliers:
+            for r, idx in zip(res, self._split_mask(mask)):
+                r["inlier_idx"] = idx
+        return res
+
+    def run(self, model_or_params, seeds=None, polish=False):
         """usac_multi_run: batch-granular RANSAC with the standard termination criterion over all
-        problems (uniform device sampler; no SPRT / LO / polish).  model_or_params: a Model or a
+        problems (uniform device sampler; no SPRT / LO).  model_or_params: a Model or a
         usac_params structure; seeds default to model.seed + p.  Returns a list of P dicts: best
-        (record dict), hypotheses, rounds, bound, status."""
+        (record dict), hypotheses, rounds, bound, status.  polish=True (usac_multi_run_polished)
+        adds the non-minimal polish of every best model at the run's threshold: each dict gains
+        "polished" (polish()'s dict) and "inliers" (the polished model's inliers, ascending local
+        indices)."""
         if isinstance(model_or_params, _Params):
             p = model_or_params
         else:
@@ -673,9 +728,20 @@ class MultiContext:
         if sd is not None and sd.size != self.P:
             raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
         out = (_MultiOutput * self.P)()
-        self._check(lib().usac_multi_run(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out), "multi_run")
-        return [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
-                 "bound": int(o.bound), "status": int(o.status)} for o in out]
+        if polish:
+            pol = (_MultiPolishOutput * self.P)()
+            mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8)
+            self._check(lib().usac_multi_run_polished(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, pol,
+                                                      _ptr(mask, ctypes.c_uint8)), "multi_run_polished")
+        else:
+            self._check(lib().usac_multi_run(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out), "multi_run")
+        res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
+                "bound": int(o.bound), "status": int(o.status)} for o in out]
+        if polish:
+            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
+                r["polished"] = po
+                r["inliers"] = idx
+        return res
 
     def inliers(self, models, thr):
         """Ascending inlier indices (local to each problem) of each problem's model (P x 9), by the
@@ -685,8 +751,7 @@ class MultiContext:
         cnt = np.zeros(self.P, dtype=np.int32)
         self._check(lib().usac_multi_inliers(self._h, _ptr(m, ctypes.c_float), ctypes.c_float(thr),
                                              _ptr(mask, ctypes.c_uint8), _ptr(cnt, ctypes.c_int32)), "multi_inliers")
-        o = self.offsets
-        return [np.flatnonzero(mask[int(o[p]):int(o[p + 1])]).astype(np.int32) for p in range(self.P)]
+        return self._split_mask(mask)
 
 
 def record_better(a, b):

@@ -1282,6 +1282,125 @@ hipError_t launch_polish_fused(hipStream_t st, int estimator, const void *pts, u
     return hipGetLastError();
 }
 
+// The polish of a multi context (DESIGN.md "Multi-problem batches"): k_polish_fused's workgroup,
+// one per problem.  Problem p's points are the slice offsets[p] .. offsets[p + 1] of the
+// concatenated array and its indices are local; its start model is models[p * model_stride ..
+// + 8] (a P x 9 array, or the model field of the run's device records).  The loop is
+// ransac.cpp:157-214 with the break taken on the device: getInliers(start) -> (list, c0), then up
+// to four passes of pol_fit on the first `best` entries of the current list and pol_score of the
+// fitted model into the other list, stopped by a failed fit, (float)c / (float)best < 0.8 or
+// c <= prev (k_polish_prep's expression), else the lists swap.  The current list then is the
+// accepted model's own getInliers (same pol_score, model and threshold), which the mask is written
+// from.  Every value comes from the device pieces k_polish_fused runs, so a problem's result has
+// the bits of the single-context path.  A problem past the workgroup's caps (n_p > kPolPtsMax, or
+// a list to fit > kPolFitMax) writes status kMultiPolishDefer and nothing else: the host takes
+// those problems through the single-context kernels.
+template <int EST>
+__global__ __launch_bounds__(kPolT) void k_multi_polish(const float4 *__restrict__ pts_all,
+                                                        const uint32_t *__restrict__ offsets,
+                                                        const float *__restrict__ models, uint32_t model_stride,
+                                                        float thr, int32_t *__restrict__ lists, uint32_t n_total,
+                                                        usac_multi_polish_output *__restrict__ out,
+                                                        uint8_t *__restrict__ mask) {
+    constexpr bool FUND = EST != USAC_HOMOGRAPHY;
+    __shared__ __attribute__((aligned(16))) float4 s_q[kPolFitMax];
+    __shared__ __attribute__((aligned(16))) double s_d[kPolSbWin * 64 * 45 > 2 * kPolFitMax ? kPolSbWin * 64 * 45
+                                                                                            : 2 * kPolFitMax];
+    __shared__ double s_part[(kPolFitMax / 1024) * 45];
+    __shared__ double A[9][9], V[9][9], s_v[9], s_psum[8 * 64 / kPolC];
+    __shared__ float s_R[kPolT], s_sums[8], s_ws[18], s_model[18], s_sum[1], s_best[9];
+    __shared__ uint32_t s_wc[8 * (kPolT / 64)];
+    __shared__ int32_t s_ok;
+    PolShared sh;
+    sh.Q = s_q;
+    sh.D = s_d;
+    sh.E = reinterpret_cast<float *>(s_d);
+    sh.part = s_part;
+    sh.psum = s_psum;
+    sh.R = s_R;
+    sh.wc = s_wc;
+    sh.dbg = nullptr;
+    const uint32_t t = threadIdx.x, p = blockIdx.x;
+    const uint32_t base = offsets[p], N = offsets[p + 1] - base;
+    usac_multi_polish_output *o = out + p;
+    if (N > kPolPtsMax) {  // workgroup-uniform
+        if (t == 0) o->status = kMultiPolishDefer;
+        return;
+    }
+    const float4 *__restrict__ pts = pts_all + base;
+    int32_t *cur = lists + base, *nxt = lists + (size_t)n_total + base;
+    if (t == 0) {  // inl_model: the model, H^-1 for H
+        for (int k = 0; k < 9; k++) s_best[k] = s_model[k] = models[(size_t)p * model_stride + k];
+        if (EST == USAC_HOMOGRAPHY) inv3x3(s_model, s_model + 9);
+    }
+    __syncthreads();
+    const uint32_t c0 = pol_score<EST>(pts, N, s_model, thr, cur, sh);
+    pol_seq<1, false>(sh.E, 0, c0, sh, s_sum);
+    const float sum0 = s_sum[0];
+    int32_t best = (int32_t)c0, prev = 0, passes = 0;
+    float best_sum = sum0;
+    bool defer = false;
+    constexpr int kPasses = 4;
+    for (int k = 0; k < kPasses && c0 > 0; k++) {
+        if ((uint32_t)best > kPolFitMax) {  // workgroup-uniform
+            defer = true;
+            break;
+        }
+        pol_fit<FUND>(pts, cur, (uint32_t)best, sh, s_sums, s_ws, A, V, s_v, s_model, &s_ok, nullptr);
+        if (!s_ok) break;
+        if (EST == USAC_HOMOGRAPHY && t == 0) inv3x3(s_model, s_model + 9);
+        __syncthreads();
+        const int32_t cnt = (int32_t)pol_score<EST>(pts, N, s_model, thr, nxt, sh);
+        pol_seq<1, false>(sh.E, 0, (uint32_t)cnt, sh, s_sum);
+        if ((double)((float)cnt / (float)best) < 0.8 || cnt <= prev) break;
+        prev = best = cnt;
+        best_sum = s_sum[0];
+        passes++;
+        if (t == 0)
+            for (int j = 0; j < 9; j++) s_best[j] = s_model[j];
+        int32_t *sw = cur;
+        cur = nxt;
+        nxt = sw;
+        __syncthreads();  // s_ok, s_model and s_sum are rewritten by the next pass
+    }
+    if (defer) {
+        if (t == 0) o->status = kMultiPolishDefer;
+        return;
+    }
+    if (mask) {  // the final getInliers(best model): `cur`
+        uint8_t *m = mask + base;
+        for (uint32_t i = t; i < N; i += kPolT) m[i] = 0;
+        __syncthreads();  // (global writes of this workgroup, ordered by the barrier's release)
+        for (uint32_t i = t; i < (uint32_t)best; i += kPolT) m[cur[i]] = 1;
+    }
+    if (t == 0) {
+        for (int j = 0; j < 9; j++) o->model[j] = s_best[j];
+        o->inliers = best;
+        o->score = best_sum;
+        o->minimal_inliers = (int32_t)c0;
+        o->minimal_score = sum0;
+        o->passes = passes;
+        o->status = c0 > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
+    }
+}
+
+hipError_t launch_multi_polish(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,
+                               uint32_t n_total, const float *models, uint32_t model_stride, float thr, int32_t *lists,
+                               usac_multi_polish_output *out, uint8_t *mask) {
+    if (P == 0) return hipErrorInvalidValue;
+    switch (estimator) {
+        case USAC_HOMOGRAPHY:
+            hipLaunchKernelGGL(k_multi_polish<USAC_HOMOGRAPHY>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, lists, n_total, out, mask);
+            break;
+        case USAC_FUNDAMENTAL:
+            hipLaunchKernelGGL(k_multi_polish<USAC_FUNDAMENTAL>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, lists, n_total, out, mask);
+            break;
+        default:
+            return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 // getInliers of ONE model over N <= kPolPtsMax points in one workgroup (pol_score + the Σerr
 // chain), for launch_inliers_batch's single-model calls with sums: one launch instead of five
 // (flags, compact, and the three launches of the Σ chain), the same list, count and sum bits.

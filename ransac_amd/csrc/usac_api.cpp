@@ -3976,7 +3976,7 @@ void usac_lo_destroy(usac_lo *h) {
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- multi-problem batches (ABI 15)
+// ---------------------------------------------------------------- multi-problem batches (ABI 15, 16)
 // P independent two-view problems in one context (kernels_multi.hip): the usac_hypothesize_score
 // round over (active problem, hypothesis tile), and a batch-granular RANSAC whose host loop only
 // reads the active problems' records once per round, evaluates the standard termination criterion
@@ -3990,8 +3990,11 @@ struct usac_multi {
     hipStream_t stream = nullptr;
     std::vector<uint32_t> offsets;  // host copy, P + 1
     DevBuf pts, offs, items, samples, models, counts, sums, list, list_n, out, running, mmodels, m18, mask;
+    DevBuf pol_lists, pol_out;  // the polish: two inlier lists per problem (2 x N_total), P results
     void *pin = nullptr;  // pinned staging: the active list up, the records down
     size_t pin_bytes = 0;
+    void *pol_pin = nullptr;  // pinned staging of the polish: P results and the mask down
+    size_t pol_pin_bytes = 0;
     std::string err;
 };
 
@@ -4052,6 +4055,89 @@ usac::MultiRound multi_round(usac_multi *mc, uint32_t A, uint32_t R, uint64_t fi
     return r;
 }
 
+// The polish of one problem past k_multi_polish's caps: the loop of ransac.cpp:157-214 over
+// usac_get_inliers / usac_nonminimal of a temporary single context on the problem's points (the
+// multi-launch kernels, any n and any list size; the same bits as the fused workgroup where both
+// apply).  mask_p (nullable): the problem's n_p mask bytes.
+int multi_polish_single(usac_multi *mc, uint32_t p, const float *start, float thr, usac_multi_polish_output *o,
+                        uint8_t *mask_p) {
+    const uint32_t base = mc->offsets[p], n = mc->offsets[p + 1] - base;
+    std::vector<float> pts(4 * (size_t)n);
+    HIP_TRY(mc, hipMemcpy(pts.data(), mc->pts.as<float>() + 4 * (size_t)base, sizeof(float) * 4 * (size_t)n,
+                          hipMemcpyDeviceToHost));
+    usac_ctx *c = nullptr;
+    int rc = usac_create(&c, mc->device, mc->estimator, pts.data(), n, 4);
+    if (rc) return fail(mc, rc, "usac_multi_polish: no single context for a problem past the fused caps");
+    std::vector<int32_t> cur(n), nxt(n);
+    uint32_t c0 = 0, cnt = 0;
+    float s0 = 0.f, s = 0.f;
+    auto done = [&](int code, const char *what) {
+        if (code) fail(mc, code, std::string("usac_multi_polish: ") + what + ": " + usac_last_error(c));
+        usac_destroy(c);
+        return code;
+    };
+    if ((rc = usac_get_inliers(c, start, thr, cur.data(), &c0, &s0))) return done(rc, "get_inliers");
+    *o = usac_multi_polish_output{};
+    memcpy(o->model, start, sizeof(o->model));
+    o->inliers = o->minimal_inliers = (int32_t)c0;
+    o->score = o->minimal_score = s0;
+    o->status = c0 > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
+    int32_t prev = 0;
+    for (int k = 0; k < 4 && c0 > 0; k++) {
+        float nm[9];
+        rc = usac_nonminimal(c, cur.data(), (uint32_t)o->inliers, nm);
+        if (rc == USAC_ERR_NO_MODEL) break;
+        if (rc) return done(rc, "nonminimal");
+        if ((rc = usac_get_inliers(c, nm, thr, nxt.data(), &cnt, &s))) return done(rc, "get_inliers");
+        if ((double)((float)(int32_t)cnt / (float)o->inliers) < 0.8 || (int32_t)cnt <= prev) break;
+        prev = o->inliers = (int32_t)cnt;
+        o->score = s;
+        memcpy(o->model, nm, sizeof(nm));
+        o->passes++;
+        cur.swap(nxt);
+    }
+    if (mask_p) {
+        memset(mask_p, 0, n);
+        for (int32_t i = 0; i < o->inliers; i++) mask_p[cur[i]] = 1;
+    }
+    return done(USAC_OK, "");
+}
+
+// usac_multi_polish on start models already on the device (dmodels + p * stride floats); hstart:
+// the same models on the host (+ p * hstride floats), read only for the problems the kernel defers
+int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, const float *hstart, size_t hstride,
+                        float thr, usac_multi_polish_output *out, uint8_t *mask) {
+    const uint32_t P = mc->P;
+    HIP_TRY(mc, mc->pol_lists.reserve(sizeof(int32_t) * 2 * (size_t)mc->n_total));
+    HIP_TRY(mc, mc->pol_out.reserve(sizeof(usac_multi_polish_output) * (size_t)P));
+    if (mask) HIP_TRY(mc, mc->mask.reserve(mc->n_total));
+    HIP_TRY(mc, usac::launch_multi_polish(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), P,
+                                          mc->n_total, dmodels, stride, thr, mc->pol_lists.as<int32_t>(),
+                                          mc->pol_out.as<usac_multi_polish_output>(),
+                                          mask ? mc->mask.as<uint8_t>() : nullptr));
+    // results and mask come down through pinned staging, then into the caller's (pageable) buffers
+    const size_t out_bytes = sizeof(usac_multi_polish_output) * (size_t)P, need = out_bytes + (mask ? mc->n_total : 0);
+    if (need > mc->pol_pin_bytes) {
+        if (mc->pol_pin) PinnedPool::get().give_back(mc->pol_pin, mc->pol_pin_bytes);
+        mc->pol_pin_bytes = 0;
+        mc->pol_pin = PinnedPool::get().take(need, &mc->pol_pin_bytes);
+        if (!mc->pol_pin) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
+    }
+    uint8_t *stage = static_cast<uint8_t *>(mc->pol_pin);
+    HIP_TRY(mc, hipMemcpyAsync(stage, mc->pol_out.p, out_bytes, hipMemcpyDeviceToHost, mc->stream));
+    if (mask) HIP_TRY(mc, hipMemcpyAsync(stage + out_bytes, mc->mask.p, mc->n_total, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    memcpy(out, stage, out_bytes);
+    if (mask) memcpy(mask, stage + out_bytes, mc->n_total);
+    for (uint32_t p = 0; p < P; p++) {
+        if (out[p].status != usac::kMultiPolishDefer) continue;
+        const int rc = multi_polish_single(mc, p, hstart + (size_t)p * hstride, thr, out + p,
+                                           mask ? mask + mc->offsets[p] : nullptr);
+        if (rc) return rc;
+    }
+    return USAC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4104,8 +4190,10 @@ void usac_multi_destroy(usac_multi *mc) {
     (void)hipSetDevice(mc->device);
     if (mc->stream) (void)hipStreamSynchronize(mc->stream);
     if (mc->pin) PinnedPool::get().give_back(mc->pin, mc->pin_bytes);
+    if (mc->pol_pin) PinnedPool::get().give_back(mc->pol_pin, mc->pol_pin_bytes);
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
-                      &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask})
+                      &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
+                      &mc->pol_out})
         b->release();
     if (mc->stream) StreamPool::get().give_back(mc->stream);
     delete mc;
@@ -4233,6 +4321,31 @@ int usac_multi_inliers(usac_multi *mc, const float *models, float thr, uint8_t *
             counts[p] = c;
         }
     return USAC_OK;
+}
+
+int usac_multi_polish(usac_multi *mc, const float *models, float thr, usac_multi_polish_output *out, uint8_t *mask) {
+    if (!mc || !models || !out) return USAC_ERR_ARG;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    HIP_TRY(mc, mc->mmodels.reserve(sizeof(float) * 9 * (size_t)mc->P));
+    HIP_TRY(mc, hipMemcpyAsync(mc->mmodels.p, models, sizeof(float) * 9 * (size_t)mc->P, hipMemcpyHostToDevice,
+                               mc->stream));
+    return multi_polish_device(mc, mc->mmodels.as<float>(), 9, models, 9, thr, out, mask);
+}
+
+int usac_multi_run_polished(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
+                            usac_multi_polish_output *pol, uint8_t *mask) {
+    if (!mc || !prm || !out || !pol) return USAC_ERR_ARG;
+    const int rc = usac_multi_run(mc, prm, seeds, out);
+    if (rc) return rc;
+    // the run's final records are the device's running records (a problem without a model: all
+    // zero, which the polish reports as USAC_ERR_NO_MODEL): their model fields are the start models
+    static_assert(offsetof(usac_record, model) % sizeof(float) == 0 && sizeof(usac_record) % sizeof(float) == 0,
+                  "usac_record's model as a strided float array");
+    static_assert(offsetof(usac_multi_output, best) % sizeof(float) == 0 && sizeof(usac_multi_output) % sizeof(float) == 0,
+                  "usac_multi_output's model as a strided float array");
+    return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
+                               sizeof(usac_record) / sizeof(float), out[0].best.model,
+                               sizeof(usac_multi_output) / sizeof(float), prm->threshold, pol, mask);
 }
 
 }  // extern "C"

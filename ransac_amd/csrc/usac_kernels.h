@@ -359,6 +359,15 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r);
 // floats of scratch): the residual of launch_inliers, H^-1 by inv3x3
 hipError_t launch_multi_mask(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,
                              uint32_t n_total, const float *models, float thr, float *m18, uint8_t *mask);
+// the non-minimal polish and final getInliers of every problem (kernels_nonmin.hip k_multi_polish:
+// k_polish_fused's workgroup, one per problem).  models: problem p's start model at models + p *
+// model_stride floats (device); lists: 2 x n_total int32 of scratch; out: P results (device); mask
+// (nullable): n_total bytes.  A problem past the workgroup's caps (n_p > kPolPtsMax, or a list to
+// fit > kPolFitMax) gets out[p].status = kMultiPolishDefer and no other output.
+constexpr int32_t kMultiPolishDefer = 1;
+hipError_t launch_multi_polish(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,
+                               uint32_t n_total, const float *models, uint32_t model_stride, float thr, int32_t *lists,
+                               usac_multi_polish_output *out, uint8_t *mask);
 
 // k nearest neighbours of every point (kernels_knn.hip, nearest_neighbors.cpp:69-128):
 // idx / d2 (nullable) n x k, self excluded, ascending distance, ties by index; 1 <= k <= 32

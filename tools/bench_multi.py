@@ -13,8 +13,13 @@ clock around work that ends in a device synchronise (both calls return after the
 The per-pair best inlier counts of (a) and (b) must agree.  Prints one JSON line (and writes it to
 --out): median and spread (max - min) of each, and the ratio of the medians.  The baseline is (b)
 in the same job, never (a) itself; (a) counts as faster only beyond the larger of the two spreads.
+
+--polish times the run with its non-minimal polish instead: MultiContext.run(polish=True), the multi
+run alone (what the polish adds), and loop (b) followed per pair by the polish restated with
+get_inliers + nonminimal.  The per-pair minimal and polished inlier counts must agree.
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -54,6 +59,119 @@ def loop_run(ctxs, m, seeds, R, thr, prob, max_iters):
     return best
 
 
+def loop_run_polished(ctxs, m, seeds, R, thr, prob, max_iters):
+    """method (b) with --polish: the schedule of loop_run keeping each pair's best record
+    (usac_merge_records' order), then the polish of ransac.cpp:157-214 restated per context with
+    get_inliers + nonminimal -- the only way to polish a batch of pairs without usac_multi_polish"""
+    out = []
+    for ctx, seed in zip(ctxs, seeds):
+        best, r = None, 0
+        while True:
+            rec = ctx.hypothesize_score(B=R, seed=seed, first_hyp=r * R, thr=thr, per_hypothesis=False)[2]
+            if rec["valid"] and (best is None or (rec["inliers"], rec["score"]) > (best["inliers"], best["score"])):
+                best = rec
+            r += 1
+            inl = best["inliers"] if best else 0
+            if r * R >= min(max_iters, usac.std_termination(inl, ctx.n, m, prob, max_iters)):
+                break
+        polished = 0
+        if best is not None:
+            c0, _, idx = ctx.get_inliers(best["model"], thr)
+            polished, prev = c0, 0
+            for _ in range(4 if c0 else 0):
+                try:
+                    nm = ctx.nonminimal(idx[:polished])
+                except usac.UsacError:
+                    break
+                c, _, idx2 = ctx.get_inliers(nm, thr)
+                if np.float32(c) / np.float32(polished) < 0.8 or c <= prev:
+                    break
+                prev = polished = c
+                idx = idx2
+        out.append((inl, r, polished))
+    return out
+
+
+def main_polish(a, mc, ctxs, model, seeds, thr, prob):
+    """--polish: (a) MultiContext.run(polish=True), (a0) MultiContext.run alone, (b) the loop over
+    contexts with the restated polish; alternated, host-timed, medians and spreads as in main()"""
+    def run_a():
+        return [(r["best"]["inliers"], r["rounds"], r["polished"]["inliers"], r["polished"]["passes"])
+                for r in mc.run(model, polish=True)]
+
+    def run_a0():
+        return mc.run(model)
+
+    def run_b():
+        return loop_run_polished(ctxs, mc.m, seeds, a.R, thr, prob, a.max_iterations)
+
+    for _ in range(a.warmup):
+        ra, _, rb = run_a(), run_a0(), run_b()
+    ta, ta0, tb = [], [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        ra = run_a()
+        t1 = time.perf_counter()
+        run_a0()
+        t2 = time.perf_counter()
+        rb = run_b()
+        t3 = time.perf_counter()
+        ta.append((t1 - t0) * 1e3)
+        ta0.append((t2 - t1) * 1e3)
+        tb.append((t3 - t2) * 1e3)
+    agree = [(x[0], x[2]) for x in ra] == [(x[0], x[2]) for x in rb]
+    # the C entry points alone (no Python result lists): run + polish with the mask, the run, and
+    # the polish of the run's best models with and without the mask
+    L, P = usac.lib(), mc.P
+    prm = usac._params(model)
+    prm.seed = model.seed
+    out, pol = (usac._MultiOutput * P)(), (usac._MultiPolishOutput * P)()
+    mask = np.zeros(int(mc.offsets[-1]), dtype=np.uint8)
+    maskp = mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+    L.usac_multi_run(mc._h, ctypes.byref(prm), None, out)
+    best = np.ascontiguousarray([o.best.model[:] for o in out], dtype=np.float32)
+    bestp = best.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    calls = {"lib_run_polished_ms": lambda: L.usac_multi_run_polished(mc._h, ctypes.byref(prm), None, out, pol, maskp),
+             "lib_run_ms": lambda: L.usac_multi_run(mc._h, ctypes.byref(prm), None, out),
+             "lib_polish_ms": lambda: L.usac_multi_polish(mc._h, bestp, ctypes.c_float(thr), pol, maskp),
+             "lib_polish_nomask_ms": lambda: L.usac_multi_polish(mc._h, bestp, ctypes.c_float(thr), pol, None)}
+    lib_ms = {}
+    for name, call in calls.items():
+        ts = []
+        for i in range(a.warmup + a.reps):
+            t0 = time.perf_counter()
+            rc = call()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            if rc != 0:
+                raise RuntimeError("%s failed: %d" % (name, rc))
+        lib_ms[name] = round(statistics.median(ts[a.warmup:]), 3)
+    ma, ma0, mb = statistics.median(ta), statistics.median(ta0), statistics.median(tb)
+    sa, sa0, sb = max(ta) - min(ta), max(ta0) - min(ta0), max(tb) - min(tb)
+    line = {"bench": "multi_polish", "estimator": a.estimator, "pairs": a.pairs, "points": a.points, "round": a.R,
+            "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio, "dlt": a.dlt, "reps": a.reps,
+            "multi_polished_ms": round(ma, 3), "multi_polished_spread_ms": round(sa, 3),
+            "multi_run_ms": round(ma0, 3), "multi_run_spread_ms": round(sa0, 3),
+            "polish_adds_ms": round(ma - ma0, 3),
+            "loop_polished_ms": round(mb, 3), "loop_polished_spread_ms": round(sb, 3),
+            "ratio_loop_over_multi": round(mb / ma, 2),
+            "multi_faster_beyond_spread": bool(mb - ma > max(sa, sb)),
+            "mean_minimal_inliers": round(float(np.mean([x[0] for x in ra])), 2),
+            "mean_polished_inliers": round(float(np.mean([x[2] for x in ra])), 2),
+            "mean_passes": round(float(np.mean([x[3] for x in ra])), 2),
+            "inliers_agree": bool(agree)}
+    line.update(lib_ms)
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    mc.close()
+    for c in ctxs:
+        c.close()
+    return 0 if agree else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=512)
@@ -66,6 +184,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--polish", action="store_true",
+                    help="time run + non-minimal polish: MultiContext.run(polish=True) against the multi run "
+                         "alone and against the loop over contexts with the polish restated per context")
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
@@ -89,6 +210,9 @@ def main():
 
     def run_b():
         return loop_run(ctxs, mc.m, seeds, a.R, thr, prob, a.max_iterations)
+
+    if a.polish:
+        return main_polish(a, mc, ctxs, model, seeds, thr, prob)
 
     for _ in range(a.warmup):
         ra, rb = run_a(), run_b()
