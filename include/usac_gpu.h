@@ -50,7 +50,12 @@
  *                                  standard termination criterion over a ragged set of point sets;
  *                                  ABI 16: usac_multi_polish / usac_multi_run_polished, the non-minimal
  *                                  polish and final getInliers of ransac.cpp:157-214 for every
- *                                  problem in one launch (one workgroup per problem)
+ *                                  problem in one launch (one workgroup per problem);
+ *                                  ABI 17: usac_multi_run_prosac, the PROSAC sampler and PROSAC's
+ *                                  termination criterion per problem (the sampler in closed form on the
+ *                                  device, the termination scan split between a kernel and the host),
+ *                                  with usac_prosac_schedule / usac_multi_draw_samples /
+ *                                  usac_multi_prosac_scan exposing its parts
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -65,7 +70,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 16
+#define USAC_ABI_VERSION 17
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -469,7 +474,7 @@ int usac_exchange_best_wait(usac_ctx *ctx, uint32_t slot, usac_record *all);
 /* Merge n records by Score::bigger, earliest hyp_index on exact ties. */
 int usac_merge_records(const usac_record *recs, uint32_t n, usac_record *best);
 
-/* ---- multi-problem batches (ABI 15; polish: ABI 16) ------------------------------------------------------
+/* ---- multi-problem batches (ABI 15; polish: ABI 16; PROSAC: ABI 17, below) ----------------------------
  * A multi context holds P independent two-view problems of one estimator (USAC_HOMOGRAPHY or
  * USAC_FUNDAMENTAL; line and essential: USAC_ERR_UNSUPPORTED) and runs them together: one launch
  * whose grid covers (problem, 64-hypothesis tile).  Points are one concatenated N_total x 4 fp32
@@ -521,9 +526,10 @@ int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint3
  * problem is finished once (r + 1) R >= min(max_iterations, bound_p).  The clamp to max_iterations is
  * a deviation from ransac.cpp, which lets the bound exceed it: a batch call must stay bounded.  A run
  * evaluates at least as many hypotheses as the bound asks for, so the confidence guarantee holds.
- * This is NOT the glibc-stream Ransac::run (usac_ransac_run): no SPRT, LO, PROSAC or NAPSAC --
- * params->sprt, ->lo or a sampler other than USAC_SAMPLER_UNIFORM return USAC_ERR_UNSUPPORTED -- and it
- * stops at the best minimal model; usac_multi_run_polished adds the run's non-minimal polish.
+ * This is NOT the glibc-stream Ransac::run (usac_ransac_run): no SPRT, LO or NAPSAC, and PROSAC is
+ * usac_multi_run_prosac's -- params->sprt, ->lo or a sampler other than USAC_SAMPLER_UNIFORM return
+ * USAC_ERR_UNSUPPORTED here -- and it stops at the best minimal model; usac_multi_run_polished adds
+ * the run's non-minimal polish.
  * Reads threshold, desired_prob, max_iterations, dlt_mode, seed and batch (= R, 0 = 256).
  * out: P results. */
 int usac_multi_run(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out);
@@ -558,10 +564,80 @@ int usac_multi_polish(usac_multi *mc, const float *models, float thr,
 /* usac_multi_run, then the polish of every problem's best model at params->threshold without the
  * records leaving the device in between; out as usac_multi_run writes it (unchanged), pol / mask as
  * usac_multi_polish (a problem without a model: USAC_ERR_NO_MODEL in both).  The remaining deviations
- * from Ransac::run are usac_multi_run's: no SPRT, LO, PROSAC or NAPSAC, batch-granular termination.
+ * from Ransac::run are usac_multi_run's: no SPRT, LO or NAPSAC (PROSAC: usac_multi_run_prosac),
+ * batch-granular termination.
  * NULL mc, params, out or pol: USAC_ERR_ARG before any device call. */
 int usac_multi_run_polished(usac_multi *mc, const usac_params *params, const uint64_t *seeds,
                             usac_multi_output *out, usac_multi_polish_output *pol, uint8_t *mask);
+
+/* ---- multi-problem batches: PROSAC (ABI 17) ---------------------------------------------------------
+ * The sampler in closed form.  With g = the reference's growth function of (n, m) (prosac_sampler.hpp:
+ * 62-114), ProsacSampler::generateSample's subset after the call with hypCount = t is
+ *     s(t) = min(n, m + #{ i in [m - 1, n) : g[i] < t }),  s(0) = m,
+ * so the sampler is a pure function of two integers per problem, both fixed for a round: the clock T
+ * (the sampler's hypCount, from 1) and the termination length L (from n_p).  Lane j of a round has
+ * t = T + j and draws, from the (seed, global hypothesis index) stream of the uniform device sampler,
+ *     t > 200000    : m distinct indices of [0, n_p)             (clock does not advance)
+ *     s(t - 1) > L  : m distinct indices of the closed [0, L]    (clock does not advance; L < n_p)
+ *     otherwise     : m - 1 distinct indices of [0, s(t) - 2] and point s(t) - 1  (a PROSAC lane)
+ * The PROSAC lanes are a prefix of the round; after it T += their number, and largest_sample_size =
+ * max(previous, s(T_old + n_prosac - 1)).
+ *
+ * usac_prosac_schedule: that rule for one problem and one round, on the host (no context, no device).
+ * subset (nullable, R): s(t) of a PROSAC lane, 0 = uniform over [0, term_len], UINT32_MAX = uniform
+ * over n.  largest (nullable): in = the previous value, out = the updated one.  USAC_ERR_ARG unless
+ * 2 <= m <= term_len <= n and clock >= 1. */
+int usac_prosac_schedule(uint32_t n, uint32_t m, uint32_t clock, uint32_t term_len, uint32_t R, uint32_t *subset,
+                         uint32_t *clock_next, uint32_t *largest);
+/* For tests: the samples the solve kernels of a round draw (the same device function), n_problems x R x
+ * m indices local to each problem.  clock == NULL: the uniform sampler of usac_multi_hypothesize_score;
+ * else the PROSAC sampler with clock[i] / term_len[i] for problems[i] (m <= term_len <= n_p).  problems,
+ * R, seeds, first_hyp as usac_multi_hypothesize_score. */
+int usac_multi_draw_samples(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t R,
+                            const uint64_t *seeds, uint64_t first_hyp, const uint32_t *clock, const uint32_t *term_len,
+                            int32_t *out);
+
+/* One problem's PROSAC state at the end of usac_multi_run_prosac. */
+typedef struct usac_multi_prosac_output {
+    uint32_t termination_length;   /* ProsacTerminationCriteria's, n_p if no scan moved it */
+    uint32_t largest_sample_size;  /* the sampler's */
+    uint32_t clock;                /* the sampler's hypCount at the end */
+    uint32_t scans;                /* rounds whose new best was scanned */
+} usac_multi_prosac_output;
+
+/* usac_multi_run with the PROSAC sampler and PROSAC's termination criterion (prosac_termination_
+ * criteria.hpp:148-201) per problem.  Every problem's points are assumed sorted by descending quality
+ * (not checked).  Per problem T = 1, L = n_p, largest = m, bound = max_iterations.  In round r every
+ * active problem evaluates hypotheses [r R, (r + 1) R) drawn under its (T, L), and its running best is
+ * merged as in usac_multi_run.  If the running best improved in the round, the device walks the
+ * problem's points under the new best (inlier flags by the residual of usac_get_inliers, the running
+ * count, non_random[i] = max(old, count_i) for i >= 20) and hands the host the raised points that end a
+ * run of inliers, in order; the host evaluates them as the reference does (its libm's log, the
+ * maximality samples, the minimum with its tie rule) with hypCount = best.hyp_index (0-based, as
+ * usac_ransac_run passes it; uint32 wrap-around in hypCount - growth[i] kept) and largest_sample_size
+ * at that hypothesis, which gives the new bound and L.  Then T and largest advance, and the problem is
+ * finished once (r + 1) R >= min(max_iterations, bound).
+ * Deviations from Ransac::run with PROSAC: batch granularity, two ways -- only a round's final best is
+ * scanned (the reference scans every new best), and L changes only between rounds (the reference's next
+ * sample already sees it); the clamp to max_iterations; the device random stream (the reference draws
+ * from std::mt19937).  No SPRT, LO or NAPSAC.
+ * USAC_ERR_UNSUPPORTED for params->sprt or ->lo; USAC_ERR_ARG for a sampler other than
+ * USAC_SAMPLER_PROSAC, any n_p <= 20 (the reference reads point 20), a bad batch or dlt_mode, NULL mc,
+ * params or out -- all before any device call.
+ * out: P results as usac_multi_run's (bound: the last scan's, max_iterations if none ran).  pro
+ * (nullable): P states.  pol (nullable): the polish of usac_multi_run_polished from the device's running
+ * records, with mask (nullable, read only with pol). */
+int usac_multi_run_prosac(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
+                          usac_multi_prosac_output *pro, usac_multi_polish_output *pol, uint8_t *mask);
+/* For tests: one termination scan of every problem, models (P x 9) taken as new bests found at
+ * hypothesis hyp_count[p] with largest_sample_size largest[p], at params->threshold.  The termination
+ * state persists in the context from call to call; reset != 0 (and any usac_multi_run_prosac) starts
+ * it afresh from params->desired_prob and ->max_iterations.  bound / term_len: P values after the
+ * scan.  n_cand (nullable): P candidate numbers; cand (nullable): N_total / 2 + P pairs (i, count),
+ * problem p's from pair offsets[p] / 2 + p, ascending i.  Every n_p > 20. */
+int usac_multi_prosac_scan(usac_multi *mc, const usac_params *params, int reset, const float *models,
+                           const uint32_t *hyp_count, const uint32_t *largest, uint32_t *bound, uint32_t *term_len,
+                           uint32_t *n_cand, uint32_t *cand);
 
 /* ---- self-test hooks (ABI 13) ------------------------------------------------------- */
 /* The essential 5-point solver's root step alone (five_points.cpp:139-157: rpoly_ak1's real zeros

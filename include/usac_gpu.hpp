@@ -643,6 +643,28 @@ public:
         return out;
     }
 
+    // one problem's result of runProsac: run()'s output and the PROSAC state at its end
+    struct Prosac {
+        std::vector<usac_multi_output> run;
+        std::vector<usac_multi_prosac_output> prosac;
+    };
+
+    // usac_multi_run_prosac: run() with the PROSAC sampler and PROSAC's termination criterion per
+    // problem (model.sampler = Prosac; every point set sorted by descending quality, n_p > 20)
+    Prosac runProsac(const Model &model, const std::vector<uint64_t> &seeds = std::vector<uint64_t>()) const {
+        usac_params p = model.params();
+        p.seed = model.seed;
+        const unsigned int P = problems();
+        if (!seeds.empty() && seeds.size() != P) throw Error(USAC_ERR_ARG, "runProsac: one seed per problem");
+        Prosac out;
+        out.run.resize(P);
+        out.prosac.resize(P);
+        check(usac_multi_run_prosac(mc_, &p, seeds.empty() ? nullptr : seeds.data(), out.run.data(), out.prosac.data(),
+                                    nullptr, nullptr),
+              "MultiContext::runProsac");
+        return out;
+    }
+
 private:
     void splitMask(const std::vector<uint8_t> &mask, std::vector<std::vector<int> > *out) const {
         const unsigned int P = problems();

@@ -132,6 +132,12 @@ class _MultiPolishOutput(ctypes.Structure):
                 for p in range(len(a))]
 
 
+class _MultiProsacOutput(ctypes.Structure):
+    """usac_multi_prosac_output (include/usac_gpu.h): one problem's PROSAC state after usac_multi_run_prosac."""
+    _fields_ = [("termination_length", ctypes.c_uint32), ("largest_sample_size", ctypes.c_uint32),
+                ("clock", ctypes.c_uint32), ("scans", ctypes.c_uint32)]
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -152,6 +158,7 @@ ABI_SYMBOLS = [
     "usac_multi_create", "usac_multi_destroy", "usac_multi_last_error", "usac_multi_num_problems",
     "usac_multi_hypothesize_score", "usac_multi_run", "usac_multi_inliers", "usac_multi_polish",
     "usac_multi_run_polished",
+    "usac_prosac_schedule", "usac_multi_draw_samples", "usac_multi_run_prosac", "usac_multi_prosac_scan",
 ]
 
 
@@ -260,6 +267,13 @@ def lib():
         "usac_multi_polish": (ctypes.c_int, [_vp, f32p, ctypes.c_float, _P(_MultiPolishOutput), u8p]),
         "usac_multi_run_polished": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
                                                    _P(_MultiPolishOutput), u8p]),
+        "usac_prosac_schedule": (ctypes.c_int, [ctypes.c_uint32] * 5 + [u32p, u32p, u32p]),
+        "usac_multi_draw_samples": (ctypes.c_int, [_vp, u32p, ctypes.c_uint32, ctypes.c_uint32, _P(ctypes.c_uint64),
+                                                   ctypes.c_uint64, u32p, u32p, i32p]),
+        "usac_multi_run_prosac": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
+                                                 _P(_MultiProsacOutput), _P(_MultiPolishOutput), u8p]),
+        "usac_multi_prosac_scan": (ctypes.c_int, [_vp, _P(_Params), ctypes.c_int, f32p, u32p, u32p, u32p, u32p, u32p,
+                                                  u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -299,6 +313,24 @@ def prosac_samples(seed, n_points, m, count, termination_length=None):
     if rc:
         raise UsacError(rc, "usac_prosac_samples")
     return out
+
+
+UNIFORM_OVER_N = 0xFFFFFFFF  # prosac_schedule: a lane past T_N = 200000
+
+
+def prosac_schedule(n, m, clock, term_len, R, largest=None):
+    """usac_prosac_schedule: one round of the multi-problem PROSAC sampler for one problem, on the host.
+    Returns (subset uint32[R], clock_next, largest): subset[j] = s(t) of a PROSAC lane, 0 for a lane
+    drawn uniformly from [0, term_len], UNIFORM_OVER_N for one drawn uniformly from all n points;
+    largest = the sampler's largest_sample_size after the round (in: its value before, default m)."""
+    sub = np.zeros(R, dtype=np.uint32)
+    nxt = ctypes.c_uint32(0)
+    lg = ctypes.c_uint32(m if largest is None else largest)
+    rc = lib().usac_prosac_schedule(n, m, clock, term_len, R, _ptr(sub, ctypes.c_uint32), ctypes.byref(nxt),
+                                    ctypes.byref(lg))
+    if rc:
+        raise UsacError(rc, "usac_prosac_schedule")
+    return sub, int(nxt.value), int(lg.value)
 
 
 def sprt_pool(seed, estimator, n_points, m):
@@ -742,6 +774,80 @@ class MultiContext:
                 r["polished"] = po
                 r["inliers"] = idx
         return res
+
+    def draw_samples(self, R, seeds, first_hyp=0, problems=None, clock=None, term_len=None):
+        """usac_multi_draw_samples (for tests): the samples a round's solve kernels draw, A x R x m local
+        indices.  clock=None: the uniform sampler; else the PROSAC sampler with clock[i] (its hypCount
+        at the round's first lane) and term_len[i] (default n_p) for the i-th listed problem."""
+        A = self.P if problems is None else len(problems)
+        pr = None if problems is None else np.ascontiguousarray(problems, dtype=np.uint32)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd.size != A:
+            raise ValueError("seeds: one per listed problem (%d), got %d" % (A, sd.size))
+        ck = tl = None
+        if clock is not None:
+            ck = np.ascontiguousarray(clock, dtype=np.uint32)
+            ids = np.arange(self.P) if problems is None else np.asarray(problems, dtype=np.int64)
+            tl = np.ascontiguousarray(self.sizes[ids] if term_len is None else term_len, dtype=np.uint32)
+            if ck.size != A or tl.size != A:
+                raise ValueError("clock / term_len: one per listed problem (%d)" % A)
+        out = np.zeros((A, R, self.m), dtype=np.int32)
+        self._check(lib().usac_multi_draw_samples(self._h, _ptr(pr, ctypes.c_uint32), A, R, _ptr(sd, ctypes.c_uint64),
+                                                  first_hyp, _ptr(ck, ctypes.c_uint32), _ptr(tl, ctypes.c_uint32),
+                                                  _ptr(out, ctypes.c_int32)), "multi_draw_samples")
+        return out
+
+    def _run_params(self, model_or_params):
+        if isinstance(model_or_params, _Params):
+            return model_or_params
+        p = _params(model_or_params)
+        p.seed = model_or_params.seed  # the default seeds are seed + p, never a random one
+        return p
+
+    def run_prosac(self, model_or_params, seeds=None, polish=False):
+        """usac_multi_run_prosac: run() with the PROSAC sampler and PROSAC's termination criterion per
+        problem; every point set sorted by descending quality.  Returns run()'s dicts plus
+        termination_length, largest_sample_size, clock (the sampler's hypCount at the end) and scans;
+        polish=True adds "polished" and "inliers" as run() does."""
+        p = self._run_params(model_or_params)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != self.P:
+            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
+        out = (_MultiOutput * self.P)()
+        pro = (_MultiProsacOutput * self.P)()
+        pol = (_MultiPolishOutput * self.P)() if polish else None
+        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if polish else None
+        self._check(lib().usac_multi_run_prosac(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, pro, pol,
+                                                _ptr(mask, ctypes.c_uint8)), "multi_run_prosac")
+        res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
+                "bound": int(o.bound), "status": int(o.status), "termination_length": int(q.termination_length),
+                "largest_sample_size": int(q.largest_sample_size), "clock": int(q.clock), "scans": int(q.scans)}
+               for o, q in zip(out, pro)]
+        if polish:
+            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
+                r["polished"] = po
+                r["inliers"] = idx
+        return res
+
+    def prosac_scan(self, model_or_params, models, hyp_count, largest, reset=False):
+        """usac_multi_prosac_scan (for tests): one PROSAC termination scan of every problem with models
+        (P x 9) as new bests at hypothesis hyp_count[p] and largest_sample_size largest[p]; the state
+        persists between calls, reset=True starts it afresh.  Returns (bound uint32[P], term_len
+        uint32[P], candidates: per problem a k x 2 array of (i, count), ascending i)."""
+        p = self._run_params(model_or_params)
+        m = np.ascontiguousarray(models, dtype=np.float32).reshape(self.P, 9)
+        hc = np.ascontiguousarray(hyp_count, dtype=np.uint32)
+        lg = np.ascontiguousarray(largest, dtype=np.uint32)
+        if hc.size != self.P or lg.size != self.P:
+            raise ValueError("hyp_count / largest: one per problem (%d)" % self.P)
+        bound, tl, nc = (np.zeros(self.P, dtype=np.uint32) for _ in range(3))
+        cand = np.zeros((int(self.offsets[-1]) // 2 + self.P, 2), dtype=np.uint32)
+        u32 = ctypes.c_uint32
+        self._check(lib().usac_multi_prosac_scan(self._h, ctypes.byref(p), 1 if reset else 0, _ptr(m, ctypes.c_float),
+                                                 _ptr(hc, u32), _ptr(lg, u32), _ptr(bound, u32), _ptr(tl, u32),
+                                                 _ptr(nc, u32), _ptr(cand, u32)), "multi_prosac_scan")
+        segs = [cand[int(o) // 2 + q:int(o) // 2 + q + int(nc[q])].copy() for q, o in enumerate(self.offsets[:-1])]
+        return bound, tl, segs
 
     def inliers(self, models, thr):
         """Ascending inlier indices (local to each problem) of each problem's model (P x 9), by the

@@ -5,7 +5,9 @@
 //   points   : N_total x float4, the problems' rows concatenated; offsets[P + 1], problem p owns
 //              rows offsets[p] .. offsets[p + 1] - 1 (sample, hypothesis and inlier indices are
 //              local to the problem);
-//   items    : A x MultiItem, the launch's active list (problem id and its sampler seed);
+//   items    : A x MultiItem, the launch's active list (problem id, its sampler seed and, for the
+//              PROSAC sampler, the round's clock and termination length);
+//   growth   : PROSAC only, N_total uint32: problem p's growth function at growth + offsets[p];
 //   models   : per-launch SoA slab over the A * R hypotheses of the launch, hypothesis h of
 //              active entry a at g = a * R + h -- H: [18][A R] (H then H^-1), F: [9][3 A R] with
 //              slot 3 g + j = the j-th valid model of the sample (seven_points.cpp root order);
@@ -14,7 +16,8 @@
 //
 // Every per-hypothesis step is the single-problem path's device math (usac_device.hpp), so a
 // problem's models, counts and sums equal those of a usac_ctx over its points bit for bit: the
-// sample of (seed, global hypothesis index) by draw_sample over n_p, the thin-QR DLT with the
+// sample of (seed, global hypothesis index) by draw_sample over n_p (or, in the PROSAC
+// instantiations, by multi_sample's closed-form PROSAC rule on the same stream), the thin-QR DLT with the
 // row-Jacobi fall-back (or the 7-point chain), and the ONE-CHUNK score: each lane walks its
 // problem's points in order, so Σ is the reference's sequential fp32 sum.  R is a multiple of
 // 64: a wave never spans two problems, so the problem id, the point base and every point are
@@ -24,6 +27,7 @@
 
 #include "usac_device.hpp"
 #include "usac_kernels.h"
+#include "usac_prosac.hpp"
 
 namespace usac {
 
@@ -33,6 +37,51 @@ __device__ __forceinline__ DevSampler uniform_sampler(uint64_t seed) {
     DevSampler ds{};
     ds.seed = seed;
     return ds;
+}
+
+// Lane h's sample of a round.  Uniform: draw_sample over n_p.  PROSAC (usac_prosac.hpp's closed form
+// over the problem's growth function g, the item's clock T and termination length L): t = T + h,
+//   t > T_N        : M distinct indices of [0, n)        (the reference past its growth table)
+//   s(t - 1) > L   : M distinct indices of [0, L]        (closed range, L < n; the subset is tested
+//                                                          before this call's increment)
+//   otherwise      : M - 1 distinct indices of [0, s(t) - 2] and point s(t) - 1
+// from the (seed, global hypothesis index) stream either way: the first M - 1 draws are
+// draw_unique's over the branch's range, the last one is its M-th step or the fixed point.
+template <int M, bool PROSAC>
+__device__ __forceinline__ void multi_sample(const MultiItem &it, const uint32_t *__restrict__ g, uint32_t n,
+                                             uint64_t hyp, uint32_t h, int32_t (&s)[M]) {
+    if constexpr (!PROSAC) {
+        draw_sample<M>(uniform_sampler(it.seed), hyp, n, s);
+    } else {
+        uint64_t st = it.seed ^ (hyp * 0xD1B54A32D192ED03ull);
+        const uint32_t t = it.clock + h;
+        uint32_t range = n, last = 0;  // last != 0: the fixed point + 1
+        if (t <= kProsacGrowthMax) {
+            uint32_t s_prev, s_now;
+            prosac_subset_pair(g, n, (uint32_t)M, t, s_prev, s_now);
+            if (s_prev > it.term_len) {
+                range = it.term_len + 1;
+            } else {
+                range = s_now - 1;
+                last = s_now;
+            }
+        }
+        draw_unique<M - 1>(st, range, s);
+        if (last) {
+            s[M - 1] = (int32_t)last - 1;
+        } else {  // draw_unique<M>'s last step
+            int32_t v;
+            bool dup;
+            do {
+                const uint64_t r = splitmix64(st);
+                v = (int32_t)(((r >> 32) * (uint64_t)range) >> 32);
+                dup = false;
+#pragma unroll
+                for (int j = 0; j < M - 1; j++) dup |= (s[j] == v);
+            } while (dup);
+            s[M - 1] = v;
+        }
+    }
 }
 
 // as kernels.hip store_h: H = v / v[8] in fp64, one cast, H^-1 by inv3x3
@@ -63,12 +112,13 @@ __device__ __forceinline__ void multi_dlt_system(const float4 *__restrict__ pts,
 // grid (R / 64, A).  Thin mode: dlt4_thin_qr, and the lanes it refuses solve the rebuilt system by
 // row_jacobi + pick_vector in the same kernel (what k_solve_h4_jac does for k_solve_h4's list);
 // nullspace mode: the row Jacobi for every lane.
-template <bool NULLSPACE>
+template <bool NULLSPACE, bool PROSAC>
 __global__ __launch_bounds__(64) void k_multi_solve_h4(const float4 *__restrict__ pts_all,
                                                        const uint32_t *__restrict__ offsets,
                                                        const MultiItem *__restrict__ items,
                                                        const int32_t *__restrict__ samples_in, uint32_t R,
-                                                       uint64_t first_hyp, float *__restrict__ models) {
+                                                       uint64_t first_hyp, float *__restrict__ models,
+                                                       const uint32_t *__restrict__ growth) {
     const uint32_t a = blockIdx.y;
     const MultiItem it = items[a];
     const uint32_t base = offsets[it.problem], n = offsets[it.problem + 1] - base;
@@ -80,7 +130,7 @@ __global__ __launch_bounds__(64) void k_multi_solve_h4(const float4 *__restrict_
 #pragma unroll
         for (int i = 0; i < 4; i++) s[i] = samples_in[4 * g + i];
     } else {
-        draw_sample<4>(uniform_sampler(it.seed), first_hyp + h, n, s);
+        multi_sample<4, PROSAC>(it, growth + base, n, first_hyp + h, h, s);
     }
     double W[8][9];
     double v[9];
@@ -100,13 +150,15 @@ __global__ __launch_bounds__(64) void k_multi_solve_h4(const float4 *__restrict_
 // ------------------------------------------------------------------------ solve (F, 7-pt)
 // grid (R / 64, A): k_solve_f7's chain per lane, slots 3 g + j, the occupied slots appended to
 // the active entry's list (wave-aggregated atomic on list_n[a], zeroed by the launcher).
+template <bool PROSAC>
 __global__ __launch_bounds__(64) void k_multi_solve_f7(const float4 *__restrict__ pts_all,
                                                        const uint32_t *__restrict__ offsets,
                                                        const MultiItem *__restrict__ items,
                                                        const int32_t *__restrict__ samples_in, uint32_t R,
                                                        uint64_t first_hyp, float *__restrict__ models,
                                                        int32_t *__restrict__ counts, float *__restrict__ sums,
-                                                       uint32_t *__restrict__ list, uint32_t *__restrict__ list_n) {
+                                                       uint32_t *__restrict__ list, uint32_t *__restrict__ list_n,
+                                                       const uint32_t *__restrict__ growth) {
     const uint32_t a = blockIdx.y;
     const MultiItem it = items[a];
     const uint32_t base = offsets[it.problem], n = offsets[it.problem + 1] - base;
@@ -121,7 +173,7 @@ __global__ __launch_bounds__(64) void k_multi_solve_f7(const float4 *__restrict_
 #pragma unroll
             for (int i = 0; i < 7; i++) s[i] = samples_in[7 * g + i];
         } else {
-            draw_sample<7>(uniform_sampler(it.seed), first_hyp + h, n, s);
+            multi_sample<7, PROSAC>(it, growth + base, n, first_hyp + h, h, s);
         }
         double W[7][9];
 #pragma unroll
@@ -365,12 +417,10 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
     if (r.A == 0 || r.R == 0 || r.R % 64) return hipErrorInvalidValue;
     const dim3 grid(r.R / 64, r.A);
     if (r.estimator == USAC_HOMOGRAPHY) {
-        if (r.nullspace)
-            hipLaunchKernelGGL(k_multi_solve_h4<true>, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in,
-                               r.R, r.first_hyp, r.models);
-        else
-            hipLaunchKernelGGL(k_multi_solve_h4<false>, grid, dim3(64), 0, st, r.pts, r.offsets, r.items,
-                               r.samples_in, r.R, r.first_hyp, r.models);
+        auto *solve = r.growth ? (r.nullspace ? k_multi_solve_h4<true, true> : k_multi_solve_h4<false, true>)
+                               : (r.nullspace ? k_multi_solve_h4<true, false> : k_multi_solve_h4<false, false>);
+        hipLaunchKernelGGL(solve, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R, r.first_hyp,
+                           r.models, r.growth);
         hipLaunchKernelGGL(k_multi_score_h, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.models, r.R, r.thr,
                            r.counts, r.sums);
         hipLaunchKernelGGL(k_multi_argmax, dim3(r.A), dim3(256), 0, st, r.items, r.counts, r.sums, r.models, r.R, 9,
@@ -378,8 +428,9 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
     } else if (r.estimator == USAC_FUNDAMENTAL) {
         hipError_t e = hipMemsetAsync(r.list_n, 0, sizeof(uint32_t) * r.A, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_multi_solve_f7, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R,
-                           r.first_hyp, r.models, r.counts, r.sums, r.list, r.list_n);
+        auto *solve = r.growth ? k_multi_solve_f7<true> : k_multi_solve_f7<false>;
+        hipLaunchKernelGGL(solve, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R, r.first_hyp,
+                           r.models, r.counts, r.sums, r.list, r.list_n, r.growth);
         hipLaunchKernelGGL(k_multi_score_f, dim3(3 * r.R / 64, r.A), dim3(64), 0, st, r.pts, r.offsets, r.items,
                            r.models, r.R, r.list, r.list_n, r.thr, r.counts, r.sums);
         hipLaunchKernelGGL(k_multi_argmax, dim3(r.A), dim3(256), 0, st, r.items, r.counts, r.sums, r.models, 3 * r.R,
@@ -387,6 +438,35 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
     } else {
         return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// the samples alone: grid (R / 64, A), lane h of entry a writes its m indices
+template <int M, bool PROSAC>
+__global__ __launch_bounds__(64) void k_multi_draw(const uint32_t *__restrict__ offsets,
+                                                   const MultiItem *__restrict__ items, uint32_t R,
+                                                   uint64_t first_hyp, const uint32_t *__restrict__ growth,
+                                                   int32_t *__restrict__ out) {
+    const uint32_t a = blockIdx.y;
+    const MultiItem it = items[a];
+    const uint32_t base = offsets[it.problem], n = offsets[it.problem + 1] - base;
+    const uint32_t h = blockIdx.x * 64 + threadIdx.x;
+    int32_t s[M];
+    multi_sample<M, PROSAC>(it, growth + base, n, first_hyp + h, h, s);
+    int32_t *__restrict__ o = out + ((size_t)a * R + h) * M;
+#pragma unroll
+    for (int i = 0; i < M; i++) o[i] = s[i];
+}
+
+hipError_t launch_multi_draw(hipStream_t st, int estimator, const uint32_t *offsets, const MultiItem *items, uint32_t A,
+                             uint32_t R, uint64_t first_hyp, const uint32_t *growth, int32_t *out) {
+    if (A == 0 || R == 0 || R % 64) return hipErrorInvalidValue;
+    const dim3 grid(R / 64, A);
+    if (estimator != USAC_HOMOGRAPHY && estimator != USAC_FUNDAMENTAL) return hipErrorInvalidValue;
+    auto *draw4 = growth ? k_multi_draw<4, true> : k_multi_draw<4, false>;
+    auto *draw7 = growth ? k_multi_draw<7, true> : k_multi_draw<7, false>;
+    hipLaunchKernelGGL(estimator == USAC_HOMOGRAPHY ? draw4 : draw7, grid, dim3(64), 0, st, offsets, items, R,
+                       first_hyp, growth, out);
     return hipGetLastError();
 }
 

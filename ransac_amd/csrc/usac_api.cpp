@@ -3976,12 +3976,15 @@ void usac_lo_destroy(usac_lo *h) {
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- multi-problem batches (ABI 15, 16)
+// ---------------------------------------------------------------- multi-problem batches (ABI 15, 16, 17)
 // P independent two-view problems in one context (kernels_multi.hip): the usac_hypothesize_score
 // round over (active problem, hypothesis tile), and a batch-granular RANSAC whose host loop only
 // reads the active problems' records once per round, evaluates the standard termination criterion
 // and uploads the compacted active list.  One stream; every buffer is sized once per call, for
-// (active problems) x R, none inside the round loop.
+// (active problems) x R, none inside the round loop.  ABI 17 (usac_multi_run_prosac): the same loop
+// with the PROSAC sampler in closed form (usac_prosac.hpp) and PROSAC's termination scan split between
+// k_multi_prosac_scan, which stores its candidates into pinned host memory, and
+// ProsacTerminationCriteria::applyCandidates.
 
 struct usac_multi {
     int device = 0;
@@ -3995,6 +3998,14 @@ struct usac_multi {
     size_t pin_bytes = 0;
     void *pol_pin = nullptr;  // pinned staging of the polish: P results and the mask down
     size_t pol_pin_bytes = 0;
+    // PROSAC (built at the first PROSAC call): the problems' growth functions and pristine non-random
+    // minima (N_total values each, the points' offsets), the working copy the scan kernel raises, the
+    // pinned block it stores candidates and their numbers into, and the per-problem host halves
+    DevBuf growth, non_random0, non_random;
+    std::vector<std::shared_ptr<const std::vector<uint32_t>>> growth_host;  // per problem, shared by shape
+    void *pro_pin = nullptr;  // (N_total / 2 + P) candidate pairs, then P numbers
+    size_t pro_pin_bytes = 0;
+    std::vector<std::unique_ptr<usac::ProsacTerminationCriteria>> pterm;
     std::string err;
 };
 
@@ -4138,9 +4149,89 @@ int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, c
     return USAC_OK;
 }
 
+// ---- PROSAC for multi-problem batches (ABI 17)
+uint32_t *multi_cand_pin(usac_multi *mc) { return static_cast<uint32_t *>(mc->pro_pin); }
+uint32_t *multi_cand_n_pin(usac_multi *mc) {
+    return multi_cand_pin(mc) + 2 * usac::multi_cand_capacity(mc->n_total, mc->P);
+}
+
+// once per context: the device growth functions and non-random minima, the pinned candidate block
+int multi_prosac_ensure(usac_multi *mc) {
+    if (!mc->growth_host.empty()) return USAC_OK;
+    const size_t bytes = sizeof(uint32_t) * (size_t)mc->n_total;
+    std::vector<uint32_t> g(mc->n_total), nr(mc->n_total);
+    std::vector<std::shared_ptr<const std::vector<uint32_t>>> tabs(mc->P);
+    for (uint32_t p = 0; p < mc->P; p++) {
+        const uint32_t base = mc->offsets[p], n = mc->offsets[p + 1] - base;
+        tabs[p] = usac::ProsacSampler::growth_table(n, mc->m);
+        std::copy(tabs[p]->begin(), tabs[p]->end(), g.begin() + base);
+        const std::vector<uint32_t> t = usac::ProsacTerminationCriteria::table(n, mc->m);
+        std::copy(t.begin(), t.end(), nr.begin() + base);
+    }
+    HIP_TRY(mc, mc->growth.reserve(bytes));
+    HIP_TRY(mc, mc->non_random0.reserve(bytes));
+    HIP_TRY(mc, mc->non_random.reserve(bytes));
+    HIP_TRY(mc, hipMemcpy(mc->growth.p, g.data(), bytes, hipMemcpyHostToDevice));
+    HIP_TRY(mc, hipMemcpy(mc->non_random0.p, nr.data(), bytes, hipMemcpyHostToDevice));
+    const size_t need = sizeof(uint32_t) * (2 * usac::multi_cand_capacity(mc->n_total, mc->P) + mc->P);
+    if (!mc->pro_pin) mc->pro_pin = PinnedPool::get().take(need, &mc->pro_pin_bytes);
+    if (!mc->pro_pin) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
+    mc->growth_host.swap(tabs);
+    return USAC_OK;
+}
+
+// the start of a run: every problem's termination state fresh, the device minima pristine
+int multi_prosac_reset(usac_multi *mc, const usac_params *prm) {
+    mc->pterm.resize(mc->P);
+    for (uint32_t p = 0; p < mc->P; p++)
+        mc->pterm[p].reset(new usac::ProsacTerminationCriteria(usac::ProsacTerminationCriteria::CandidatesOnly{},
+                                                               *mc->growth_host[p], prm->desired_prob, mc->m,
+                                                               mc->offsets[p + 1] - mc->offsets[p],
+                                                               prm->max_iterations));
+    HIP_TRY(mc, hipMemcpyAsync(mc->non_random.p, mc->non_random0.p, sizeof(uint32_t) * (size_t)mc->n_total,
+                               hipMemcpyDeviceToDevice, mc->stream));
+    return USAC_OK;
+}
+
+hipError_t multi_launch_scan(usac_multi *mc, uint32_t A, uint64_t first_hyp, float thr) {
+    return usac::launch_multi_prosac_scan(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(),
+                                          mc->items.as<usac::MultiItem>(), A, mc->running.as<usac_record>(),
+                                          first_hyp, thr, mc->non_random.as<uint32_t>(), multi_cand_pin(mc),
+                                          multi_cand_n_pin(mc));
+}
+
+// the host half of problem p's scan: the candidates active entry a's workgroup left
+uint32_t multi_apply_candidates(usac_multi *mc, uint32_t a, uint32_t p, uint32_t hyp_count, uint32_t largest) {
+    const uint32_t *cand = multi_cand_pin(mc) + 2 * usac::multi_cand_offset(mc->offsets[p], p);
+    return mc->pterm[p]->applyCandidates(hyp_count, largest, cand, multi_cand_n_pin(mc)[a]);
+}
+
 }  // namespace
 
 extern "C" {
+
+int usac_prosac_schedule(uint32_t n, uint32_t m, uint32_t clock, uint32_t term_len, uint32_t R, uint32_t *subset,
+                         uint32_t *clock_next, uint32_t *largest) {
+    if (m < 2 || n < m || clock < 1 || clock > (1u << 30) || term_len < m || term_len > n || R > (1u << 20))
+        return USAC_ERR_ARG;
+    const auto tab = usac::ProsacSampler::growth_table(n, m);
+    const uint32_t *g = tab->data();
+    if (subset)
+        for (uint32_t j = 0; j < R; j++) {  // the branch rule of the device sampler, lane by lane
+            const uint32_t t = clock + j;
+            uint32_t s_prev, s_now;
+            if (t > usac::kProsacGrowthMax) {
+                subset[j] = UINT32_MAX;
+                continue;
+            }
+            usac::prosac_subset_pair(g, n, m, t, s_prev, s_now);
+            subset[j] = s_prev > term_len ? 0u : s_now;
+        }
+    const uint32_t n_prosac = usac::prosac_round_lanes(g, n, clock, term_len, R);
+    if (clock_next) *clock_next = clock + n_prosac;
+    if (largest) *largest = usac::prosac_largest_at(g, n, m, clock, n_prosac, *largest, R ? R - 1 : 0);
+    return USAC_OK;
+}
 
 int usac_multi_create(usac_multi **out, int device, int estimator, const float *pts, const uint32_t *offsets,
                       uint32_t P) {
@@ -4191,6 +4282,8 @@ void usac_multi_destroy(usac_multi *mc) {
     if (mc->stream) (void)hipStreamSynchronize(mc->stream);
     if (mc->pin) PinnedPool::get().give_back(mc->pin, mc->pin_bytes);
     if (mc->pol_pin) PinnedPool::get().give_back(mc->pol_pin, mc->pol_pin_bytes);
+    if (mc->pro_pin) PinnedPool::get().give_back(mc->pro_pin, mc->pro_pin_bytes);
+    for (DevBuf *b : {&mc->growth, &mc->non_random0, &mc->non_random}) b->release();
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
                       &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
                       &mc->pol_out})
@@ -4343,6 +4436,152 @@ int usac_multi_run_polished(usac_multi *mc, const usac_params *prm, const uint64
                   "usac_record's model as a strided float array");
     static_assert(offsetof(usac_multi_output, best) % sizeof(float) == 0 && sizeof(usac_multi_output) % sizeof(float) == 0,
                   "usac_multi_output's model as a strided float array");
+    return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
+                               sizeof(usac_record) / sizeof(float), out[0].best.model,
+                               sizeof(usac_multi_output) / sizeof(float), prm->threshold, pol, mask);
+}
+
+// ---- PROSAC (ABI 17)
+int usac_multi_draw_samples(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t R,
+                            const uint64_t *seeds, uint64_t first_hyp, const uint32_t *clock, const uint32_t *term_len,
+                            int32_t *out) {
+    if (!mc) return USAC_ERR_ARG;
+    if (!seeds || !out || (clock && !term_len)) return fail(mc, USAC_ERR_ARG, "seeds, out and (with clock) term_len");
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
+    if (!problems && n_problems != 0 && n_problems != mc->P)
+        return fail(mc, USAC_ERR_ARG, "problems == NULL means all problems: n_problems must be P or 0");
+    const uint32_t A = problems ? n_problems : mc->P;
+    if (A == 0 || A > usac::kMultiMaxActive) return fail(mc, USAC_ERR_ARG, "n_problems out of range");
+    for (uint32_t a = 0; a < A; a++) {
+        const uint32_t p = problems ? problems[a] : a;
+        if (p >= mc->P) return fail(mc, USAC_ERR_ARG, "problem index out of range");
+        if (!clock) continue;
+        const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
+        if (clock[a] < 1 || clock[a] > (1u << 30) || term_len[a] < mc->m || term_len[a] > n)
+            return fail(mc, USAC_ERR_ARG, "clock >= 1 and sample size <= term_len <= n_p");
+    }
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    int rc = multi_ensure(mc, A, R, true);
+    if (rc) return rc;
+    if (clock && (rc = multi_prosac_ensure(mc))) return rc;
+    usac::MultiItem *items = multi_items_pin(mc);
+    for (uint32_t a = 0; a < A; a++)
+        items[a] = usac::MultiItem{problems ? problems[a] : a, clock ? clock[a] : 0u, seeds[a],
+                                   clock ? term_len[a] : 0u, 0u};
+    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
+                               mc->stream));
+    HIP_TRY(mc, usac::launch_multi_draw(mc->stream, mc->estimator, mc->offs.as<uint32_t>(),
+                                        mc->items.as<usac::MultiItem>(), A, R, first_hyp,
+                                        clock ? mc->growth.as<uint32_t>() : nullptr, mc->samples.as<int32_t>()));
+    HIP_TRY(mc, hipMemcpyAsync(out, mc->samples.p, sizeof(int32_t) * (size_t)A * R * mc->m, hipMemcpyDeviceToHost,
+                               mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return USAC_OK;
+}
+
+int usac_multi_prosac_scan(usac_multi *mc, const usac_params *prm, int reset, const float *models,
+                           const uint32_t *hyp_count, const uint32_t *largest, uint32_t *bound, uint32_t *term_len,
+                           uint32_t *n_cand, uint32_t *cand) {
+    if (!mc || !prm || !models || !hyp_count || !largest || !bound || !term_len) return USAC_ERR_ARG;
+    const uint32_t P = mc->P;
+    for (uint32_t p = 0; p < P; p++)
+        if (mc->offsets[p + 1] - mc->offsets[p] <= 20) return fail(mc, USAC_ERR_ARG, "PROSAC needs > 20 points per problem");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    int rc = multi_ensure(mc, P, 64, false);
+    if (rc || (rc = multi_prosac_ensure(mc))) return rc;
+    if ((reset || mc->pterm.size() != P) && (rc = multi_prosac_reset(mc, prm))) return rc;
+    std::vector<usac_record> recs(P);
+    usac::MultiItem *items = multi_items_pin(mc);
+    for (uint32_t p = 0; p < P; p++) {
+        recs[p] = usac_record{};
+        recs[p].hyp_index = hyp_count[p];
+        recs[p].valid = 1;
+        memcpy(recs[p].model, models + 9 * (size_t)p, sizeof(recs[p].model));
+        items[p] = usac::MultiItem{p, 0u, 0ull, 0u, 0u};
+    }
+    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)P, hipMemcpyHostToDevice, mc->stream));
+    HIP_TRY(mc, hipMemcpyAsync(mc->running.p, recs.data(), sizeof(usac_record) * (size_t)P, hipMemcpyHostToDevice,
+                               mc->stream));
+    HIP_TRY(mc, multi_launch_scan(mc, P, 0, prm->threshold));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    for (uint32_t p = 0; p < P; p++) {
+        bound[p] = multi_apply_candidates(mc, p, p, hyp_count[p], largest[p]);
+        term_len[p] = mc->pterm[p]->terminationLength();
+        if (n_cand) n_cand[p] = multi_cand_n_pin(mc)[p];
+    }
+    if (cand) memcpy(cand, multi_cand_pin(mc), sizeof(uint32_t) * 2 * usac::multi_cand_capacity(mc->n_total, P));
+    return USAC_OK;
+}
+
+int usac_multi_run_prosac(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
+                          usac_multi_prosac_output *pro, usac_multi_polish_output *pol, uint8_t *mask) {
+    if (!mc || !prm || !out) return USAC_ERR_ARG;
+    if (prm->sprt || prm->lo != USAC_LO_NONE)
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run_prosac: no SPRT, no LO");
+    if (prm->sampler != USAC_SAMPLER_PROSAC) return fail(mc, USAC_ERR_ARG, "usac_multi_run_prosac: the PROSAC sampler");
+    const uint32_t R = prm->batch ? prm->batch : 256u;
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
+    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    const uint32_t P = mc->P, m = mc->m;
+    for (uint32_t p = 0; p < P; p++)
+        if (mc->offsets[p + 1] - mc->offsets[p] <= 20)
+            return fail(mc, USAC_ERR_ARG, "PROSAC needs > 20 points per problem (prosac_termination_criteria.hpp:158-163)");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    int rc = multi_ensure(mc, P, R, false);
+    if (rc || (rc = multi_prosac_ensure(mc)) || (rc = multi_prosac_reset(mc, prm))) return rc;
+    HIP_TRY(mc, hipMemsetAsync(mc->running.p, 0, sizeof(usac_record) * (size_t)P, mc->stream));
+    usac::MultiItem *items = multi_items_pin(mc);
+    usac_record *recs = multi_records_pin(mc, P);
+    // per problem: the sampler's largest_sample_size, the last scan's bound, the scans
+    std::vector<uint32_t> largest(P, m), bound(P, prm->max_iterations), scans(P, 0);
+    for (uint32_t p = 0; p < P; p++) {
+        items[p] = usac::MultiItem{p, 1u, seeds ? seeds[p] : (uint64_t)prm->seed + p, mc->offsets[p + 1] - mc->offsets[p], 0u};
+        out[p] = usac_multi_output{};
+    }
+    uint32_t A = P;
+    for (uint32_t round = 0; A > 0; round++) {
+        const uint64_t first = (uint64_t)round * R, done = first + R;
+        HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
+                                   mc->stream));
+        usac::MultiRound r = multi_round(mc, A, R, first, prm->threshold, prm->dlt_mode);
+        r.running = mc->running.as<usac_record>();
+        r.growth = mc->growth.as<uint32_t>();
+        HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
+        HIP_TRY(mc, multi_launch_scan(mc, A, first, prm->threshold));
+        HIP_TRY(mc, hipMemcpyAsync(recs, mc->out.p, sizeof(usac_record) * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
+        HIP_TRY(mc, stream_wait(mc->stream));
+        uint32_t keep = 0;
+        for (uint32_t a = 0; a < A; a++) {
+            const usac::MultiItem it = items[a];
+            const uint32_t p = it.problem, n = mc->offsets[p + 1] - mc->offsets[p];
+            const uint32_t *g = mc->growth_host[p]->data();
+            // the round's sampler: PROSAC lanes [0, n_prosac), drawn under (clock, term_len) of its start
+            const uint32_t n_prosac = usac::prosac_round_lanes(g, n, it.clock, it.term_len, R);
+            uint32_t L = it.term_len;
+            if (recs[a].valid && recs[a].hyp_index >= first) {  // a new best: the kernel scanned it
+                const uint32_t j = (uint32_t)(recs[a].hyp_index - first);
+                const uint32_t at = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], j);
+                bound[p] = multi_apply_candidates(mc, a, p, (uint32_t)recs[a].hyp_index, at);
+                L = mc->pterm[p]->terminationLength();
+                scans[p]++;
+            }
+            largest[p] = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], R - 1);
+            const uint32_t T = it.clock + n_prosac;
+            if (done >= std::min(prm->max_iterations, bound[p])) {
+                usac_multi_output &o = out[p];
+                o.best = recs[a];
+                o.hypotheses = (uint32_t)done;
+                o.rounds = round + 1;
+                o.bound = bound[p];
+                o.status = recs[a].inliers > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
+                if (pro) pro[p] = usac_multi_prosac_output{L, largest[p], T, scans[p]};
+            } else {
+                items[keep++] = usac::MultiItem{p, T, it.seed, L, 0u};
+            }
+        }
+        A = keep;
+    }
+    if (!pol) return USAC_OK;
     return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
                                sizeof(usac_record) / sizeof(float), out[0].best.model,
                                sizeof(usac_multi_output) / sizeof(float), prm->threshold, pol, mask);

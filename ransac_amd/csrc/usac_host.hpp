@@ -27,6 +27,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "usac_prosac.hpp"
+
 namespace usac {
 
 struct Score {
@@ -303,6 +305,24 @@ class ProsacSampler {
     uint32_t n_, m_, largest_, subset_, hyp_;
 };
 
+// One round of the multi-problem PROSAC sampler (usac_prosac.hpp's closed form): the sampler is a
+// pure function of the clock T (ProsacSampler's hypCount, from 1) and the termination length L,
+// both fixed for the round.  Lane j has t = T + j and is a PROSAC lane while t <= T_N and
+// s(t - 1) <= L; the PROSAC lanes are a prefix of the round (s and t only grow), and for L < n
+// s(x) <= L <=> x <= g[L - 1].  Needs m <= L <= n.
+inline uint32_t prosac_round_lanes(const uint32_t *g, uint32_t n, uint32_t T, uint32_t L, uint32_t R) {
+    uint64_t t_max = kProsacGrowthMax;
+    if (L < n) t_max = std::min<uint64_t>(t_max, (uint64_t)g[L - 1] + 1);
+    if ((uint64_t)T > t_max) return 0;
+    return (uint32_t)std::min<uint64_t>(R, t_max - T + 1);
+}
+// the sampler's largest_sample_size after lane j of that round (previous: its value before)
+inline uint32_t prosac_largest_at(const uint32_t *g, uint32_t n, uint32_t m, uint32_t T, uint32_t n_prosac,
+                                  uint32_t previous, uint32_t j) {
+    if (n_prosac == 0) return previous;
+    return std::max(previous, prosac_subset(g, n, m, T + std::min(j, n_prosac - 1)));
+}
+
 class ProsacTerminationCriteria {
    public:
     // prosac_termination_criteria.hpp:44-119: non-random inlier minima (beta 0.05,
@@ -312,6 +332,18 @@ class ProsacTerminationCriteria {
         : std_(desired_prob, sample_size, points_size, max_iterations),
           growth_(growth),
           non_random_(table(points_size, sample_size)),
+          maximality_(points_size, 10000),
+          pend_(points_size, 0),
+          n_(points_size),
+          term_len_(points_size) {}
+    // The candidate-list mode (multi-problem batches): the O(n) walk and the non-random minima live
+    // on the device (kernels_multi_prosac.hip), this object keeps the O(candidates) state alone --
+    // only applyCandidates may be called on it.
+    struct CandidatesOnly {};
+    ProsacTerminationCriteria(CandidatesOnly, const std::vector<uint32_t> &growth, float desired_prob,
+                              uint32_t sample_size, uint32_t points_size, uint32_t max_iterations)
+        : std_(desired_prob, sample_size, points_size, max_iterations),
+          growth_(growth),
           maximality_(points_size, 10000),
           pend_(points_size, 0),
           n_(points_size),
@@ -424,6 +456,16 @@ class ProsacTerminationCriteria {
             }
             i = e;
         }
+        return max_samples;
+    }
+
+    // The same call from the scan's candidates alone: cand = ncand pairs (i, count) in ascending i,
+    // each a point whose non-random minimum the scan just raised to count and that ends a run of
+    // inliers (or is point n - 1) -- what the walks above hand to candidate(), in their order.
+    // non_random_ is neither read nor written.
+    uint32_t applyCandidates(uint32_t hypCount, uint32_t largest, const uint32_t *cand, uint32_t ncand) {
+        uint32_t max_samples = maximality(term_len_ - 1);
+        for (uint32_t k = 0; k < ncand; k++) candidate(cand[2 * k], cand[2 * k + 1], hypCount, largest, max_samples);
         return max_samples;
     }
 

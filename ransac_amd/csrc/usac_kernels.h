@@ -334,9 +334,13 @@ size_t nonminimal_seq_bytes(uint32_t nmax, uint32_t W);
 // hypotheses (R a multiple of 64, A <= kMultiMaxActive: the launch grid's y extent).
 constexpr uint32_t kMultiMaxActive = 65535;
 struct MultiItem {
-    uint32_t problem, pad;
-    uint64_t seed;  // the problem's device-sampler seed (draw_sample's key with the hypothesis index)
+    uint32_t problem;
+    uint32_t clock;     // PROSAC: the sampler's hypCount T at the round's first lane (>= 1); else 0
+    uint64_t seed;      // the problem's device-sampler seed (draw_sample's key with the hypothesis index)
+    uint32_t term_len;  // PROSAC: the termination length L of the round (m <= L <= n_p); else 0
+    uint32_t pad;
 };
+static_assert(sizeof(MultiItem) == 24, "MultiItem: a multiple of 8 bytes");
 struct MultiRound {
     int estimator;  // USAC_HOMOGRAPHY | USAC_FUNDAMENTAL
     int nullspace;  // H: USAC_DLT_NULLSPACE
@@ -353,8 +357,28 @@ struct MultiRound {
     uint32_t *list, *list_n;    // F: occupied slots, 3 R per entry, and their numbers [A]
     usac_record *running;       // nullable, indexed by problem: the round's best is folded into it
     usac_record *out;           // [A]: the merged record (running given) or the round's record
+    const uint32_t *growth;     // nullable: the PROSAC sampler (items' clock / term_len) over the growth
+                                // functions, n_total values, problem p's at growth + offsets[p]
 };
 hipError_t launch_multi_round(hipStream_t st, const MultiRound &r);
+// the samples launch_multi_round's solve kernels draw (same device function), out: A x R x m local
+// indices; growth == nullptr: the uniform sampler
+hipError_t launch_multi_draw(hipStream_t st, int estimator, const uint32_t *offsets, const MultiItem *items, uint32_t A,
+                             uint32_t R, uint64_t first_hyp, const uint32_t *growth, int32_t *out);
+// PROSAC termination scan (kernels_multi_prosac.hip), one workgroup per active entry, after the
+// round's argmax: a problem whose running record improved in this round (valid, hyp_index >=
+// first_hyp) gets the O(n) part of prosac_termination_criteria.hpp:148-201 under that model --
+// non_random[offsets[p] + i] = max(old, count_i) for i >= 20, and the raised points that end a run of
+// inliers (or are point n_p - 1) as (i, count_i) pairs in ascending i at cand + 2 * multi_cand_offset,
+// their number in cand_n[a] (0 for a problem that did not improve).  cand and cand_n may be pinned
+// host memory: the kernel only stores to them.
+constexpr uint32_t kMultiScanTile = 256;  // points per step of the walk (= the workgroup)
+__host__ __device__ inline size_t multi_cand_offset(uint32_t point_offset, uint32_t p) { return (size_t)(point_offset >> 1) + p; }
+inline size_t multi_cand_capacity(uint32_t n_total, uint32_t P) { return (size_t)(n_total >> 1) + P; }
+hipError_t launch_multi_prosac_scan(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets,
+                                    const MultiItem *items, uint32_t A, const usac_record *running,
+                                    uint64_t first_hyp, float thr, uint32_t *non_random, uint32_t *cand,
+                                    uint32_t *cand_n);
 // per-point inlier flags of each problem's model (models P x 9 row-major, device; m18 = P x 18
 // floats of scratch): the residual of launch_inliers, H^-1 by inv3x3
 hipError_t launch_multi_mask(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,

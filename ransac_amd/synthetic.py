@@ -18,6 +18,16 @@ def _h_gt():
     return H / H[2, 2]
 
 
+def quality_sort(points, is_inlier, seed):
+    """Rows sorted by the PROSAC quality of fundamental_points(prosac_order=True), q = U(0,1) +
+    0.5 [inlier], descending -- for sets generated in another order.  Returns (points, is_inlier)."""
+    rng = np.random.default_rng(seed)
+    inl = np.asarray(is_inlier, dtype=bool)
+    q = rng.uniform(0.0, 1.0, len(inl)) + 0.5 * inl
+    order = np.argsort(-q, kind="stable")
+    return np.ascontiguousarray(points[order]), inl[order]
+
+
 def homography_points(n=10000, inlier_ratio=0.3, seed=1, noise=1.0, size=1000.0, cluster=None):
     """cfg2 (and cfg5 with cluster=(cx, cy, half_width)): N x 4 fp32 [x1 y1 x2 y2].
 

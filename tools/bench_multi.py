@@ -17,6 +17,13 @@ in the same job, never (a) itself; (a) counts as faster only beyond the larger o
 --polish times the run with its non-minimal polish instead: MultiContext.run(polish=True), the multi
 run alone (what the polish adds), and loop (b) followed per pair by the polish restated with
 get_inliers + nonminimal.  The per-pair minimal and polished inlier counts must agree.
+
+--sampler prosac compares the two multi runs instead: every pair's points are sorted by the PROSAC
+quality of synthetic.fundamental_points(prosac_order=True) (the homography sets too), and
+MultiContext.run_prosac is alternated with MultiContext.run (uniform sampler) on those same inputs;
+with --polish both runs include the polish.  Reported for both: median ms and spread, rounds per pair,
+the rounds of the longest pair (= the launch chains of the run) and ms per such round, total
+hypotheses, mean best (and polished) inlier counts.  No loop over single contexts in this mode.
 """
 import argparse
 import ctypes
@@ -36,7 +43,16 @@ import ransac_amd as usac  # noqa: E402
 from ransac_amd import synthetic  # noqa: E402
 
 
-def make_pairs(estimator, pairs, points, ratio):
+def make_pairs(estimator, pairs, points, ratio, quality_sorted=False):
+    if quality_sorted:
+        if estimator == "homography":
+            sets = []
+            for p in range(pairs):
+                pts, _, inl = synthetic.homography_points(n=points, inlier_ratio=ratio, seed=1000 + p)
+                sets.append(synthetic.quality_sort(pts, inl, 5000 + p)[0])
+            return sets
+        return [synthetic.fundamental_points(n=points, inlier_ratio=ratio, seed=1000 + p, prosac_order=True)[0]
+                for p in range(pairs)]
     if estimator == "homography":
         return [synthetic.homography_points(n=points, inlier_ratio=ratio, seed=1000 + p)[0] for p in range(pairs)]
     return [synthetic.fundamental_points(n=points, inlier_ratio=ratio, seed=1000 + p, prosac_order=False)[0]
@@ -172,6 +188,51 @@ def main_polish(a, mc, ctxs, model, seeds, thr, prob):
     return 0 if agree else 1
 
 
+def main_prosac(a, mc, model, est):
+    """--sampler prosac: MultiContext.run_prosac against MultiContext.run on the same quality-sorted
+    inputs, alternated, host-timed, medians and spreads as in main()"""
+    pmodel = usac.Model(model.threshold, mc.m, model.desired_prob, 5, est, usac.SAMPLER.Prosac)
+    pmodel.max_iterations, pmodel.batch, pmodel.seed = model.max_iterations, model.batch, model.seed
+    pmodel.setDLTMode(model.dlt_mode)
+
+    def summary(res, ms):
+        rounds = [r["rounds"] for r in res]
+        d = {"ms": round(statistics.median(ms), 3), "spread_ms": round(max(ms) - min(ms), 3),
+             "mean_rounds": round(float(np.mean(rounds)), 2), "launch_rounds": int(max(rounds)),
+             "ms_per_launch_round": round(statistics.median(ms) / max(rounds), 3),
+             "hypotheses": int(sum(r["hypotheses"] for r in res)),
+             "mean_best_inliers": round(float(np.mean([r["best"]["inliers"] for r in res])), 2)}
+        if a.polish:
+            d["mean_polished_inliers"] = round(float(np.mean([r["polished"]["inliers"] for r in res])), 2)
+        return d
+
+    for _ in range(a.warmup):
+        rp, ru = mc.run_prosac(pmodel, polish=a.polish), mc.run(model, polish=a.polish)
+    tp, tu = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        rp = mc.run_prosac(pmodel, polish=a.polish)
+        t1 = time.perf_counter()
+        ru = mc.run(model, polish=a.polish)
+        t2 = time.perf_counter()
+        tp.append((t1 - t0) * 1e3)
+        tu.append((t2 - t1) * 1e3)
+    line = {"bench": "multi_prosac", "estimator": a.estimator, "pairs": a.pairs, "points": a.points, "round": a.R,
+            "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio, "dlt": a.dlt, "reps": a.reps,
+            "polish": bool(a.polish), "prosac": summary(rp, tp), "uniform": summary(ru, tu),
+            "mean_scans": round(float(np.mean([r["scans"] for r in rp])), 2),
+            "mean_termination_length": round(float(np.mean([r["termination_length"] for r in rp])), 1)}
+    line["ratio_uniform_over_prosac"] = round(line["uniform"]["ms"] / line["prosac"]["ms"], 2)
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    mc.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=512)
@@ -187,19 +248,23 @@ def main():
     ap.add_argument("--polish", action="store_true",
                     help="time run + non-minimal polish: MultiContext.run(polish=True) against the multi run "
                          "alone and against the loop over contexts with the polish restated per context")
+    ap.add_argument("--sampler", choices=["uniform", "prosac"], default="uniform",
+                    help="prosac: quality-sorted inputs, MultiContext.run_prosac against the uniform multi run")
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
 
     est = usac.ESTIMATOR.Homography if a.estimator == "homography" else usac.ESTIMATOR.Fundamental
     thr, prob = 2.0, 0.95
-    sets = make_pairs(a.estimator, a.pairs, a.points, a.inlier_ratio)
+    sets = make_pairs(a.estimator, a.pairs, a.points, a.inlier_ratio, quality_sorted=a.sampler == "prosac")
     model = usac.Model(thr, 4 if a.estimator == "homography" else 7, prob, 5, est, usac.SAMPLER.Uniform)
     model.max_iterations, model.batch, model.seed = a.max_iterations, a.R, 1
     model.setDLTMode(usac.DLT.NULLSPACE if a.dlt == "nullspace" else usac.DLT.THIN)
     seeds = [model.seed + p for p in range(a.pairs)]
 
     mc = usac.MultiContext(est, sets)
+    if a.sampler == "prosac":
+        return main_prosac(a, mc, model, est)
     ctxs = [usac.Context(est, p) for p in sets]
     for c in ctxs:
         c.set_dlt_mode(model.dlt_mode)
