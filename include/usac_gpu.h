@@ -55,7 +55,10 @@
  *                                  termination criterion per problem (the sampler in closed form on the
  *                                  device, the termination scan split between a kernel and the host),
  *                                  with usac_prosac_schedule / usac_multi_draw_samples /
- *                                  usac_multi_prosac_scan exposing its parts
+ *                                  usac_multi_prosac_scan exposing its parts;
+ *                                  ABI 18: usac_multi_run_lo, inner + iterative LO-RANSAC of every
+ *                                  round's new bests in one launch (one workgroup per problem), with
+ *                                  usac_lo_draw / usac_multi_lo exposing its parts
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -70,7 +73,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 17
+#define USAC_ABI_VERSION 18
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -526,8 +529,8 @@ int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint3
  * problem is finished once (r + 1) R >= min(max_iterations, bound_p).  The clamp to max_iterations is
  * a deviation from ransac.cpp, which lets the bound exceed it: a batch call must stay bounded.  A run
  * evaluates at least as many hypotheses as the bound asks for, so the confidence guarantee holds.
- * This is NOT the glibc-stream Ransac::run (usac_ransac_run): no SPRT, LO or NAPSAC, and PROSAC is
- * usac_multi_run_prosac's -- params->sprt, ->lo or a sampler other than USAC_SAMPLER_UNIFORM return
+ * This is NOT the glibc-stream Ransac::run (usac_ransac_run): no SPRT or NAPSAC, PROSAC is
+ * usac_multi_run_prosac's and LO is usac_multi_run_lo's -- params->sprt, ->lo or a sampler other than USAC_SAMPLER_UNIFORM return
  * USAC_ERR_UNSUPPORTED here -- and it stops at the best minimal model; usac_multi_run_polished adds
  * the run's non-minimal polish.
  * Reads threshold, desired_prob, max_iterations, dlt_mode, seed and batch (= R, 0 = 256).
@@ -564,8 +567,8 @@ int usac_multi_polish(usac_multi *mc, const float *models, float thr,
 /* usac_multi_run, then the polish of every problem's best model at params->threshold without the
  * records leaving the device in between; out as usac_multi_run writes it (unchanged), pol / mask as
  * usac_multi_polish (a problem without a model: USAC_ERR_NO_MODEL in both).  The remaining deviations
- * from Ransac::run are usac_multi_run's: no SPRT, LO or NAPSAC (PROSAC: usac_multi_run_prosac),
- * batch-granular termination.
+ * from Ransac::run are usac_multi_run's: no SPRT or NAPSAC (PROSAC: usac_multi_run_prosac, LO:
+ * usac_multi_run_lo), batch-granular termination.
  * NULL mc, params, out or pol: USAC_ERR_ARG before any device call. */
 int usac_multi_run_polished(usac_multi *mc, const usac_params *params, const uint64_t *seeds,
                             usac_multi_output *out, usac_multi_polish_output *pol, uint8_t *mask);
@@ -620,7 +623,7 @@ typedef struct usac_multi_prosac_output {
  * Deviations from Ransac::run with PROSAC: batch granularity, two ways -- only a round's final best is
  * scanned (the reference scans every new best), and L changes only between rounds (the reference's next
  * sample already sees it); the clamp to max_iterations; the device random stream (the reference draws
- * from std::mt19937).  No SPRT, LO or NAPSAC.
+ * from std::mt19937).  No SPRT or NAPSAC; LO: usac_multi_run_lo.
  * USAC_ERR_UNSUPPORTED for params->sprt or ->lo; USAC_ERR_ARG for a sampler other than
  * USAC_SAMPLER_PROSAC, any n_p <= 20 (the reference reads point 20), a bad batch or dlt_mode, NULL mc,
  * params or out -- all before any device call.
@@ -638,6 +641,66 @@ int usac_multi_run_prosac(usac_multi *mc, const usac_params *params, const uint6
 int usac_multi_prosac_scan(usac_multi *mc, const usac_params *params, int reset, const float *models,
                            const uint32_t *hyp_count, const uint32_t *largest, uint32_t *bound, uint32_t *term_len,
                            uint32_t *n_cand, uint32_t *cand);
+
+/* ---- multi-problem batches: LO-RANSAC (ABI 18) -------------------------------------------------------
+ * The sample sets of the LO: k distinct integers of the closed range [0, max], in draw order --
+ * UniformRandomGenerator::generateUniqueRandomSet(sample, max) with the reference's generator replaced
+ * by the device sampler's SplitMix64 stream keyed by (seed, a fixed LO tag, draw), draw = the number of
+ * sets drawn so far for the problem in the run.  The device draws through the same text.  No context,
+ * no device.  USAC_ERR_ARG unless 1 <= k <= 64, k <= max + 1 and max < 2^31. */
+int usac_lo_draw(uint64_t seed, uint64_t draw, uint32_t k, uint32_t max, int32_t *out);
+
+/* One problem's LO state: the counters of a run (or since the last reset of usac_multi_lo). */
+typedef struct usac_multi_lo_output {
+    uint32_t lo_calls, inner_iters, iterative_iters, fits, improved, capped, draws;
+    float threshold;  /* the LO threshold as the last call left it */
+} usac_multi_lo_output;
+/* lo_calls: LO calls on a new best (those that return at once for < 12 inliers included);
+ * inner_iters / iterative_iters: the reference's "only for test" counters at their positions;
+ * fits: non-minimal fits; improved: inner iterations whose model became the best; capped: calls ended
+ * by the caps rule; draws: sets drawn. */
+
+/* One LO call -- InnerLocalOptimization::GetModelScore (inner_local_optimization.hpp:74-133) with
+ * IterativeLocalOptimization::GetScoreUnlimited / GetScoreLimited (iterative_local_optimization.hpp:
+ * 61-136), params->lo = USAC_LO_INITLORSC / USAC_LO_INITFLORSC -- for every problem at once, one
+ * workgroup per problem, every exit taken on the device.  recs[p] (in / out) is taken as a new best:
+ * its model, and (inliers, score) as best_score; a record that is not valid or has < 12 inliers comes
+ * back unchanged.  The list of the model's inliers is its getInliers at params->threshold, and the list's
+ * own length stands for best_score's count wherever the reference sizes a sample by it (equal for a
+ * record that holds its model's count).  Fits are usac_nonminimal's, scores usac_get_inliers' (count and
+ * sequential Σ), comparisons Score::bigger's; on an improvement model, inliers and score change, hyp_index
+ * and valid stay.  The LO threshold, the draw counter and the counters are per-problem state that
+ * persists in the context from call to call (the threshold compounds as the reference's does); reset
+ * != 0 (and any usac_multi_run_lo) starts them afresh.  seeds (nullable): P draw seeds, NULL =
+ * params->seed + p.  lo (nullable): P states after the call.
+ * The caps rule, a deviation: a problem of n_p > 16384 points, or an iterative-stage list to fit of
+ * > 4096 points, ends that LO call there -- the best so far is kept, the threshold goes back to
+ * params->threshold, capped is incremented.
+ * Reads of params: threshold, seed, lo, sprt, lo_sample_size, lo_inner_iterations,
+ * lo_iterative_iterations and lo_threshold_multiplier -- not sampler, batch, dlt_mode, desired_prob or
+ * max_iterations.  USAC_ERR_UNSUPPORTED for USAC_LO_GC or params->sprt; USAC_ERR_ARG for USAC_LO_NONE,
+ * lo_sample_size 0 or > 64, lo_iterative_iterations 0, NULL mc, params or recs -- all before any device
+ * call. */
+int usac_multi_lo(usac_multi *mc, const usac_params *params, int reset, const uint64_t *seeds,
+                  usac_record *recs, usac_multi_lo_output *lo);
+
+/* usac_multi_run (params->sampler = USAC_SAMPLER_UNIFORM) or usac_multi_run_prosac (USAC_SAMPLER_PROSAC)
+ * with LO-RANSAC: in every round, after the merge, each problem whose running best improved in the round
+ * gets one LO call as usac_multi_lo's on the device, before the PROSAC scan (which therefore sees the
+ * LO'd model: ransac.cpp:110-128) and before the records come down -- so the termination bound comes
+ * from the LO'd count.  The LO'd record keeps the hyp_index of the minimal model it started from (later
+ * merges, the "improved in this round" test and PROSAC's hypCount read it).
+ * Deviations from Ransac::run: only a round's final best is optimised (the reference optimises every new
+ * best); the LO draws come from the device stream (usac_lo_draw); the caps rule of usac_multi_lo; and
+ * those of usac_multi_run / usac_multi_run_prosac.  No SPRT or NAPSAC.
+ * USAC_ERR_UNSUPPORTED for USAC_LO_GC or params->sprt; USAC_ERR_ARG for USAC_LO_NONE, lo_sample_size 0
+ * or > 64, lo_iterative_iterations 0, USAC_SAMPLER_NAPSAC, a bad batch or dlt_mode, NULL mc, params or
+ * out, and with PROSAC any n_p <= 20 -- all before any device call.
+ * out / pol / mask as usac_multi_run_prosac's; lo (nullable): P LO states; pro (nullable) is written
+ * only with PROSAC. */
+int usac_multi_run_lo(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
+                      usac_multi_lo_output *lo, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
+                      uint8_t *mask);
 
 /* ---- self-test hooks (ABI 13) ------------------------------------------------------- */
 /* The essential 5-point solver's root step alone (five_points.cpp:139-157: rpoly_ak1's real zeros

@@ -665,6 +665,48 @@ public:
         return out;
     }
 
+    // usac_multi_lo: one LO call (inner + iterative LO-RANSAC, model.lo = InItLORsc / InItFLORsc) for
+    // every problem, records[p] (in / out) taken as a new best; the LO threshold, the draw counter and
+    // the counters persist from call to call unless reset.  Returns the P LO states after the call.
+    std::vector<usac_multi_lo_output> lo(const Model &model, std::vector<usac_record> &records,
+                                         const std::vector<uint64_t> &seeds = std::vector<uint64_t>(),
+                                         bool reset = true) const {
+        usac_params p = model.params();
+        p.seed = model.seed;
+        const unsigned int P = problems();
+        if (records.size() != P) throw Error(USAC_ERR_ARG, "lo: one record per problem");
+        if (!seeds.empty() && seeds.size() != P) throw Error(USAC_ERR_ARG, "lo: one seed per problem");
+        std::vector<usac_multi_lo_output> out(P);
+        check(usac_multi_lo(mc_, &p, reset ? 1 : 0, seeds.empty() ? nullptr : seeds.data(), records.data(), out.data()),
+              "MultiContext::lo");
+        return out;
+    }
+
+    // one problem's result of runLo: run()'s output, the LO counters and, with the PROSAC sampler,
+    // the PROSAC state at the end (empty otherwise)
+    struct Lo {
+        std::vector<usac_multi_output> run;
+        std::vector<usac_multi_lo_output> lo;
+        std::vector<usac_multi_prosac_output> prosac;
+    };
+
+    // usac_multi_run_lo: run() (model.sampler = Uniform) or runProsac() (Prosac) with LO-RANSAC of every
+    // round's new bests on the device (model.lo = InItLORsc / InItFLORsc, lo_sample_size <= 64)
+    Lo runLo(const Model &model, const std::vector<uint64_t> &seeds = std::vector<uint64_t>()) const {
+        usac_params p = model.params();
+        p.seed = model.seed;
+        const unsigned int P = problems();
+        if (!seeds.empty() && seeds.size() != P) throw Error(USAC_ERR_ARG, "runLo: one seed per problem");
+        Lo out;
+        out.run.resize(P);
+        out.lo.resize(P);
+        if (p.sampler == USAC_SAMPLER_PROSAC) out.prosac.resize(P);
+        check(usac_multi_run_lo(mc_, &p, seeds.empty() ? nullptr : seeds.data(), out.run.data(), out.lo.data(),
+                                out.prosac.empty() ? nullptr : out.prosac.data(), nullptr, nullptr),
+              "MultiContext::runLo");
+        return out;
+    }
+
 private:
     void splitMask(const std::vector<uint8_t> &mask, std::vector<std::vector<int> > *out) const {
         const unsigned int P = problems();

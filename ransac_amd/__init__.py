@@ -17,7 +17,7 @@ import numpy as np
 
 __all__ = ["ESTIMATOR", "SAMPLER", "LocOpt", "NeighborsSearch", "DLT", "Model", "Ransac", "RansacOutput", "Score", "Context", "Record",
            "RandomGenerator", "Sampler", "TerminationCriteria", "SPRT", "LocalOptimization", "SprtState", "MultiContext",
-           "build", "lib", "std_termination", "uniform_samples", "prosac_samples", "sprt_pool", "UsacError"]
+           "build", "lib", "std_termination", "uniform_samples", "prosac_samples", "sprt_pool", "lo_draw", "UsacError"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RANSAC_AMD_LIB") or os.path.join(_HERE, "libransac_amd.so")  # override: A/B builds
@@ -138,6 +138,18 @@ class _MultiProsacOutput(ctypes.Structure):
                 ("clock", ctypes.c_uint32), ("scans", ctypes.c_uint32)]
 
 
+class _MultiLoOutput(ctypes.Structure):
+    """usac_multi_lo_output (include/usac_gpu.h): one problem's LO counters and threshold."""
+    _fields_ = [("lo_calls", ctypes.c_uint32), ("inner_iters", ctypes.c_uint32), ("iterative_iters", ctypes.c_uint32),
+                ("fits", ctypes.c_uint32), ("improved", ctypes.c_uint32), ("capped", ctypes.c_uint32),
+                ("draws", ctypes.c_uint32), ("threshold", ctypes.c_float)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_[:-1]}
+        d["threshold"] = np.float32(self.threshold)
+        return d
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -159,6 +171,7 @@ ABI_SYMBOLS = [
     "usac_multi_hypothesize_score", "usac_multi_run", "usac_multi_inliers", "usac_multi_polish",
     "usac_multi_run_polished",
     "usac_prosac_schedule", "usac_multi_draw_samples", "usac_multi_run_prosac", "usac_multi_prosac_scan",
+    "usac_lo_draw", "usac_multi_lo", "usac_multi_run_lo",
 ]
 
 
@@ -274,6 +287,11 @@ def lib():
                                                  _P(_MultiProsacOutput), _P(_MultiPolishOutput), u8p]),
         "usac_multi_prosac_scan": (ctypes.c_int, [_vp, _P(_Params), ctypes.c_int, f32p, u32p, u32p, u32p, u32p, u32p,
                                                   u32p]),
+        "usac_lo_draw": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, i32p]),
+        "usac_multi_lo": (ctypes.c_int, [_vp, _P(_Params), ctypes.c_int, _P(ctypes.c_uint64), _P(Record),
+                                         _P(_MultiLoOutput)]),
+        "usac_multi_run_lo": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
+                                             _P(_MultiLoOutput), _P(_MultiProsacOutput), _P(_MultiPolishOutput), u8p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -331,6 +349,16 @@ def prosac_schedule(n, m, clock, term_len, R, largest=None):
     if rc:
         raise UsacError(rc, "usac_prosac_schedule")
     return sub, int(nxt.value), int(lg.value)
+
+
+def lo_draw(seed, draw, k, max):
+    """usac_lo_draw: the draw-th sample set of the multi-problem LO under `seed` -- k distinct integers of
+    the closed range [0, max], in draw order (int32[k]).  On the host; the device draws through the same text."""
+    out = np.zeros(int(k) if 0 < int(k) <= 64 else 1, dtype=np.int32)  # (a bad k: the C call refuses it)
+    rc = lib().usac_lo_draw(int(seed), int(draw), int(k), int(max), _ptr(out, ctypes.c_int32))
+    if rc:
+        raise UsacError(rc, "usac_lo_draw")
+    return out
 
 
 def sprt_pool(seed, estimator, n_points, m):
@@ -745,7 +773,7 @@ class MultiContext:
 
     def run(self, model_or_params, seeds=None, polish=False):
         """usac_multi_run: batch-granular RANSAC with the standard termination criterion over all
-        problems (uniform device sampler; no SPRT / LO).  model_or_params: a Model or a
+        problems (uniform device sampler; no SPRT; LO: run_lo).  model_or_params: a Model or a
         usac_params structure; seeds default to model.seed + p.  Returns a list of P dicts: best
         (record dict), hypotheses, rounds, bound, status.  polish=True (usac_multi_run_polished)
         adds the non-minimal polish of every best model at the run's threshold: each dict gains
@@ -848,6 +876,59 @@ class MultiContext:
                                                  _ptr(nc, u32), _ptr(cand, u32)), "multi_prosac_scan")
         segs = [cand[int(o) // 2 + q:int(o) // 2 + q + int(nc[q])].copy() for q, o in enumerate(self.offsets[:-1])]
         return bound, tl, segs
+
+    def lo(self, model_or_params, records, seeds=None, reset=True):
+        """usac_multi_lo: one LO call (inner + iterative LO-RANSAC, model.lo = InItLORsc / InItFLORsc) for
+        every problem, records[p] (a Record or a record dict) taken as a new best.  The LO threshold, the
+        draw counter and the counters persist between calls unless reset.  Returns (list of P record
+        dicts, list of P dicts: lo_calls, inner_iters, iterative_iters, fits, improved, capped, draws,
+        threshold)."""
+        p = self._run_params(model_or_params)
+        if len(records) != self.P:
+            raise ValueError("records: one per problem (%d), got %d" % (self.P, len(records)))
+        recs = (Record * self.P)()
+        for i, r in enumerate(records):
+            if isinstance(r, Record):
+                recs[i] = r
+            else:
+                recs[i] = Record(int(r["hyp_index"]), int(r["inliers"]), float(r["score"]),
+                                 (ctypes.c_float * 9)(*np.asarray(r["model"], dtype=np.float32).tolist()),
+                                 int(r["valid"]))
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != self.P:
+            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
+        lo = (_MultiLoOutput * self.P)()
+        self._check(lib().usac_multi_lo(self._h, ctypes.byref(p), 1 if reset else 0, _ptr(sd, ctypes.c_uint64), recs,
+                                        lo), "multi_lo")
+        return [r.as_dict() for r in recs], [q.as_dict() for q in lo]
+
+    def run_lo(self, model_or_params, seeds=None, polish=False):
+        """usac_multi_run_lo: run() (model.sampler Uniform) or run_prosac() (Prosac) with LO-RANSAC of every
+        round's new bests on the device (model.lo = InItLORsc / InItFLORsc).  Returns run()'s dicts plus
+        "lo" (the problem's LO counters and threshold); with PROSAC also run_prosac()'s keys; polish=True
+        adds "polished" and "inliers" as run() does."""
+        p = self._run_params(model_or_params)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != self.P:
+            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
+        out = (_MultiOutput * self.P)()
+        lo = (_MultiLoOutput * self.P)()
+        pro = (_MultiProsacOutput * self.P)()
+        pol = (_MultiPolishOutput * self.P)() if polish else None
+        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if polish else None
+        self._check(lib().usac_multi_run_lo(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, lo, pro, pol,
+                                            _ptr(mask, ctypes.c_uint8)), "multi_run_lo")
+        res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
+                "bound": int(o.bound), "status": int(o.status), "lo": q.as_dict()} for o, q in zip(out, lo)]
+        if p.sampler == int(SAMPLER.Prosac):
+            for r, q in zip(res, pro):
+                r.update(termination_length=int(q.termination_length), largest_sample_size=int(q.largest_sample_size),
+                         clock=int(q.clock), scans=int(q.scans))
+        if polish:
+            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
+                r["polished"] = po
+                r["inliers"] = idx
+        return res
 
     def inliers(self, models, thr):
         """Ascending inlier indices (local to each problem) of each problem's model (P x 9), by the

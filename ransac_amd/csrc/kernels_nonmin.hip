@@ -13,6 +13,7 @@
 #include "usac_device.hpp"
 #include "usac_device_e5.hpp"
 #include "usac_kernels.h"
+#include "usac_lo_draw.hpp"
 #include "usac_seqsum.hpp"
 
 namespace usac {
@@ -1394,6 +1395,217 @@ hipError_t launch_multi_polish(hipStream_t st, int estimator, const float4 *pts,
             break;
         case USAC_FUNDAMENTAL:
             hipLaunchKernelGGL(k_multi_polish<USAC_FUNDAMENTAL>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, lists, n_total, out, mask);
+            break;
+        default:
+            return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// LO-RANSAC of a multi context (DESIGN.md "Multi-problem batches", LO): k_multi_polish's workgroup
+// and device pieces under the control flow of InnerLocalOptimization::GetModelScore
+// (inner_local_optimization.hpp:74-133) with GetScoreUnlimited / GetScoreLimited
+// (iterative_local_optimization.hpp:61-136), one workgroup per active entry, every exit taken on the
+// device.  A workgroup leaves at once unless its problem's running record is valid and improved in
+// this round (hyp_index >= first_hyp, k_multi_prosac_scan's test; `force`: the test hook, every
+// record counts as new).
+//
+// Why the threshold compounds: the reference keeps the LO threshold in lo_model, which
+// outlives GetModelScore.  An inner iteration multiplies it (K * thr) before it knows whether the
+// iterative stage will run: the `<= sample_size` continue leaves it multiplied, and a completed
+// stage leaves it within 1e-5 of θ but not at θ's bits.  The next inner iteration -- of this call or
+// of the next new best -- starts from that value.  So the threshold is per-problem state here, read
+// and written once per call, and stepped by the fp32 expressions of LoRansac (usac_api.cpp).
+//
+// The body is one loop whose trip is "an optional fit, then a score", so pol_fit, pol_score and the
+// Σerr chain are each instantiated once.  `stage` says where the reference's control flow stands;
+// every decision is made from values all threads hold identically (counts pol_score returns, LDS
+// words read after a barrier, kernel arguments), so each branch around the barriers inside the
+// pol_* pieces is workgroup-uniform.  The two global lists of the problem hold max_inliers and
+// lo_inliers: the iterative stage scores into the list it was just fitted from (pol_fit has the
+// points in LDS by then), and an improvement swaps the two pointers.  The length of max_inliers
+// stands for best_score->inlier_number wherever the reference sizes a list by it.
+template <int EST>
+__global__ __launch_bounds__(kPolT) void k_multi_lo(const float4 *__restrict__ pts_all,
+                                                    const uint32_t *__restrict__ offsets, MultiLo g) {
+    constexpr bool FUND = EST != USAC_HOMOGRAPHY;
+    constexpr int32_t kM = FUND ? 7 : 4;
+    __shared__ __attribute__((aligned(16))) float4 s_q[kPolFitMax];
+    __shared__ __attribute__((aligned(16))) double s_d[kPolSbWin * 64 * 45 > 2 * kPolFitMax ? kPolSbWin * 64 * 45
+                                                                                            : 2 * kPolFitMax];
+    __shared__ double s_part[(kPolFitMax / 1024) * 45];
+    __shared__ double A[9][9], V[9][9], s_v[9], s_psum[8 * 64 / kPolC];
+    __shared__ float s_R[kPolT], s_sums[8], s_ws[18], s_model[18], s_sum[1], s_best[9];
+    __shared__ uint32_t s_wc[8 * (kPolT / 64)];
+    __shared__ int32_t s_ok, s_draw[kLoDrawMax], s_samp[kLoDrawMax];
+    PolShared sh;
+    sh.Q = s_q;
+    sh.D = s_d;
+    sh.E = reinterpret_cast<float *>(s_d);
+    sh.part = s_part;
+    sh.psum = s_psum;
+    sh.R = s_R;
+    sh.wc = s_wc;
+    sh.dbg = nullptr;
+    const uint32_t t = threadIdx.x, a = blockIdx.x;
+    const MultiItem item = g.items[a];
+    const uint32_t p = item.problem;
+    const usac_record rec = g.running[p];
+    if (!rec.valid || !(g.force || rec.hyp_index >= g.first_hyp)) return;  // workgroup-uniform
+    usac_multi_lo_output st = g.state[p];
+    st.lo_calls++;
+    const uint32_t base = offsets[p], N = offsets[p + 1] - base;
+    const float4 *__restrict__ pts = pts_all + base;
+    int32_t *lmax = g.lists + base, *llo = g.lists + (size_t)g.n_total + base;
+    int32_t best_cnt = rec.inliers, lo_cnt = 0;
+    float best_sum = rec.score, lo_sum = 0.f, thr = st.threshold;
+    uint32_t n_max = 0, it = 0, k = 0;
+    bool changed = false;
+    enum { kInit, kInner, kIter, kEnd };
+    int stage = best_cnt < 12 ? kEnd : kInit;
+    if (stage == kInit && N > kPolPtsMax) {  // the caps rule
+        st.capped++;
+        thr = g.thr;
+        stage = kEnd;
+    }
+    // the end of the iterative stage: the fail test, the best's update, the reference's counter
+    auto finish = [&]() {
+        const bool fail = (double)fabsf(thr - g.thr) > 0.00001;
+        if (fail) thr = g.thr;
+        if (!fail && (lo_cnt > best_cnt || (lo_cnt == best_cnt && lo_sum > best_sum))) {
+            best_cnt = lo_cnt;
+            best_sum = lo_sum;
+            if (t == 0)
+                for (int j = 0; j < 9; j++) s_best[j] = s_model[j];
+            int32_t *sw = lmax;
+            lmax = llo;
+            llo = sw;
+            n_max = (uint32_t)lo_cnt;
+            changed = true;
+            st.improved++;
+        }
+        st.inner_iters++;
+        stage = kInner;
+    };
+    // LDS words reused from trip to trip, and the barrier between a trip's last read and the next write:
+    //   s_ok, s_model[0..8]: written by lane 0 at the end of fit_finish; read after pol_fit's last
+    //       barrier (s_ok by all, s_model by pol_score's prologue and by lane 0 alone in finish()); the
+    //       next fit_finish comes after the barriers of pol_fit's gather and chains;
+    //   s_model (kInit) / s_model[9..17]: written by lane 0, then the __syncthreads() before pol_score;
+    //   s_sum[0]: written in pol_seq's link step, read after pol_seq's last barrier; the next write
+    //       is behind the two barriers inside the next pol_seq;
+    //   s_draw, s_samp: a barrier after each write; the next write is behind pol_fit's barriers;
+    //   s_best: lane 0 only.
+    // Every `continue` that skips the fit or the score (finish() at the loop head, a failed fit) goes
+    // back to a trip whose first LDS write is one of the above, behind the same barriers: a path that
+    // stops short of them must add its own __syncthreads().
+    while (stage != kEnd) {
+        const int32_t *fl = nullptr;  // the list to fit (none: the first getInliers)
+        uint32_t fn = 0;
+        bool sampled = false;
+        if (stage == kInit) {
+            if (t == 0)
+                for (int j = 0; j < 9; j++) s_best[j] = s_model[j] = rec.model[j];
+        } else if (stage == kInner) {
+            if (it >= g.inner) break;
+            it++;
+            sampled = n_max > g.limit;
+            fl = sampled ? s_samp : lmax;
+            fn = sampled ? g.limit : n_max;
+        } else {  // the iterative stage's loop head
+            bool fin = k >= g.iters;
+            if (!fin) {
+                thr -= g.step;
+                fin = lo_cnt <= kM;
+            }
+            if (fin) {
+                finish();
+                continue;
+            }
+            sampled = g.limited && (uint32_t)lo_cnt > g.limit;
+            if (!sampled && (uint32_t)lo_cnt > kPolFitMax) {  // the caps rule
+                st.capped++;
+                thr = g.thr;
+                break;
+            }
+            fl = sampled ? s_samp : llo;
+            fn = sampled ? g.limit : (uint32_t)lo_cnt;
+        }
+        if (sampled) {  // generateUniqueRandomSet over the list, then list[.]
+            const int32_t *src = stage == kInner ? lmax : llo;
+            const uint32_t top = (stage == kInner ? n_max : (uint32_t)lo_cnt) - 1;
+            if (t == 0) lo_draw(item.seed, st.draws, g.limit, top, s_draw);
+            st.draws++;
+            __syncthreads();
+            if (t < g.limit) s_samp[t] = src[s_draw[t]];
+            __syncthreads();
+        }
+        if (stage != kInit) {
+            pol_fit<FUND>(pts, fl, fn, sh, s_sums, s_ws, A, V, s_v, s_model, &s_ok, nullptr);
+            st.fits++;
+            // (LDS words and pol_score's count are the same in every lane: readfirstlane says so to the
+            // compiler, which keeps the control state in scalar registers)
+            if (!__builtin_amdgcn_readfirstlane(s_ok)) {
+                if (stage == kInner) {
+                    if (sampled) continue;
+                    break;
+                }
+                if (sampled) k++;
+                else finish();
+                continue;
+            }
+        }
+        if (EST == USAC_HOMOGRAPHY && t == 0) inv3x3(s_model, s_model + 9);
+        __syncthreads();
+        if (stage == kInner) thr = g.mult * thr;
+        const uint32_t cnt = __builtin_amdgcn_readfirstlane(
+            pol_score<EST>(pts, N, s_model, stage == kInit ? g.thr : thr, stage == kInit ? lmax : llo, sh));
+        pol_seq<1, false>(sh.E, 0, cnt, sh, s_sum);
+        if (stage == kInit) {
+            n_max = cnt;
+            stage = kInner;
+            continue;
+        }
+        lo_cnt = (int32_t)cnt;
+        lo_sum = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s_sum[0])));
+        if (stage == kInner) {
+            if (lo_cnt > kM) {
+                stage = kIter;
+                k = 0;
+            }
+            continue;
+        }
+        if (!g.limited && (best_cnt > lo_cnt || (best_cnt == lo_cnt && best_sum > lo_sum))) {
+            finish();
+            continue;
+        }
+        st.iterative_iters++;
+        k++;
+    }
+    __syncthreads();  // s_best
+    if (t == 0) {
+        st.threshold = thr;
+        g.state[p] = st;
+        if (changed) {
+            usac_record r = rec;
+            for (int j = 0; j < 9; j++) r.model[j] = s_best[j];
+            r.inliers = best_cnt;
+            r.score = best_sum;
+            g.running[p] = r;
+            g.out[a] = r;
+        }
+    }
+}
+
+hipError_t launch_multi_lo(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t A,
+                           const MultiLo &lo) {
+    if (A == 0 || lo.limit == 0 || lo.limit > kLoDrawMax || lo.iters == 0) return hipErrorInvalidValue;
+    switch (estimator) {
+        case USAC_HOMOGRAPHY:
+            hipLaunchKernelGGL(k_multi_lo<USAC_HOMOGRAPHY>, dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
+            break;
+        case USAC_FUNDAMENTAL:
+            hipLaunchKernelGGL(k_multi_lo<USAC_FUNDAMENTAL>, dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
             break;
         default:
             return hipErrorInvalidValue;

@@ -23,6 +23,7 @@
 #include "usac_host.hpp"
 #include "usac_maxflow.hpp"
 #include "usac_kernels.h"
+#include "usac_lo_draw.hpp"
 
 namespace {
 
@@ -3976,7 +3977,7 @@ void usac_lo_destroy(usac_lo *h) {
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- multi-problem batches (ABI 15, 16, 17)
+// ---------------------------------------------------------------- multi-problem batches (ABI 15 .. 18)
 // P independent two-view problems in one context (kernels_multi.hip): the usac_hypothesize_score
 // round over (active problem, hypothesis tile), and a batch-granular RANSAC whose host loop only
 // reads the active problems' records once per round, evaluates the standard termination criterion
@@ -3984,7 +3985,8 @@ void usac_lo_destroy(usac_lo *h) {
 // (active problems) x R, none inside the round loop.  ABI 17 (usac_multi_run_prosac): the same loop
 // with the PROSAC sampler in closed form (usac_prosac.hpp) and PROSAC's termination scan split between
 // k_multi_prosac_scan, which stores its candidates into pinned host memory, and
-// ProsacTerminationCriteria::applyCandidates.
+// ProsacTerminationCriteria::applyCandidates.  ABI 18 (usac_multi_run_lo): either loop with k_multi_lo
+// (kernels_nonmin.hip) between the round's merge and the scan / the record copy.
 
 struct usac_multi {
     int device = 0;
@@ -3994,6 +3996,8 @@ struct usac_multi {
     std::vector<uint32_t> offsets;  // host copy, P + 1
     DevBuf pts, offs, items, samples, models, counts, sums, list, list_n, out, running, mmodels, m18, mask;
     DevBuf pol_lists, pol_out;  // the polish: two inlier lists per problem (2 x N_total), P results
+    DevBuf lo_state;            // LO (ABI 18): per problem the threshold, the draw counter, the counters
+    bool lo_state_set = false;  // usac_multi_lo: the state of an earlier call is there to continue
     void *pin = nullptr;  // pinned staging: the active list up, the records down
     size_t pin_bytes = 0;
     void *pol_pin = nullptr;  // pinned staging of the polish: P results and the mask down
@@ -4206,6 +4210,60 @@ uint32_t multi_apply_candidates(usac_multi *mc, uint32_t a, uint32_t p, uint32_t
     return mc->pterm[p]->applyCandidates(hyp_count, largest, cand, multi_cand_n_pin(mc)[a]);
 }
 
+// ---- LO-RANSAC for multi-problem batches (ABI 18)
+// the checks of usac_multi_lo / usac_multi_run_lo that precede any device call
+int multi_lo_check(usac_multi *mc, const usac_params *prm, const char *who) {
+    if (prm->lo == USAC_LO_GC || prm->sprt)
+        return fail(mc, USAC_ERR_UNSUPPORTED, std::string(who) + ": no graph-cut LO, no SPRT");
+    if (prm->lo != USAC_LO_INITLORSC && prm->lo != USAC_LO_INITFLORSC)
+        return fail(mc, USAC_ERR_ARG, std::string(who) + ": params->lo must be USAC_LO_INITLORSC or USAC_LO_INITFLORSC");
+    if (prm->lo_sample_size == 0 || prm->lo_sample_size > usac::kLoDrawMax)
+        return fail(mc, USAC_ERR_ARG, std::string(who) + ": lo_sample_size in 1..64");
+    if (prm->lo_iterative_iterations == 0) return fail(mc, USAC_ERR_ARG, std::string(who) + ": lo_iterative_iterations >= 1");
+    return USAC_OK;
+}
+
+// the LO buffers, and at the start of a run (reset) every problem's state fresh: threshold θ, counters 0
+int multi_lo_ensure(usac_multi *mc, const usac_params *prm, bool reset) {
+    const uint32_t P = mc->P;
+    HIP_TRY(mc, mc->pol_lists.reserve(sizeof(int32_t) * 2 * (size_t)mc->n_total));
+    HIP_TRY(mc, mc->lo_state.reserve(sizeof(usac_multi_lo_output) * (size_t)P));
+    if (reset || !mc->lo_state_set) {
+        usac_multi_lo_output fresh{};
+        fresh.threshold = prm->threshold;
+        const std::vector<usac_multi_lo_output> init(P, fresh);
+        HIP_TRY(mc, hipMemcpy(mc->lo_state.p, init.data(), sizeof(usac_multi_lo_output) * (size_t)P, hipMemcpyHostToDevice));
+        mc->lo_state_set = true;
+    }
+    return USAC_OK;
+}
+
+// threshold arithmetic as LoRansac's (above): the same fp32 expressions
+usac::MultiLo multi_lo_args(usac_multi *mc, const usac_params *prm, uint64_t first_hyp, bool force) {
+    usac::MultiLo lo{};
+    lo.items = mc->items.as<usac::MultiItem>();
+    lo.running = mc->running.as<usac_record>();
+    lo.out = mc->out.as<usac_record>();
+    lo.first_hyp = first_hyp;
+    lo.force = force ? 1 : 0;
+    lo.limited = prm->lo == USAC_LO_INITFLORSC ? 1 : 0;
+    lo.thr = prm->threshold;
+    lo.mult = (float)prm->lo_threshold_multiplier;
+    lo.step = (prm->threshold * prm->lo_threshold_multiplier - prm->threshold) / prm->lo_iterative_iterations;
+    lo.inner = prm->lo_inner_iterations;
+    lo.iters = prm->lo_iterative_iterations;
+    lo.limit = prm->lo_sample_size;
+    lo.lists = mc->pol_lists.as<int32_t>();
+    lo.n_total = mc->n_total;
+    lo.state = mc->lo_state.as<usac_multi_lo_output>();
+    return lo;
+}
+
+int multi_lo_fetch(usac_multi *mc, usac_multi_lo_output *lo) {
+    if (lo) HIP_TRY(mc, hipMemcpy(lo, mc->lo_state.p, sizeof(usac_multi_lo_output) * (size_t)mc->P, hipMemcpyDeviceToHost));
+    return USAC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4286,7 +4344,7 @@ void usac_multi_destroy(usac_multi *mc) {
     for (DevBuf *b : {&mc->growth, &mc->non_random0, &mc->non_random}) b->release();
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
                       &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
-                      &mc->pol_out})
+                      &mc->pol_out, &mc->lo_state})
         b->release();
     if (mc->stream) StreamPool::get().give_back(mc->stream);
     delete mc;
@@ -4340,7 +4398,7 @@ int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint3
 int usac_multi_run(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out) {
     if (!mc || !prm || !out) return USAC_ERR_ARG;
     if (prm->sprt || prm->lo != USAC_LO_NONE || prm->sampler != USAC_SAMPLER_UNIFORM)
-        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run: uniform sampler only, no SPRT, no LO");
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run: uniform sampler only, no SPRT, no LO (LO: usac_multi_run_lo)");
     const uint32_t R = prm->batch ? prm->batch : 256u;
     if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
     if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
@@ -4517,7 +4575,7 @@ int usac_multi_run_prosac(usac_multi *mc, const usac_params *prm, const uint64_t
                           usac_multi_prosac_output *pro, usac_multi_polish_output *pol, uint8_t *mask) {
     if (!mc || !prm || !out) return USAC_ERR_ARG;
     if (prm->sprt || prm->lo != USAC_LO_NONE)
-        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run_prosac: no SPRT, no LO");
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run_prosac: no SPRT, no LO (LO: usac_multi_run_lo)");
     if (prm->sampler != USAC_SAMPLER_PROSAC) return fail(mc, USAC_ERR_ARG, "usac_multi_run_prosac: the PROSAC sampler");
     const uint32_t R = prm->batch ? prm->batch : 256u;
     if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
@@ -4581,6 +4639,122 @@ int usac_multi_run_prosac(usac_multi *mc, const usac_params *prm, const uint64_t
         }
         A = keep;
     }
+    if (!pol) return USAC_OK;
+    return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
+                               sizeof(usac_record) / sizeof(float), out[0].best.model,
+                               sizeof(usac_multi_output) / sizeof(float), prm->threshold, pol, mask);
+}
+
+// ---- LO-RANSAC (ABI 18)
+int usac_lo_draw(uint64_t seed, uint64_t draw, uint32_t k, uint32_t max, int32_t *out) {
+    if (!out || k < 1 || k > usac::kLoDrawMax || max > 0x7FFFFFFFu || k > max + 1) return USAC_ERR_ARG;
+    usac::lo_draw(seed, draw, k, max, out);
+    return USAC_OK;
+}
+
+int usac_multi_lo(usac_multi *mc, const usac_params *prm, int reset, const uint64_t *seeds, usac_record *recs,
+                  usac_multi_lo_output *lo) {
+    if (!mc || !prm || !recs) return USAC_ERR_ARG;
+    int rc = multi_lo_check(mc, prm, "usac_multi_lo");
+    if (rc) return rc;
+    const uint32_t P = mc->P;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    if ((rc = multi_ensure(mc, P, 64, false)) || (rc = multi_lo_ensure(mc, prm, reset != 0))) return rc;
+    usac::MultiItem *items = multi_items_pin(mc);
+    for (uint32_t p = 0; p < P; p++) items[p] = usac::MultiItem{p, 0u, seeds ? seeds[p] : (uint64_t)prm->seed + p, 0u, 0u};
+    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)P, hipMemcpyHostToDevice, mc->stream));
+    HIP_TRY(mc, hipMemcpyAsync(mc->running.p, recs, sizeof(usac_record) * (size_t)P, hipMemcpyHostToDevice, mc->stream));
+    HIP_TRY(mc, usac::launch_multi_lo(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), P,
+                                      multi_lo_args(mc, prm, 0, true)));
+    HIP_TRY(mc, hipMemcpyAsync(recs, mc->running.p, sizeof(usac_record) * (size_t)P, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return multi_lo_fetch(mc, lo);
+}
+
+int usac_multi_run_lo(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
+                      usac_multi_lo_output *lo, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
+                      uint8_t *mask) {
+    if (!mc || !prm || !out) return USAC_ERR_ARG;
+    int rc = multi_lo_check(mc, prm, "usac_multi_run_lo");
+    if (rc) return rc;
+    if (prm->sampler != USAC_SAMPLER_UNIFORM && prm->sampler != USAC_SAMPLER_PROSAC)
+        return fail(mc, USAC_ERR_ARG, "usac_multi_run_lo: the uniform or the PROSAC sampler");
+    const bool prosac = prm->sampler == USAC_SAMPLER_PROSAC;
+    const uint32_t R = prm->batch ? prm->batch : 256u;
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
+    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    const uint32_t P = mc->P, m = mc->m;
+    if (prosac)
+        for (uint32_t p = 0; p < P; p++)
+            if (mc->offsets[p + 1] - mc->offsets[p] <= 20)
+                return fail(mc, USAC_ERR_ARG, "PROSAC needs > 20 points per problem (prosac_termination_criteria.hpp:158-163)");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    if ((rc = multi_ensure(mc, P, R, false)) || (rc = multi_lo_ensure(mc, prm, true))) return rc;
+    if (prosac && ((rc = multi_prosac_ensure(mc)) || (rc = multi_prosac_reset(mc, prm)))) return rc;
+    HIP_TRY(mc, hipMemsetAsync(mc->running.p, 0, sizeof(usac_record) * (size_t)P, mc->stream));
+    usac::MultiItem *items = multi_items_pin(mc);
+    usac_record *recs = multi_records_pin(mc, P);
+    // PROSAC, per problem: the sampler's largest_sample_size, the last scan's bound, the scans
+    std::vector<uint32_t> largest(prosac ? P : 0, m), bound(prosac ? P : 0, prm->max_iterations), scans(prosac ? P : 0, 0);
+    for (uint32_t p = 0; p < P; p++) {
+        const uint64_t seed = seeds ? seeds[p] : (uint64_t)prm->seed + p;
+        items[p] = prosac ? usac::MultiItem{p, 1u, seed, mc->offsets[p + 1] - mc->offsets[p], 0u}
+                          : usac::MultiItem{p, 0u, seed, 0u, 0u};
+        out[p] = usac_multi_output{};
+    }
+    const usac::StandardTerminationCriteria term(prm->desired_prob, m, 0, prm->max_iterations);
+    uint32_t A = P;
+    for (uint32_t round = 0; A > 0; round++) {
+        const uint64_t first = (uint64_t)round * R, done = first + R;
+        HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
+                                   mc->stream));
+        usac::MultiRound r = multi_round(mc, A, R, first, prm->threshold, prm->dlt_mode);
+        r.running = mc->running.as<usac_record>();
+        if (prosac) r.growth = mc->growth.as<uint32_t>();
+        HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
+        // LO of the round's new bests; the scan and the record copy see the LO'd records
+        HIP_TRY(mc, usac::launch_multi_lo(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), A,
+                                          multi_lo_args(mc, prm, first, false)));
+        if (prosac) HIP_TRY(mc, multi_launch_scan(mc, A, first, prm->threshold));
+        HIP_TRY(mc, hipMemcpyAsync(recs, mc->out.p, sizeof(usac_record) * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
+        HIP_TRY(mc, stream_wait(mc->stream));
+        uint32_t keep = 0;
+        for (uint32_t a = 0; a < A; a++) {
+            const usac::MultiItem it = items[a];
+            const uint32_t p = it.problem, n = mc->offsets[p + 1] - mc->offsets[p];
+            uint32_t bnd, L = 0, T = 0;
+            if (prosac) {  // usac_multi_run_prosac's round end
+                const uint32_t *g = mc->growth_host[p]->data();
+                const uint32_t n_prosac = usac::prosac_round_lanes(g, n, it.clock, it.term_len, R);
+                L = it.term_len;
+                if (recs[a].valid && recs[a].hyp_index >= first) {
+                    const uint32_t j = (uint32_t)(recs[a].hyp_index - first);
+                    const uint32_t at = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], j);
+                    bound[p] = multi_apply_candidates(mc, a, p, (uint32_t)recs[a].hyp_index, at);
+                    L = mc->pterm[p]->terminationLength();
+                    scans[p]++;
+                }
+                largest[p] = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], R - 1);
+                T = it.clock + n_prosac;
+                bnd = bound[p];
+            } else {
+                bnd = term.getUpBoundIterations((uint32_t)recs[a].inliers, n);
+            }
+            if (done >= std::min(prm->max_iterations, bnd)) {
+                usac_multi_output &o = out[p];
+                o.best = recs[a];
+                o.hypotheses = (uint32_t)done;
+                o.rounds = round + 1;
+                o.bound = bnd;
+                o.status = recs[a].inliers > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
+                if (prosac && pro) pro[p] = usac_multi_prosac_output{L, largest[p], T, scans[p]};
+            } else {
+                items[keep++] = prosac ? usac::MultiItem{p, T, it.seed, L, 0u} : it;
+            }
+        }
+        A = keep;
+    }
+    if ((rc = multi_lo_fetch(mc, lo))) return rc;
     if (!pol) return USAC_OK;
     return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
                                sizeof(usac_record) / sizeof(float), out[0].best.model,

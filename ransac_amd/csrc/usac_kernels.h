@@ -392,6 +392,25 @@ constexpr int32_t kMultiPolishDefer = 1;
 hipError_t launch_multi_polish(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,
                                uint32_t n_total, const float *models, uint32_t model_stride, float thr, int32_t *lists,
                                usac_multi_polish_output *out, uint8_t *mask);
+// LO-RANSAC of every active problem whose running record improved in the round (kernels_nonmin.hip
+// k_multi_lo: k_multi_polish's workgroup under InnerLocalOptimization::GetModelScore's control flow).
+// lists: launch_multi_polish's 2 x n_total int32; state: per problem, the LO threshold, the draw
+// counter and the counters, read and written by the kernel; running / out: the LO'd record replaces
+// the problem's running record and the entry's round record.  limit <= 64, iters >= 1.
+struct MultiLo {
+    const MultiItem *items;  // [A]: problem, seed (the LO draws' key)
+    usac_record *running;    // indexed by problem
+    usac_record *out;        // [A]
+    uint64_t first_hyp;      // a record improved in the round when hyp_index >= first_hyp
+    int32_t force, limited;  // force: every valid record counts as new; limited: GetScoreLimited
+    float thr, mult, step;   // θ, (float)lo_threshold_multiplier, the iterative stage's threshold step
+    uint32_t inner, iters, limit;
+    int32_t *lists;
+    uint32_t n_total;
+    usac_multi_lo_output *state;
+};
+hipError_t launch_multi_lo(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t A,
+                           const MultiLo &lo);
 
 // k nearest neighbours of every point (kernels_knn.hip, nearest_neighbors.cpp:69-128):
 // idx / d2 (nullable) n x k, self excluded, ascending distance, ties by index; 1 <= k <= 32

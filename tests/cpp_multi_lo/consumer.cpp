@@ -1,0 +1,71 @@
+// A consumer of usac_gpu::MultiContext::runLo / lo (include/usac_gpu.hpp), C++11, no HIP headers:
+//   consumer abi
+//   consumer run <estimator> <P> <pts.f32> <offsets.u32> <thr> <prob> <max_iters> <R> <seed> <sampler> <lo>
+// `run` prints one JSON object: per problem the result of runLo, of the C call usac_multi_run_lo on the
+// same context, and of one more lo() call on runLo's records (floats as their int32 bit patterns).
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "consumer_host.hpp"
+#include "usac_gpu.hpp"
+
+int main(int argc, char **argv) {
+    try {
+        if (argc >= 2 && !std::strcmp(argv[1], "abi")) {
+            std::printf("{\"abi\": %d, \"header\": %d}\n", usac_abi_version(), USAC_ABI_VERSION);
+            return usac_abi_version() == USAC_ABI_VERSION ? 0 : 1;
+        }
+        if (argc != 13 || std::strcmp(argv[1], "run")) {
+            std::fprintf(stderr, "usage: consumer abi | run est P pts offsets thr prob max_iters R seed sampler lo\n");
+            return 2;
+        }
+        const usac_gpu::ESTIMATOR est = (usac_gpu::ESTIMATOR)std::atoi(argv[2]);
+        const uint32_t P = (uint32_t)std::atoi(argv[3]);
+        const std::vector<uint32_t> offsets = consumer_host::read_file<uint32_t>(argv[5], (size_t)P + 1);
+        const std::vector<float> pts = consumer_host::read_file<float>(argv[4], 4 * (size_t)offsets[P]);
+        const bool prosac = std::atoi(argv[11]) == (int)usac_gpu::Prosac;
+        usac_gpu::Model model((float)std::atof(argv[6]), est == usac_gpu::Fundamental ? 7u : 4u,
+                              (float)std::atof(argv[7]), 5, est, prosac ? usac_gpu::Prosac : usac_gpu::Uniform);
+        model.max_iterations = (unsigned int)std::atoi(argv[8]);
+        model.batch = (uint32_t)std::atoi(argv[9]);
+        model.seed = (uint32_t)std::atoi(argv[10]);
+        model.lo = (usac_gpu::LocOpt)std::atoi(argv[12]);
+        model.lo_inner_iterations = 10;
+        model.ResetRandomGenerator(false);
+
+        usac_gpu::MultiContext mc(est, pts.data(), offsets);
+        const usac_gpu::MultiContext::Lo res = mc.runLo(model);
+        usac_params prm = model.params();
+        prm.seed = model.seed;
+        std::vector<usac_multi_output> out(P);
+        std::vector<usac_multi_lo_output> lo(P);
+        std::vector<usac_multi_prosac_output> pro(P);
+        mc.check(usac_multi_run_lo(mc.get(), &prm, nullptr, out.data(), lo.data(), pro.data(), nullptr, nullptr),
+                 "usac_multi_run_lo");
+        // one more LO call on the run's records, through the hook
+        std::vector<usac_record> recs(P);
+        for (uint32_t p = 0; p < P; p++) recs[p] = res.run[p].best;
+        const std::vector<usac_multi_lo_output> hook = mc.lo(model, recs);
+
+        std::printf("{\"problems\": [");
+        for (unsigned int p = 0; p < mc.problems(); p++) {
+            usac_multi_output again = res.run[p];
+            again.best = recs[p];
+            std::printf("%s{\"cpp\": %s, \"c\": %s, \"hook\": %s}", p ? ", " : "",
+                        consumer_host::problem_json(res.run[p], res.lo[p], prosac ? &res.prosac[p] : nullptr).c_str(),
+                        consumer_host::problem_json(out[p], lo[p], prosac ? &pro[p] : nullptr).c_str(),
+                        consumer_host::problem_json(again, hook[p], nullptr).c_str());
+        }
+        std::printf("]}\n");
+        return 0;
+    } catch (const usac_gpu::Error &e) {
+        std::fprintf(stderr, "usac_gpu::Error %d: %s\n", e.code, e.what());
+        return 1;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+}

@@ -24,6 +24,12 @@ MultiContext.run_prosac is alternated with MultiContext.run (uniform sampler) on
 with --polish both runs include the polish.  Reported for both: median ms and spread, rounds per pair,
 the rounds of the longest pair (= the launch chains of the run) and ms per such round, total
 hypotheses, mean best (and polished) inlier counts.  No loop over single contexts in this mode.
+
+--lo lorsc|florsc compares the LO run with the run without it: MultiContext.run_lo (inner + iterative
+LO-RANSAC of every round's new bests on the device) is alternated with MultiContext.run -- or, with
+--sampler prosac, with MultiContext.run_prosac -- on the same inputs; with --polish both include the
+polish.  Reported for both: the --sampler prosac mode's figures; for the LO run also the mean LO calls,
+fits, improvements and capped calls per pair.  No loop over single contexts in this mode.
 """
 import argparse
 import ctypes
@@ -233,6 +239,61 @@ def main_prosac(a, mc, model, est):
     return 0
 
 
+def main_lo(a, mc, model, est):
+    """--lo: MultiContext.run_lo against the same run without LO (run, or run_prosac with --sampler
+    prosac) on the same inputs, alternated, host-timed, medians and spreads as in main()"""
+    prosac = a.sampler == "prosac"
+    base = usac.Model(model.threshold, mc.m, model.desired_prob, 5, est,
+                      usac.SAMPLER.Prosac if prosac else usac.SAMPLER.Uniform)
+    base.max_iterations, base.batch, base.seed = model.max_iterations, model.batch, model.seed
+    base.setDLTMode(model.dlt_mode)
+    lmodel = usac.Model(model.threshold, mc.m, model.desired_prob, 5, est, base.sampler)
+    lmodel.max_iterations, lmodel.batch, lmodel.seed = model.max_iterations, model.batch, model.seed
+    lmodel.setDLTMode(model.dlt_mode)
+    lmodel.lo = usac.LocOpt.InItLORsc if a.lo == "lorsc" else usac.LocOpt.InItFLORsc
+    run_base = mc.run_prosac if prosac else mc.run
+
+    def summary(res, ms):
+        rounds = [r["rounds"] for r in res]
+        d = {"ms": round(statistics.median(ms), 3), "spread_ms": round(max(ms) - min(ms), 3),
+             "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
+             "mean_rounds": round(float(np.mean(rounds)), 2), "launch_rounds": int(max(rounds)),
+             "hypotheses": int(sum(r["hypotheses"] for r in res)),
+             "mean_best_inliers": round(float(np.mean([r["best"]["inliers"] for r in res])), 2)}
+        if a.polish:
+            d["mean_polished_inliers"] = round(float(np.mean([r["polished"]["inliers"] for r in res])), 2)
+        return d
+
+    for _ in range(a.warmup):
+        rl, rb = mc.run_lo(lmodel, polish=a.polish), run_base(base, polish=a.polish)
+    tl, tb = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        rl = mc.run_lo(lmodel, polish=a.polish)
+        t1 = time.perf_counter()
+        rb = run_base(base, polish=a.polish)
+        t2 = time.perf_counter()
+        tl.append((t1 - t0) * 1e3)
+        tb.append((t2 - t1) * 1e3)
+    line = {"bench": "multi_lo", "lo": a.lo, "sampler": a.sampler, "estimator": a.estimator, "pairs": a.pairs,
+            "points": a.points, "round": a.R, "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio,
+            "dlt": a.dlt, "reps": a.reps, "polish": bool(a.polish), "with_lo": summary(rl, tl),
+            "without_lo": summary(rb, tb)}
+    for key in ("lo_calls", "fits", "improved", "capped", "inner_iters", "iterative_iters"):
+        line["with_lo"]["mean_" + key] = round(float(np.mean([r["lo"][key] for r in rl])), 3)
+    line["ratio_lo_over_without"] = round(line["with_lo"]["ms"] / line["without_lo"]["ms"], 2)
+    line["lo_faster_beyond_spread"] = bool(line["without_lo"]["ms"] - line["with_lo"]["ms"] >
+                                           max(line["with_lo"]["spread_ms"], line["without_lo"]["spread_ms"]))
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    mc.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=512)
@@ -250,6 +311,9 @@ def main():
                          "alone and against the loop over contexts with the polish restated per context")
     ap.add_argument("--sampler", choices=["uniform", "prosac"], default="uniform",
                     help="prosac: quality-sorted inputs, MultiContext.run_prosac against the uniform multi run")
+    ap.add_argument("--lo", choices=["lorsc", "florsc"], default=None,
+                    help="MultiContext.run_lo (inner + iterative LO-RANSAC, unlimited / limited) against the same "
+                         "run without LO; with --sampler prosac both use the PROSAC sampler")
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
@@ -263,6 +327,8 @@ def main():
     seeds = [model.seed + p for p in range(a.pairs)]
 
     mc = usac.MultiContext(est, sets)
+    if a.lo:
+        return main_lo(a, mc, model, est)
     if a.sampler == "prosac":
         return main_prosac(a, mc, model, est)
     ctxs = [usac.Context(est, p) for p in sets]
