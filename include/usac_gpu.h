@@ -58,7 +58,10 @@
  *                                  usac_multi_prosac_scan exposing its parts;
  *                                  ABI 18: usac_multi_run_lo, inner + iterative LO-RANSAC of every
  *                                  round's new bests in one launch (one workgroup per problem), with
- *                                  usac_lo_draw / usac_multi_lo exposing its parts
+ *                                  usac_lo_draw / usac_multi_lo exposing its parts;
+ *                                  ABI 19: usac_multi_run_sprt, SPRT verification of every slot on the
+ *                                  device with one test per problem and round, with usac_multi_sprt_setup /
+ *                                  usac_multi_hypothesize_score_sprt / usac_multi_sprt_update exposing its parts
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -73,7 +76,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 18
+#define USAC_ABI_VERSION 19
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -529,7 +532,7 @@ int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint3
  * problem is finished once (r + 1) R >= min(max_iterations, bound_p).  The clamp to max_iterations is
  * a deviation from ransac.cpp, which lets the bound exceed it: a batch call must stay bounded.  A run
  * evaluates at least as many hypotheses as the bound asks for, so the confidence guarantee holds.
- * This is NOT the glibc-stream Ransac::run (usac_ransac_run): no SPRT or NAPSAC, PROSAC is
+ * This is NOT the glibc-stream Ransac::run (usac_ransac_run): no NAPSAC, SPRT is usac_multi_run_sprt's, PROSAC is
  * usac_multi_run_prosac's and LO is usac_multi_run_lo's -- params->sprt, ->lo or a sampler other than USAC_SAMPLER_UNIFORM return
  * USAC_ERR_UNSUPPORTED here -- and it stops at the best minimal model; usac_multi_run_polished adds
  * the run's non-minimal polish.
@@ -567,8 +570,8 @@ int usac_multi_polish(usac_multi *mc, const float *models, float thr,
 /* usac_multi_run, then the polish of every problem's best model at params->threshold without the
  * records leaving the device in between; out as usac_multi_run writes it (unchanged), pol / mask as
  * usac_multi_polish (a problem without a model: USAC_ERR_NO_MODEL in both).  The remaining deviations
- * from Ransac::run are usac_multi_run's: no SPRT or NAPSAC (PROSAC: usac_multi_run_prosac, LO:
- * usac_multi_run_lo), batch-granular termination.
+ * from Ransac::run are usac_multi_run's: no NAPSAC (PROSAC: usac_multi_run_prosac, LO:
+ * usac_multi_run_lo, SPRT: usac_multi_run_sprt), batch-granular termination.
  * NULL mc, params, out or pol: USAC_ERR_ARG before any device call. */
 int usac_multi_run_polished(usac_multi *mc, const usac_params *params, const uint64_t *seeds,
                             usac_multi_output *out, usac_multi_polish_output *pol, uint8_t *mask);
@@ -623,7 +626,7 @@ typedef struct usac_multi_prosac_output {
  * Deviations from Ransac::run with PROSAC: batch granularity, two ways -- only a round's final best is
  * scanned (the reference scans every new best), and L changes only between rounds (the reference's next
  * sample already sees it); the clamp to max_iterations; the device random stream (the reference draws
- * from std::mt19937).  No SPRT or NAPSAC; LO: usac_multi_run_lo.
+ * from std::mt19937).  No NAPSAC; LO: usac_multi_run_lo, SPRT: usac_multi_run_sprt.
  * USAC_ERR_UNSUPPORTED for params->sprt or ->lo; USAC_ERR_ARG for a sampler other than
  * USAC_SAMPLER_PROSAC, any n_p <= 20 (the reference reads point 20), a bad batch or dlt_mode, NULL mc,
  * params or out -- all before any device call.
@@ -692,7 +695,7 @@ int usac_multi_lo(usac_multi *mc, const usac_params *params, int reset, const ui
  * merges, the "improved in this round" test and PROSAC's hypCount read it).
  * Deviations from Ransac::run: only a round's final best is optimised (the reference optimises every new
  * best); the LO draws come from the device stream (usac_lo_draw); the caps rule of usac_multi_lo; and
- * those of usac_multi_run / usac_multi_run_prosac.  No SPRT or NAPSAC.
+ * those of usac_multi_run / usac_multi_run_prosac.  No NAPSAC; SPRT (without LO): usac_multi_run_sprt.
  * USAC_ERR_UNSUPPORTED for USAC_LO_GC or params->sprt; USAC_ERR_ARG for USAC_LO_NONE, lo_sample_size 0
  * or > 64, lo_iterative_iterations 0, USAC_SAMPLER_NAPSAC, a bad batch or dlt_mode, NULL mc, params or
  * out, and with PROSAC any n_p <= 20 -- all before any device call.
@@ -701,6 +704,104 @@ int usac_multi_lo(usac_multi *mc, const usac_params *params, int reset, const ui
 int usac_multi_run_lo(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
                       usac_multi_lo_output *lo, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
                       uint8_t *mask);
+
+/* ---- multi-problem batches: SPRT verification (ABI 19) ----------------------------------------------
+ * A batch-granular SPRT: every problem has its own test (epsilon, delta, A), fixed for a round of R
+ * hypotheses; every slot of the round is verified on the device by usac_set_sprt's throughput test --
+ * the reference's fp64 lambda walk (sprt.hpp:209-234) over the problem's pool-ordered points from the
+ * slot tile's start (tile * 7919) mod n_p, the first 64 pool points by a wave per tile, the rest by a
+ * workgroup per survivor.  A rejected slot reads count -1, sum 0 (never a best); an accepted one reads
+ * its inliers over all n_p points and sum = (float)count (sprt.hpp:276-281).  Problem p's pool is the
+ * reference's shuffle after srandom(pool_seed_p) (usac_sprt_pool).
+ *
+ * One problem's statistics of a round. */
+typedef struct usac_multi_sprt_stats {
+    uint32_t accepted;        /* slots accepted */
+    uint32_t rejected_head;   /* slots rejected within the first min(n_p, 64) pool points' launch */
+    uint32_t rejected_tail;   /* slots rejected past them */
+    uint32_t head_inliers;    /* over the rejected_head slots: inliers seen up to the rejecting point */
+    uint32_t head_points;     /* over the same slots: points tested up to it */
+    uint32_t pad;
+    uint64_t points_tested;   /* point tests done (a tail rejection counts to the end of its chunk) */
+} usac_multi_sprt_stats;
+
+/* One entry of a problem's test history (the reference's SPRT_history). */
+typedef struct usac_multi_sprt_test {
+    double epsilon, delta, A;
+    int32_t k;                /* hypotheses evaluated under the previous test */
+    int32_t pad;
+} usac_multi_sprt_test;
+
+/* One problem's SPRT state at the end of usac_multi_run_sprt. */
+typedef struct usac_multi_sprt_output {
+    double epsilon, delta, A; /* the last test */
+    uint32_t tests;           /* tests designed, the first one included */
+    uint32_t accepted;        /* slots accepted, over the run */
+    uint32_t rejected;        /* slots rejected, over the run */
+    uint32_t pad;
+    uint64_t points_tested;   /* over the run */
+} usac_multi_sprt_output;
+
+/* Builds the problems' pools on the host (pool_seeds: P seeds, NULL: p + 1) and the pool-ordered copy
+ * of the points on the device; once per context, a later call replaces both.  The SPRT entry points
+ * below call it with the default seeds if it was never called. */
+int usac_multi_sprt_setup(usac_multi *mc, const uint32_t *pool_seeds);
+
+/* usac_multi_hypothesize_score with SPRT verification in place of the scoring.  eps_delta (nullable):
+ * n_problems x 2 doubles, (epsilon, delta) of problems[i]'s test; a 0 stands for the estimator's
+ * default (H: 0.1, 0.01; F: 0.2, 0.05); A = estimateThresholdA(epsilon, delta).  counts / sums / best as
+ * usac_multi_hypothesize_score's, over the verified slots; stats (nullable): n_problems entries;
+ * starts (nullable): n_problems x R x S first pool positions, UINT32_MAX on an empty F slot.
+ * USAC_ERR_ARG also for an epsilon or delta outside (0, 1) or delta >= epsilon -- before any device
+ * call.  The certificate's margin and climb limit are usac_set_sprt's, its budget taken at each
+ * problem's n_p, with the same USAC_SPRT_CERT_MARGIN / USAC_SPRT_CERT_CLIMB test overrides. */
+int usac_multi_hypothesize_score_sprt(usac_multi *mc, const uint32_t *problems, uint32_t n_problems,
+                                      const int32_t *samples, uint32_t R, const uint64_t *seeds, uint64_t first_hyp,
+                                      float thr, int dlt_mode, const double *eps_delta, int32_t *counts, float *sums,
+                                      usac_record *best, usac_multi_sprt_stats *stats, uint32_t *starts);
+
+/* The per-round update of one problem's test, on the host (no context, no device) -- the function
+ * usac_multi_run_sprt applies after every round.  State: hist[0 .. *n_hist) (capacity cap), *last_update,
+ * *bound.  *n_hist == 0 initialises it as the reference's constructor does (sprt.hpp:114-170: the
+ * estimator's epsilon_0, delta_0, A_0 = estimateThresholdA, k = 0; last_update 0; bound =
+ * max_iterations) before anything else; done == 0 then returns.  Otherwise, after a round that ends at
+ * `done` hypotheses, with (epsilon, delta) the current (last) test:
+ *   1. head_points > 0: d = (float)head_inliers / (float)head_points; new_delta = d > 0 &&
+ *      fabs(delta - d) / delta > 0.05 (sprt.hpp:298, over the round's head rejections);
+ *   2. improved != 0 (the running record improved in the round): e = (double)((float)best_inliers /
+ *      (float)n_points) (sprt.hpp:270);
+ *   3. with e' / d' the new values where set, else the current ones: if either is set and 0 < d' < e' <
+ *      1, the test {e', d', estimateThresholdA(e', d'), k = done - *last_update} is appended and
+ *      *last_update = done.  The guard is a deviation from the reference, which would design a test with
+ *      epsilon = 1 or delta >= epsilon;
+ *   4. improved: *bound = min(term_bound, getUpperBoundIterations(best_inliers)) (sprt.hpp:371-393 over the
+ *      history, ransac.cpp:126-132), term_bound being the caller's termination bound for that count.
+ * Returns USAC_OK, or USAC_ERR_ARG for a NULL pointer, an estimator other than homography / fundamental,
+ * n_points < m, *n_hist > cap, or a test to append with *n_hist == cap. */
+int usac_multi_sprt_update(int estimator, uint32_t n_points, uint32_t m, uint32_t max_iterations,
+                           usac_multi_sprt_test *hist, uint32_t *n_hist, uint32_t cap, uint32_t *last_update,
+                           uint32_t *bound, uint32_t done, uint32_t head_inliers, uint32_t head_points, int improved,
+                           uint32_t best_inliers, uint32_t term_bound);
+
+/* usac_multi_run (params->sampler = USAC_SAMPLER_UNIFORM) or usac_multi_run_prosac (USAC_SAMPLER_PROSAC)
+ * with SPRT verification: per round the active list and its tests go up, the round runs solve, SPRT
+ * head + tail, argmax / merge and (PROSAC) the scan, the records and statistics come down in one copy,
+ * and the host applies usac_multi_sprt_update to every active problem with term_bound =
+ * usac_std_termination(best.inliers, ...) or the PROSAC scan's bound.  A problem is finished once
+ * (r + 1) R >= min(max_iterations, bound_p).
+ * Deviations from Ransac::run with SPRT: batch granularity (one test per problem and round, at most one
+ * re-design per round); delta^ averaged over the round's head rejections; max_hypothesis_test_before_sprt
+ * is not applied (a rejected model is never a best, as in usac_set_sprt's mode); the starts are per slot
+ * tile instead of the rolling pool index; the guard of usac_multi_sprt_update; and those of usac_multi_run /
+ * usac_multi_run_prosac.  No NAPSAC; LO with SPRT would mix sum scores with count scores and is left out.
+ * USAC_ERR_ARG for params->sprt == 0, USAC_SAMPLER_NAPSAC, a bad batch or dlt_mode, NULL mc, params or
+ * out, and with PROSAC any n_p <= 20; USAC_ERR_UNSUPPORTED for params->lo != USAC_LO_NONE -- all before
+ * any device call.
+ * out / pro / pol / mask as usac_multi_run_prosac's (pro is written only with PROSAC; the polish reads
+ * only the record's model); sprt (nullable): P states. */
+int usac_multi_run_sprt(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
+                        usac_multi_sprt_output *sprt, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
+                        uint8_t *mask);
 
 /* ---- self-test hooks (ABI 13) ------------------------------------------------------- */
 /* The essential 5-point solver's root step alone (five_points.cpp:139-157: rpoly_ak1's real zeros

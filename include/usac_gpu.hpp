@@ -707,6 +707,38 @@ public:
         return out;
     }
 
+    // usac_multi_sprt_setup: the problems' SPRT pools (the reference's shuffle after srandom(seeds[p]),
+    // default p + 1) and the pool-ordered copy of the points on the device; once per context
+    void setSprtPool(const std::vector<uint32_t> &seeds = std::vector<uint32_t>()) const {
+        if (!seeds.empty() && seeds.size() != problems()) throw Error(USAC_ERR_ARG, "setSprtPool: one seed per problem");
+        check(usac_multi_sprt_setup(mc_, seeds.empty() ? nullptr : seeds.data()), "MultiContext::setSprtPool");
+    }
+
+    // one problem's result of runSprt: run()'s output, the SPRT state at the end and, with the PROSAC
+    // sampler, the PROSAC state (empty otherwise)
+    struct Sprt {
+        std::vector<usac_multi_output> run;
+        std::vector<usac_multi_sprt_output> sprt;
+        std::vector<usac_multi_prosac_output> prosac;
+    };
+
+    // usac_multi_run_sprt: run() (model.sampler = Uniform) or runProsac() (Prosac) with SPRT verification of
+    // every slot on the device, one test per problem and round (model.sprt set, model.lo = NullLO)
+    Sprt runSprt(const Model &model, const std::vector<uint64_t> &seeds = std::vector<uint64_t>()) const {
+        usac_params p = model.params();
+        p.seed = model.seed;
+        const unsigned int P = problems();
+        if (!seeds.empty() && seeds.size() != P) throw Error(USAC_ERR_ARG, "runSprt: one seed per problem");
+        Sprt out;
+        out.run.resize(P);
+        out.sprt.resize(P);
+        if (p.sampler == USAC_SAMPLER_PROSAC) out.prosac.resize(P);
+        check(usac_multi_run_sprt(mc_, &p, seeds.empty() ? nullptr : seeds.data(), out.run.data(), out.sprt.data(),
+                                  out.prosac.empty() ? nullptr : out.prosac.data(), nullptr, nullptr),
+              "MultiContext::runSprt");
+        return out;
+    }
+
 private:
     void splitMask(const std::vector<uint8_t> &mask, std::vector<std::vector<int> > *out) const {
         const unsigned int P = problems();

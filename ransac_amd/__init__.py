@@ -150,6 +150,33 @@ class _MultiLoOutput(ctypes.Structure):
         return d
 
 
+class _MultiSprtStats(ctypes.Structure):
+    """usac_multi_sprt_stats (include/usac_gpu.h): one problem's SPRT statistics of a round."""
+    _fields_ = [("accepted", ctypes.c_uint32), ("rejected_head", ctypes.c_uint32), ("rejected_tail", ctypes.c_uint32),
+                ("head_inliers", ctypes.c_uint32), ("head_points", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+                ("points_tested", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+class _MultiSprtTest(ctypes.Structure):
+    """usac_multi_sprt_test (include/usac_gpu.h): one entry of a problem's SPRT test history."""
+    _fields_ = [("epsilon", ctypes.c_double), ("delta", ctypes.c_double), ("A", ctypes.c_double),
+                ("k", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class _MultiSprtOutput(ctypes.Structure):
+    """usac_multi_sprt_output (include/usac_gpu.h): one problem's SPRT state after usac_multi_run_sprt."""
+    _fields_ = [("epsilon", ctypes.c_double), ("delta", ctypes.c_double), ("A", ctypes.c_double),
+                ("tests", ctypes.c_uint32), ("accepted", ctypes.c_uint32), ("rejected", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32), ("points_tested", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {"epsilon": float(self.epsilon), "delta": float(self.delta), "A": float(self.A), "tests": int(self.tests),
+                "accepted": int(self.accepted), "rejected": int(self.rejected), "points_tested": int(self.points_tested)}
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -172,6 +199,7 @@ ABI_SYMBOLS = [
     "usac_multi_run_polished",
     "usac_prosac_schedule", "usac_multi_draw_samples", "usac_multi_run_prosac", "usac_multi_prosac_scan",
     "usac_lo_draw", "usac_multi_lo", "usac_multi_run_lo",
+    "usac_multi_sprt_setup", "usac_multi_hypothesize_score_sprt", "usac_multi_sprt_update", "usac_multi_run_sprt",
 ]
 
 
@@ -292,6 +320,16 @@ def lib():
                                          _P(_MultiLoOutput)]),
         "usac_multi_run_lo": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
                                              _P(_MultiLoOutput), _P(_MultiProsacOutput), _P(_MultiPolishOutput), u8p]),
+        "usac_multi_sprt_setup": (ctypes.c_int, [_vp, u32p]),
+        "usac_multi_hypothesize_score_sprt": (ctypes.c_int, [_vp, u32p, ctypes.c_uint32, i32p, ctypes.c_uint32,
+                                                             _P(ctypes.c_uint64), ctypes.c_uint64, ctypes.c_float,
+                                                             ctypes.c_int, _P(ctypes.c_double), i32p, f32p, _P(Record),
+                                                             _P(_MultiSprtStats), u32p]),
+        "usac_multi_sprt_update": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_uint32] * 3 + [_P(_MultiSprtTest), u32p,
+                                                  ctypes.c_uint32, u32p, u32p] + [ctypes.c_uint32] * 3 +
+                                   [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]),
+        "usac_multi_run_sprt": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
+                                               _P(_MultiSprtOutput), _P(_MultiProsacOutput), _P(_MultiPolishOutput), u8p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -359,6 +397,56 @@ def lo_draw(seed, draw, k, max):
     if rc:
         raise UsacError(rc, "usac_lo_draw")
     return out
+
+
+class MultiSprtState:
+    """One problem's SPRT state of a multi-problem run, advanced by usac_multi_sprt_update -- the host
+    function usac_multi_run_sprt applies after every round (no context, no device).  history: a list of
+    (epsilon, delta, A, k); last_update; bound (max_iterations until a round improves the record)."""
+
+    def __init__(self, estimator, n_points, m, max_iterations, cap=256):
+        self.estimator, self.n, self.m, self.max_iterations = int(estimator), int(n_points), int(m), int(max_iterations)
+        self._hist = (_MultiSprtTest * cap)()
+        self._n = ctypes.c_uint32(0)
+        self._last = ctypes.c_uint32(0)
+        self._bound = ctypes.c_uint32(0)
+        self._call(0, 0, 0, False, 0, 0)
+
+    def _call(self, done, head_inliers, head_points, improved, best_inliers, term_bound):
+        rc = lib().usac_multi_sprt_update(self.estimator, self.n, self.m, self.max_iterations, self._hist,
+                                          ctypes.byref(self._n), len(self._hist), ctypes.byref(self._last),
+                                          ctypes.byref(self._bound), int(done), int(head_inliers), int(head_points),
+                                          1 if improved else 0, int(best_inliers), int(term_bound))
+        if rc:
+            raise UsacError(rc, "usac_multi_sprt_update")
+
+    def update(self, done, head_inliers, head_points, improved, best_inliers=0, term_bound=0):
+        """the update after a round that ends at `done` hypotheses; True when a new test was designed"""
+        before = self._n.value
+        self._call(done, head_inliers, head_points, improved, best_inliers, term_bound)
+        return self._n.value > before
+
+    @property
+    def history(self):
+        return [(h.epsilon, h.delta, h.A, int(h.k)) for h in self._hist[:self._n.value]]
+
+    @property
+    def test(self):
+        h = self._hist[self._n.value - 1]
+        return h.epsilon, h.delta, h.A
+
+    @property
+    def last_update(self):
+        return int(self._last.value)
+
+    @property
+    def bound(self):
+        return int(self._bound.value)
+
+
+def multi_sprt_update(state, done, head_inliers, head_points, improved, best_inliers=0, term_bound=0):
+    """usac_multi_sprt_update on a MultiSprtState (see MultiSprtState.update)."""
+    return state.update(done, head_inliers, head_points, improved, best_inliers, term_bound)
 
 
 def sprt_pool(seed, estimator, n_points, m):
@@ -920,6 +1008,77 @@ class MultiContext:
                                             _ptr(mask, ctypes.c_uint8)), "multi_run_lo")
         res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
                 "bound": int(o.bound), "status": int(o.status), "lo": q.as_dict()} for o, q in zip(out, lo)]
+        if p.sampler == int(SAMPLER.Prosac):
+            for r, q in zip(res, pro):
+                r.update(termination_length=int(q.termination_length), largest_sample_size=int(q.largest_sample_size),
+                         clock=int(q.clock), scans=int(q.scans))
+        if polish:
+            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
+                r["polished"] = po
+                r["inliers"] = idx
+        return res
+
+    def set_sprt_pool(self, seeds=None):
+        """usac_multi_sprt_setup: the problems' SPRT pools (the reference's shuffle after srandom(seeds[p]),
+        default p + 1 -- what Context.set_sprt(seed=seeds[p]) uses) and the pool-ordered copy of the
+        points on the device.  Once per context; the SPRT calls below do it with the default seeds
+        if it was never called."""
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint32)
+        if sd is not None and sd.size != self.P:
+            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
+        self._check(lib().usac_multi_sprt_setup(self._h, _ptr(sd, ctypes.c_uint32)), "multi_sprt_setup")
+
+    def hypothesize_score_sprt(self, R, seeds=None, first_hyp=0, thr=2.0, problems=None, samples=None,
+                               eps_delta=None):
+        """usac_multi_hypothesize_score_sprt: hypothesize_score() with every slot verified by its problem's
+        SPRT (eps_delta: A x 2 doubles, a 0 = the estimator's default) instead of scored.  Returns
+        (counts A x R*spk [-1: rejected or empty], sums [(float)count], list of A best-record dicts,
+        list of A statistics dicts, starts A x R*spk uint32 [0xFFFFFFFF: an empty F slot])."""
+        A = self.P if problems is None else len(problems)
+        pr = None if problems is None else np.ascontiguousarray(problems, dtype=np.uint32)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != A:
+            raise ValueError("seeds: one per listed problem (%d), got %d" % (A, sd.size))
+        sm = None
+        if samples is not None:
+            sm = np.ascontiguousarray(samples, dtype=np.int32)
+            if sm.size != A * R * self.m:
+                raise ValueError("samples must be %d x %d x %d" % (A, R, self.m))
+        ed = None
+        if eps_delta is not None:
+            ed = np.ascontiguousarray(eps_delta, dtype=np.float64)
+            if ed.size != 2 * A:
+                raise ValueError("eps_delta must be %d x 2" % A)
+        c = np.zeros((A, R * self.spk), dtype=np.int32)
+        s = np.zeros((A, R * self.spk), dtype=np.float32)
+        st = np.zeros((A, R * self.spk), dtype=np.uint32)
+        best = (Record * max(A, 1))()
+        stats = (_MultiSprtStats * max(A, 1))()
+        self._check(lib().usac_multi_hypothesize_score_sprt(
+            self._h, _ptr(pr, ctypes.c_uint32), A, _ptr(sm, ctypes.c_int32), R, _ptr(sd, ctypes.c_uint64), first_hyp,
+            ctypes.c_float(thr), int(self.dlt_mode), _ptr(ed, ctypes.c_double), _ptr(c, ctypes.c_int32),
+            _ptr(s, ctypes.c_float), best, stats, _ptr(st, ctypes.c_uint32)), "multi_hypothesize_score_sprt")
+        return c, s, [best[i].as_dict() for i in range(A)], [stats[i].as_dict() for i in range(A)], st
+
+    def run_sprt(self, model_or_params, seeds=None, polish=False):
+        """usac_multi_run_sprt: run() (model.sampler Uniform) or run_prosac() (Prosac) with SPRT verification
+        of every slot on the device (model.sprt set, no LO), one test per problem and round.  Returns run()'s
+        dicts plus "sprt" (epsilon, delta, A of the last test, tests designed, accepted, rejected,
+        points_tested); with PROSAC also run_prosac()'s keys; polish=True adds "polished" and "inliers"
+        as run() does."""
+        p = self._run_params(model_or_params)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != self.P:
+            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
+        out = (_MultiOutput * self.P)()
+        sp = (_MultiSprtOutput * self.P)()
+        pro = (_MultiProsacOutput * self.P)()
+        pol = (_MultiPolishOutput * self.P)() if polish else None
+        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if polish else None
+        self._check(lib().usac_multi_run_sprt(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, sp, pro, pol,
+                                              _ptr(mask, ctypes.c_uint8)), "multi_run_sprt")
+        res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
+                "bound": int(o.bound), "status": int(o.status), "sprt": q.as_dict()} for o, q in zip(out, sp)]
         if p.sampler == int(SAMPLER.Prosac):
             for r, q in zip(res, pro):
                 r.update(termination_length=int(q.termination_length), largest_sample_size=int(q.largest_sample_size),

@@ -421,8 +421,13 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
                                : (r.nullspace ? k_multi_solve_h4<true, false> : k_multi_solve_h4<false, false>);
         hipLaunchKernelGGL(solve, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R, r.first_hyp,
                            r.models, r.growth);
-        hipLaunchKernelGGL(k_multi_score_h, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.models, r.R, r.thr,
-                           r.counts, r.sums);
+        if (r.sprt) {
+            const hipError_t e = launch_multi_sprt_score(st, r);
+            if (e != hipSuccess) return e;
+        } else {
+            hipLaunchKernelGGL(k_multi_score_h, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.models, r.R, r.thr,
+                               r.counts, r.sums);
+        }
         hipLaunchKernelGGL(k_multi_argmax, dim3(r.A), dim3(256), 0, st, r.items, r.counts, r.sums, r.models, r.R, 9,
                            r.first_hyp, 1u, r.running, r.out);
     } else if (r.estimator == USAC_FUNDAMENTAL) {
@@ -431,8 +436,13 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
         auto *solve = r.growth ? k_multi_solve_f7<true> : k_multi_solve_f7<false>;
         hipLaunchKernelGGL(solve, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R, r.first_hyp,
                            r.models, r.counts, r.sums, r.list, r.list_n, r.growth);
-        hipLaunchKernelGGL(k_multi_score_f, dim3(3 * r.R / 64, r.A), dim3(64), 0, st, r.pts, r.offsets, r.items,
-                           r.models, r.R, r.list, r.list_n, r.thr, r.counts, r.sums);
+        if (r.sprt) {
+            e = launch_multi_sprt_score(st, r);
+            if (e != hipSuccess) return e;
+        } else {
+            hipLaunchKernelGGL(k_multi_score_f, dim3(3 * r.R / 64, r.A), dim3(64), 0, st, r.pts, r.offsets, r.items,
+                               r.models, r.R, r.list, r.list_n, r.thr, r.counts, r.sums);
+        }
         hipLaunchKernelGGL(k_multi_argmax, dim3(r.A), dim3(256), 0, st, r.items, r.counts, r.sums, r.models, 3 * r.R,
                            9, r.first_hyp, 3u, r.running, r.out);
     } else {

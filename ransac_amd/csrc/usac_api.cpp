@@ -3977,7 +3977,7 @@ void usac_lo_destroy(usac_lo *h) {
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- multi-problem batches (ABI 15 .. 18)
+// ---------------------------------------------------------------- multi-problem batches (ABI 15 .. 19)
 // P independent two-view problems in one context (kernels_multi.hip): the usac_hypothesize_score
 // round over (active problem, hypothesis tile), and a batch-granular RANSAC whose host loop only
 // reads the active problems' records once per round, evaluates the standard termination criterion
@@ -3986,7 +3986,10 @@ void usac_lo_destroy(usac_lo *h) {
 // with the PROSAC sampler in closed form (usac_prosac.hpp) and PROSAC's termination scan split between
 // k_multi_prosac_scan, which stores its candidates into pinned host memory, and
 // ProsacTerminationCriteria::applyCandidates.  ABI 18 (usac_multi_run_lo): either loop with k_multi_lo
-// (kernels_nonmin.hip) between the round's merge and the scan / the record copy.
+// (kernels_nonmin.hip) between the round's merge and the scan / the record copy.  ABI 19
+// (usac_multi_run_sprt): either loop with the round's score launch replaced by SPRT verification
+// (kernels_multi_sprt.hip), one test per problem and round, re-designed on the host between rounds
+// (usac::SprtRounds) from the statistics that come down with the records.
 
 struct usac_multi {
     int device = 0;
@@ -4010,6 +4013,14 @@ struct usac_multi {
     void *pro_pin = nullptr;  // (N_total / 2 + P) candidate pairs, then P numbers
     size_t pro_pin_bytes = 0;
     std::vector<std::unique_ptr<usac::ProsacTerminationCriteria>> pterm;
+    // SPRT (ABI 19): the pool-ordered copy of the points and its index (usac_multi_sprt_setup), per
+    // launch the active entries' tests (their statistics sit behind the records in `out`), the survivor
+    // list and its counter, the slots' starts (the hook only); pinned staging of the tests up and of
+    // the records and statistics down
+    DevBuf sprt_pts, sprt_idx, sprt_consts, sprt_surv, sprt_surv_n, sprt_starts;
+    bool sprt_ready = false, sprt_tail = false;
+    void *sprt_pin = nullptr;
+    size_t sprt_pin_bytes = 0;
     std::string err;
 };
 
@@ -4264,6 +4275,104 @@ int multi_lo_fetch(usac_multi *mc, usac_multi_lo_output *lo) {
     return USAC_OK;
 }
 
+// ---- SPRT for multi-problem batches (ABI 19)
+// the certificate's margin and climb limit with their test overrides, as usac_set_sprt reads them
+bool multi_sprt_cert(double &margin, double &climb) {
+    const char *em = getenv("USAC_SPRT_CERT_MARGIN"), *ec = getenv("USAC_SPRT_CERT_CLIMB");
+    margin = em ? atof(em) : 1e-7;
+    climb = ec ? atof(ec) : 700.0;
+    return margin >= 1e-7 && climb > 0 && climb <= 700.0;
+}
+
+// usac_set_sprt's constants of the test (eps, del, A) for a problem of n points: the reference's doubles,
+// their logs, and the certificate's margin raised to its error budget at this n
+usac::SprtConsts multi_sprt_consts(double eps, double del, double A, uint32_t n, double margin, double climb) {
+    usac::SprtConsts k{};
+    k.up = del / eps;
+    k.down = (1 - del) / (1 - eps);
+    k.A = A;
+    k.lu = log(k.up);
+    k.ld = log(k.down);
+    k.lA = log(k.A);
+    k.margin = margin;
+    k.climb = climb;
+    const double L = std::max(std::max(fabs(k.lu), fabs(k.ld)), 1.0);
+    const double nn = (double)n, per = std::ceil(std::max(nn - 64.0, 0.0) / 256.0) + 64.0;
+    const double budget = 2.0 * nn * L * 0x1p-51 + per * per * L * 0x1p-53 + fabs(k.lA) * 0x1p-53;
+    k.margin = std::max(k.margin, 8.0 * budget);
+    return k;
+}
+
+// the pools on the host, the pool-ordered copy of the points on the device (k_gather's rule)
+int multi_sprt_setup(usac_multi *mc, const uint32_t *pool_seeds) {
+    std::vector<uint32_t> idx(mc->n_total);
+    bool tail = false;
+    for (uint32_t p = 0; p < mc->P; p++) {
+        const uint32_t base = mc->offsets[p], n = mc->offsets[p + 1] - base;
+        usac::GlibcRandom g(pool_seeds ? pool_seeds[p] : p + 1);
+        const usac::Sprt sp(g, mc->estimator, n, mc->m, 10000);
+        const std::vector<uint32_t> &pool = sp.pool();
+        for (uint32_t i = 0; i < n; i++) idx[base + i] = base + pool[i];
+        tail = tail || n > 64;
+    }
+    mc->sprt_ready = false;
+    HIP_TRY(mc, mc->sprt_idx.reserve(sizeof(uint32_t) * (size_t)mc->n_total));
+    HIP_TRY(mc, mc->sprt_pts.reserve(sizeof(float) * 4 * (size_t)mc->n_total));
+    HIP_TRY(mc, mc->sprt_surv_n.reserve(sizeof(uint32_t)));
+    HIP_TRY(mc, hipMemcpyAsync(mc->sprt_idx.p, idx.data(), sizeof(uint32_t) * (size_t)mc->n_total, hipMemcpyHostToDevice,
+                               mc->stream));
+    HIP_TRY(mc, usac::launch_gather_points(mc->stream, mc->pts.p, 4, mc->sprt_idx.as<uint32_t>(), mc->n_total,
+                                           mc->sprt_pts.p));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    mc->sprt_ready = true;
+    mc->sprt_tail = tail;
+    return USAC_OK;
+}
+
+// The SPRT buffers of a launch of up to A entries x R hypotheses (after multi_ensure): the tests, the
+// survivor list, the starts if asked for; the statistics sit behind the records in mc->out, so that both
+// come down in one copy; pinned staging: A tests up, then A records and A statistics down.
+int multi_sprt_ensure(usac_multi *mc, uint32_t A, uint32_t R, bool starts) {
+    if (!mc->sprt_ready) {
+        const int rc = multi_sprt_setup(mc, nullptr);
+        if (rc) return rc;
+    }
+    const size_t S = (size_t)A * R * mc->spk;
+    HIP_TRY(mc, mc->sprt_consts.reserve(sizeof(usac::SprtConsts) * (size_t)A));
+    HIP_TRY(mc, mc->out.reserve((sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A));
+    HIP_TRY(mc, mc->sprt_surv.reserve(usac::multi_sprt_survivor_bytes() * S));
+    if (starts) HIP_TRY(mc, mc->sprt_starts.reserve(sizeof(uint32_t) * S));
+    const size_t need = (sizeof(usac::SprtConsts) + sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A;
+    if (need > mc->sprt_pin_bytes) {
+        if (mc->sprt_pin) PinnedPool::get().give_back(mc->sprt_pin, mc->sprt_pin_bytes);
+        mc->sprt_pin_bytes = 0;
+        mc->sprt_pin = PinnedPool::get().take(need, &mc->sprt_pin_bytes);
+        if (!mc->sprt_pin) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
+    }
+    return USAC_OK;
+}
+static_assert(sizeof(usac_record) % 8 == 0 && sizeof(usac::SprtConsts) % 8 == 0 && sizeof(usac_multi_sprt_stats) == 32,
+              "the records, then the statistics, 8-byte aligned");
+
+usac::SprtConsts *multi_sprt_consts_pin(usac_multi *mc) { return static_cast<usac::SprtConsts *>(mc->sprt_pin); }
+// the down area behind A_cap tests: the launch's A records, then its A statistics
+usac_record *multi_sprt_down_pin(usac_multi *mc, uint32_t A_cap) {
+    return reinterpret_cast<usac_record *>(multi_sprt_consts_pin(mc) + A_cap);
+}
+
+// a launch of A entries: the device statistics behind the A records of mc->out
+usac::MultiSprt multi_sprt_args(usac_multi *mc, uint32_t A, bool starts) {
+    usac::MultiSprt s{};
+    s.pool_pts = mc->sprt_pts.as<float4>();
+    s.consts = mc->sprt_consts.as<usac::SprtConsts>();
+    s.stats = reinterpret_cast<usac_multi_sprt_stats *>(mc->out.as<usac_record>() + A);
+    s.surv = mc->sprt_surv.p;
+    s.surv_n = mc->sprt_surv_n.as<uint32_t>();
+    s.starts = starts ? mc->sprt_starts.as<uint32_t>() : nullptr;
+    s.tail = mc->sprt_tail ? 1 : 0;
+    return s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4341,7 +4450,10 @@ void usac_multi_destroy(usac_multi *mc) {
     if (mc->pin) PinnedPool::get().give_back(mc->pin, mc->pin_bytes);
     if (mc->pol_pin) PinnedPool::get().give_back(mc->pol_pin, mc->pol_pin_bytes);
     if (mc->pro_pin) PinnedPool::get().give_back(mc->pro_pin, mc->pro_pin_bytes);
+    if (mc->sprt_pin) PinnedPool::get().give_back(mc->sprt_pin, mc->sprt_pin_bytes);
     for (DevBuf *b : {&mc->growth, &mc->non_random0, &mc->non_random}) b->release();
+    for (DevBuf *b : {&mc->sprt_pts, &mc->sprt_idx, &mc->sprt_consts, &mc->sprt_surv, &mc->sprt_surv_n, &mc->sprt_starts})
+        b->release();
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
                       &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
                       &mc->pol_out, &mc->lo_state})
@@ -4755,6 +4867,226 @@ int usac_multi_run_lo(usac_multi *mc, const usac_params *prm, const uint64_t *se
         A = keep;
     }
     if ((rc = multi_lo_fetch(mc, lo))) return rc;
+    if (!pol) return USAC_OK;
+    return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
+                               sizeof(usac_record) / sizeof(float), out[0].best.model,
+                               sizeof(usac_multi_output) / sizeof(float), prm->threshold, pol, mask);
+}
+
+// ---- SPRT (ABI 19)
+int usac_multi_sprt_update(int estimator, uint32_t n_points, uint32_t m, uint32_t max_iterations,
+                           usac_multi_sprt_test *hist, uint32_t *n_hist, uint32_t cap, uint32_t *last_update,
+                           uint32_t *bound, uint32_t done, uint32_t head_inliers, uint32_t head_points, int improved,
+                           uint32_t best_inliers, uint32_t term_bound) {
+    static_assert(USAC_HOMOGRAPHY == 2 && USAC_FUNDAMENTAL == 3, "usac_host.hpp's estimator numbers");
+    if (!hist || !n_hist || cap == 0 || *n_hist > cap) return USAC_ERR_ARG;
+    // the state as usac_host.hpp keeps it (sprt_rounds_update: the text the run applies), and back
+    std::vector<usac::Sprt::History> h(cap);
+    for (uint32_t i = 0; i < *n_hist; i++) h[i] = usac::Sprt::History{hist[i].epsilon, hist[i].delta, hist[i].A, hist[i].k};
+    uint32_t nh = *n_hist;
+    if (usac::sprt_rounds_update(estimator, n_points, m, max_iterations, h.data(), &nh, cap, last_update, bound, done,
+                                 head_inliers, head_points, improved != 0, best_inliers, term_bound))
+        return USAC_ERR_ARG;
+    for (uint32_t i = *n_hist; i < nh; i++) hist[i] = usac_multi_sprt_test{h[i].epsilon, h[i].delta, h[i].A, h[i].k, 0};
+    *n_hist = nh;
+    return USAC_OK;
+}
+
+int usac_multi_sprt_setup(usac_multi *mc, const uint32_t *pool_seeds) {
+    if (!mc) return USAC_ERR_ARG;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    return multi_sprt_setup(mc, pool_seeds);
+}
+
+int usac_multi_hypothesize_score_sprt(usac_multi *mc, const uint32_t *problems, uint32_t n_problems,
+                                      const int32_t *samples, uint32_t R, const uint64_t *seeds, uint64_t first_hyp,
+                                      float thr, int dlt_mode, const double *eps_delta, int32_t *counts, float *sums,
+                                      usac_record *best, usac_multi_sprt_stats *stats, uint32_t *starts) {
+    if (!mc) return USAC_ERR_ARG;
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
+    if (dlt_mode != USAC_DLT_THIN && dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    if (!problems && n_problems != 0 && n_problems != mc->P)
+        return fail(mc, USAC_ERR_ARG, "problems == NULL means all problems: n_problems must be P or 0");
+    const uint32_t A = problems ? n_problems : mc->P;
+    if (A == 0 || A > usac::kMultiMaxActive) return fail(mc, USAC_ERR_ARG, "n_problems out of range");
+    if (!samples && !seeds) return fail(mc, USAC_ERR_ARG, "seeds are required with the device sampler");
+    double margin, climb;
+    if (!multi_sprt_cert(margin, climb)) return fail(mc, USAC_ERR_ARG, "SPRT certificate: margin >= 1e-7 and 0 < climb <= 700");
+    for (uint32_t a = 0; a < A; a++) {
+        const uint32_t p = problems ? problems[a] : a;
+        if (p >= mc->P) return fail(mc, USAC_ERR_ARG, "problem index out of range");
+        if (eps_delta) {
+            const double e = eps_delta[2 * a], d = eps_delta[2 * a + 1];
+            if ((e != 0 && !(e > 0 && e < 1)) || (d != 0 && !(d > 0 && d < 1)))
+                return fail(mc, USAC_ERR_ARG, "SPRT: epsilon and delta must be in (0, 1)");
+        }
+        if (!samples) continue;
+        const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
+        const int32_t *s = samples + (size_t)a * R * mc->m;
+        for (size_t i = 0; i < (size_t)R * mc->m; i++)
+            if (s[i] < 0 || (uint32_t)s[i] >= n) return fail(mc, USAC_ERR_ARG, "sample index out of range");
+    }
+    // the tests, before any device call (delta < epsilon with the defaults filled in)
+    std::vector<usac::SprtConsts> kc(A);
+    for (uint32_t a = 0; a < A; a++) {
+        const uint32_t p = problems ? problems[a] : a, n = mc->offsets[p + 1] - mc->offsets[p];
+        const usac::SprtRounds st(mc->estimator, n, mc->m, 10000);
+        const double e = eps_delta && eps_delta[2 * a] != 0 ? eps_delta[2 * a] : st.test().epsilon;
+        const double d = eps_delta && eps_delta[2 * a + 1] != 0 ? eps_delta[2 * a + 1] : st.test().delta;
+        if (!(d < e)) return fail(mc, USAC_ERR_ARG, "SPRT: delta must be below epsilon");
+        kc[a] = multi_sprt_consts(e, d, st.thresholdA(e, d), n, margin, climb);
+    }
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    int rc = multi_ensure(mc, A, R, samples != nullptr);
+    if (rc || (rc = multi_sprt_ensure(mc, A, R, starts != nullptr))) return rc;
+    usac::MultiItem *items = multi_items_pin(mc);
+    for (uint32_t a = 0; a < A; a++) items[a] = usac::MultiItem{problems ? problems[a] : a, 0u, seeds ? seeds[a] : 0ull};
+    memcpy(multi_sprt_consts_pin(mc), kc.data(), sizeof(usac::SprtConsts) * (size_t)A);
+    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
+                               mc->stream));
+    HIP_TRY(mc, hipMemcpyAsync(mc->sprt_consts.p, multi_sprt_consts_pin(mc), sizeof(usac::SprtConsts) * (size_t)A,
+                               hipMemcpyHostToDevice, mc->stream));
+    const size_t G = (size_t)A * R, S = G * mc->spk;
+    if (samples)
+        HIP_TRY(mc, hipMemcpyAsync(mc->samples.p, samples, sizeof(int32_t) * G * mc->m, hipMemcpyHostToDevice,
+                                   mc->stream));
+    usac::MultiRound r = multi_round(mc, A, R, first_hyp, thr, dlt_mode);
+    r.samples_in = samples ? mc->samples.as<int32_t>() : nullptr;
+    const usac::MultiSprt ms = multi_sprt_args(mc, A, starts != nullptr);
+    r.sprt = &ms;
+    HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
+    if (counts) HIP_TRY(mc, hipMemcpyAsync(counts, mc->counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, mc->stream));
+    if (sums) HIP_TRY(mc, hipMemcpyAsync(sums, mc->sums.p, sizeof(float) * S, hipMemcpyDeviceToHost, mc->stream));
+    if (best)
+        HIP_TRY(mc, hipMemcpyAsync(best, mc->out.p, sizeof(usac_record) * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
+    if (stats)
+        HIP_TRY(mc, hipMemcpyAsync(stats, ms.stats, sizeof(usac_multi_sprt_stats) * (size_t)A, hipMemcpyDeviceToHost,
+                                   mc->stream));
+    if (starts) HIP_TRY(mc, hipMemcpyAsync(starts, mc->sprt_starts.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return USAC_OK;
+}
+
+int usac_multi_run_sprt(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
+                        usac_multi_sprt_output *sprt, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
+                        uint8_t *mask) {
+    if (!mc || !prm || !out) return USAC_ERR_ARG;
+    if (prm->lo != USAC_LO_NONE)
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run_sprt: no LO with SPRT (LO: usac_multi_run_lo)");
+    if (!prm->sprt) return fail(mc, USAC_ERR_ARG, "usac_multi_run_sprt: params->sprt must be set");
+    if (prm->sampler != USAC_SAMPLER_UNIFORM && prm->sampler != USAC_SAMPLER_PROSAC)
+        return fail(mc, USAC_ERR_ARG, "usac_multi_run_sprt: the uniform or the PROSAC sampler");
+    const bool prosac = prm->sampler == USAC_SAMPLER_PROSAC;
+    const uint32_t R = prm->batch ? prm->batch : 256u;
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
+    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    const uint32_t P = mc->P, m = mc->m;
+    if (prosac)
+        for (uint32_t p = 0; p < P; p++)
+            if (mc->offsets[p + 1] - mc->offsets[p] <= 20)
+                return fail(mc, USAC_ERR_ARG, "PROSAC needs > 20 points per problem (prosac_termination_criteria.hpp:158-163)");
+    double margin, climb;
+    if (!multi_sprt_cert(margin, climb)) return fail(mc, USAC_ERR_ARG, "SPRT certificate: margin >= 1e-7 and 0 < climb <= 700");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    int rc = multi_ensure(mc, P, R, false);
+    if (rc || (rc = multi_sprt_ensure(mc, P, R, false))) return rc;
+    if (prosac && ((rc = multi_prosac_ensure(mc)) || (rc = multi_prosac_reset(mc, prm)))) return rc;
+    HIP_TRY(mc, hipMemsetAsync(mc->running.p, 0, sizeof(usac_record) * (size_t)P, mc->stream));
+    usac::MultiItem *items = multi_items_pin(mc);
+    usac::SprtConsts *kc = multi_sprt_consts_pin(mc);
+    usac_record *recs = multi_sprt_down_pin(mc, P);
+    // PROSAC, per problem: the sampler's largest_sample_size, the last scan's bound, the scans
+    std::vector<uint32_t> largest(prosac ? P : 0, m), pbound(prosac ? P : 0, prm->max_iterations), scans(prosac ? P : 0, 0);
+    // SPRT, per problem: the test history and the bound, the run's totals
+    std::vector<usac::SprtRounds> tests;
+    tests.reserve(P);
+    std::vector<usac_multi_sprt_output> tot(P, usac_multi_sprt_output{});
+    for (uint32_t p = 0; p < P; p++) {
+        const uint64_t seed = seeds ? seeds[p] : (uint64_t)prm->seed + p;
+        const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
+        items[p] = prosac ? usac::MultiItem{p, 1u, seed, n, 0u} : usac::MultiItem{p, 0u, seed, 0u, 0u};
+        out[p] = usac_multi_output{};
+        tests.emplace_back(mc->estimator, n, m, prm->max_iterations);
+        tests.back().reserve_tests((size_t)prm->max_iterations / R + 2);  // at most one test per round
+    }
+    const usac::StandardTerminationCriteria term(prm->desired_prob, m, 0, prm->max_iterations);
+    uint32_t A = P;
+    for (uint32_t round = 0; A > 0; round++) {
+        const uint64_t first = (uint64_t)round * R, done = first + R;
+        for (uint32_t a = 0; a < A; a++) {  // every active problem's current test
+            const uint32_t p = items[a].problem;
+            const usac::Sprt::History &t = tests[p].test();
+            kc[a] = multi_sprt_consts(t.epsilon, t.delta, t.A, mc->offsets[p + 1] - mc->offsets[p], margin, climb);
+        }
+        HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
+                                   mc->stream));
+        HIP_TRY(mc, hipMemcpyAsync(mc->sprt_consts.p, kc, sizeof(usac::SprtConsts) * (size_t)A, hipMemcpyHostToDevice,
+                                   mc->stream));
+        usac::MultiRound r = multi_round(mc, A, R, first, prm->threshold, prm->dlt_mode);
+        r.running = mc->running.as<usac_record>();
+        if (prosac) r.growth = mc->growth.as<uint32_t>();
+        const usac::MultiSprt ms = multi_sprt_args(mc, A, false);
+        r.sprt = &ms;
+        HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
+        if (prosac) HIP_TRY(mc, multi_launch_scan(mc, A, first, prm->threshold));
+        // the A records and, behind them, the A statistics: one copy
+        HIP_TRY(mc, hipMemcpyAsync(recs, mc->out.p, (sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A,
+                                   hipMemcpyDeviceToHost, mc->stream));
+        HIP_TRY(mc, stream_wait(mc->stream));
+        const usac_multi_sprt_stats *stats = reinterpret_cast<const usac_multi_sprt_stats *>(recs + A);
+        uint32_t keep = 0;
+        for (uint32_t a = 0; a < A; a++) {
+            const usac::MultiItem it = items[a];
+            const uint32_t p = it.problem, n = mc->offsets[p + 1] - mc->offsets[p];
+            const bool improved = recs[a].valid && recs[a].hyp_index >= first;
+            uint32_t tb = 0, L = 0, T = 0;
+            if (prosac) {  // usac_multi_run_prosac's round end
+                const uint32_t *g = mc->growth_host[p]->data();
+                const uint32_t n_prosac = usac::prosac_round_lanes(g, n, it.clock, it.term_len, R);
+                L = it.term_len;
+                if (improved) {
+                    const uint32_t j = (uint32_t)(recs[a].hyp_index - first);
+                    const uint32_t at = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], j);
+                    pbound[p] = multi_apply_candidates(mc, a, p, (uint32_t)recs[a].hyp_index, at);
+                    L = mc->pterm[p]->terminationLength();
+                    scans[p]++;
+                }
+                largest[p] = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], R - 1);
+                T = it.clock + n_prosac;
+                tb = pbound[p];
+            } else if (improved) {
+                tb = term.getUpBoundIterations((uint32_t)recs[a].inliers, n);
+            }
+            usac_multi_sprt_output &so = tot[p];
+            so.accepted += stats[a].accepted;
+            so.rejected += stats[a].rejected_head + stats[a].rejected_tail;
+            so.points_tested += stats[a].points_tested;
+            tests[p].update((uint32_t)done, stats[a].head_inliers, stats[a].head_points, improved,
+                            (uint32_t)recs[a].inliers, tb);
+            const uint32_t bnd = tests[p].bound();
+            if (done >= std::min(prm->max_iterations, bnd)) {
+                usac_multi_output &o = out[p];
+                o.best = recs[a];
+                o.hypotheses = (uint32_t)done;
+                o.rounds = round + 1;
+                o.bound = bnd;
+                o.status = recs[a].inliers > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
+                if (prosac && pro) pro[p] = usac_multi_prosac_output{L, largest[p], T, scans[p]};
+            } else {
+                items[keep++] = prosac ? usac::MultiItem{p, T, it.seed, L, 0u} : it;
+            }
+        }
+        A = keep;
+    }
+    if (sprt)
+        for (uint32_t p = 0; p < P; p++) {
+            const usac::Sprt::History &t = tests[p].test();
+            tot[p].epsilon = t.epsilon;
+            tot[p].delta = t.delta;
+            tot[p].A = t.A;
+            tot[p].tests = (uint32_t)tests[p].histories();
+            sprt[p] = tot[p];
+        }
     if (!pol) return USAC_OK;
     return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
                                sizeof(usac_record) / sizeof(float), out[0].best.model,

@@ -11,6 +11,7 @@
 //   usac::ProsacSampler              prosac_sampler.hpp:62-172
 //   usac::ProsacTerminationCriteria  prosac_termination_criteria.hpp:44-201
 //   usac::Sprt                       sprt.hpp:89-491 (decisions on device inlier masks)
+//   usac::SprtRounds                 its test state advanced once per round (multi-problem batches)
 //   usac::GridNeighbors              nearest_neighbors.cpp:160-202
 //   usac::NapsacSampler              napsac_sampler.hpp:40-158 (grid), array_random_generator.hpp
 //   usac::NapsacKnnSampler           napsac_sampler.hpp:76-98 (KNN rows from usac_knn)
@@ -529,14 +530,13 @@ class Sprt {
         : pool_(points_size), n_(points_size), m_(sample_size), max_iters_(max_iterations),
           max_before_(max_hypothesis_test_before_sprt), rng_(&rng) {
         if (!defer_pool) shuffle_pool();
-        double eps0, delta0;
-        switch (estimator) {
-            case 2: delta0 = 0.01; eps0 = 0.1; t_M_ = 200; m_S_ = 1; break;        // homography
-            case 3: delta0 = 0.05; eps0 = 0.2; t_M_ = 200; m_S_ = 2.48; break;     // fundamental
-            case 4: delta0 = 0.05; eps0 = 0.2; t_M_ = 300; m_S_ = 4; break;        // essential
-            default: delta0 = 0.0001; eps0 = 0.001; t_M_ = 100; m_S_ = 1; break;   // line2d
-        }
-        hist_.push_back(History{eps0, delta0, thresholdA(eps0, delta0), 0});
+        first_test(estimator);
+    }
+    // the test state alone, without a pool (SprtRounds: the pools of a multi-problem batch live on the device)
+    struct NoPool {};
+    Sprt(NoPool, int estimator, uint32_t points_size, uint32_t sample_size, uint32_t max_iterations)
+        : n_(points_size), m_(sample_size), max_iters_(max_iterations), max_before_(0), rng_(nullptr) {
+        first_test(estimator);
     }
     void shuffle_pool() {
         if (!rng_) return;
@@ -712,7 +712,18 @@ class Sprt {
         return An;
     }
 
-   private:
+   protected:
+    // the constructor's test (sprt.hpp:114-170): the estimator's (epsilon, delta, t_M, m_S), A_0, k = 0
+    void first_test(int estimator) {
+        double eps0, delta0;
+        switch (estimator) {
+            case 2: delta0 = 0.01; eps0 = 0.1; t_M_ = 200; m_S_ = 1; break;        // homography
+            case 3: delta0 = 0.05; eps0 = 0.2; t_M_ = 200; m_S_ = 2.48; break;     // fundamental
+            case 4: delta0 = 0.05; eps0 = 0.2; t_M_ = 300; m_S_ = 4; break;        // essential
+            default: delta0 = 0.0001; eps0 = 0.001; t_M_ = 100; m_S_ = 1; break;   // line2d
+        }
+        hist_.push_back(History{eps0, delta0, thresholdA(eps0, delta0), 0});
+    }
     // pool position of the last of r >= 1 positions walked from p (< n_), wrapping at n_
     uint32_t last_of(uint32_t p, uint32_t r) const {
         const uint64_t q = (uint64_t)p + r - 1;
@@ -792,6 +803,91 @@ class Sprt {
     bool plain_ = getenv("USAC_SPRT_PLAIN_WALK") != nullptr;
     GlibcRandom *rng_;  // set until the pool is shuffled
 };
+
+// The SPRT state of one problem of a multi-problem batch (usac_multi_run_sprt): the test is fixed for a
+// round of R hypotheses and re-designed at most once between rounds, from the round's device statistics.
+// After a round that ends at `done` hypotheses, with the current test (epsilon, delta):
+//   1. head_points > 0: delta^ = (float)head_inliers / (float)head_points -- the reference's
+//      (float) tested_inliers / tested_point over the round's head-rejected models instead of one model;
+//      new_delta = delta^ > 0 && fabs(delta - delta^) / delta > 0.05 (sprt.hpp:298);
+//   2. new_epsilon = the running record improved in the round; epsilon^ = (double)((float)inliers /
+//      (float)n) (sprt.hpp:270);
+//   3. with epsilon' / delta' the new values where set: if either is, and 0 < delta' < epsilon' < 1,
+//      push {epsilon', delta', estimateThresholdA, k = done - last_update}, last_update = done (k sits on
+//      the new entry, as push() stores it, so getUpperBoundIterations is used unchanged).  The guard is a
+//      deviation: the reference would design a test with epsilon = 1 or delta >= epsilon;
+//   4. in a round that improved the record: bound = min(T, getUpperBoundIterations(inliers)), T the
+//      caller's termination bound for that count (ransac.cpp:126-132); otherwise the bound keeps its
+//      value (max_iterations at the start).
+class SprtRounds : public Sprt {
+   public:
+    SprtRounds(int estimator, uint32_t n, uint32_t m, uint32_t max_iterations)
+        : Sprt(NoPool{}, estimator, n, m, max_iterations), bound_(max_iterations) {}
+    // a state taken up where an earlier update left it: the history (>= 1 entries), last_update, the bound
+    SprtRounds(int estimator, uint32_t n, uint32_t m, uint32_t max_iterations, const History *hist, uint32_t n_hist,
+               uint32_t last_update, uint32_t bound)
+        : Sprt(NoPool{}, estimator, n, m, max_iterations), bound_(bound) {
+        hist_.assign(hist, hist + n_hist);
+        cur_ = n_hist - 1;
+        last_update_ = (int)last_update;
+    }
+    void reserve_tests(size_t tests) { hist_.reserve(tests); }  // so that update() does not allocate
+    const History &test() const { return hist_[cur_]; }
+    uint32_t last_update() const { return (uint32_t)last_update_; }
+    uint32_t bound() const { return bound_; }
+    // true: a new test was designed
+    bool update(uint32_t done, uint32_t head_inliers, uint32_t head_points, bool improved, uint32_t best_inliers,
+                uint32_t term_bound) {
+        const double epsilon = hist_[cur_].epsilon, delta = hist_[cur_].delta;
+        double eps_new = epsilon, delta_new = delta;
+        bool new_delta = false;
+        if (head_points > 0) {
+            const float dest = (float)head_inliers / (float)head_points;
+            new_delta = dest > 0 && std::fabs(delta - dest) / delta > 0.05;
+            if (new_delta) delta_new = dest;
+        }
+        if (improved) eps_new = (double)((float)best_inliers / (float)n_);
+        bool designed = false;
+        if ((improved || new_delta) && 0 < delta_new && delta_new < eps_new && eps_new < 1) {
+            push(eps_new, delta_new, (int)done);
+            designed = true;
+        }
+        if (improved) bound_ = std::min(term_bound, getUpperBoundIterations((int)best_inliers));
+        return designed;
+    }
+
+   private:
+    uint32_t bound_;
+};
+
+// usac_multi_sprt_update (include/usac_gpu.h) on a plain state: hist[0 .. *n_hist) of capacity cap,
+// *last_update, *bound.  *n_hist == 0 initialises the state first; done == 0 then returns.  0, or -1 for
+// an argument error (the state is then unchanged).
+inline int sprt_rounds_update(int estimator, uint32_t n, uint32_t m, uint32_t max_iterations, Sprt::History *hist,
+                              uint32_t *n_hist, uint32_t cap, uint32_t *last_update, uint32_t *bound, uint32_t done,
+                              uint32_t head_inliers, uint32_t head_points, bool improved, uint32_t best_inliers,
+                              uint32_t term_bound) {
+    if (!hist || !n_hist || !last_update || !bound || cap == 0 || *n_hist > cap || m == 0 || n < m ||
+        (estimator != 2 && estimator != 3))
+        return -1;
+    if (*n_hist == 0) {
+        const SprtRounds fresh(estimator, n, m, max_iterations);
+        hist[0] = fresh.test();
+        *n_hist = 1;
+        *last_update = 0;
+        *bound = max_iterations;
+    }
+    if (done == 0) return 0;
+    SprtRounds st(estimator, n, m, max_iterations, hist, *n_hist, *last_update, *bound);
+    if (st.update(done, head_inliers, head_points, improved, best_inliers, term_bound)) {
+        if (*n_hist == cap) return -1;
+        hist[*n_hist] = st.test();
+        ++*n_hist;
+    }
+    *last_update = st.last_update();
+    *bound = st.bound();
+    return 0;
+}
 
 // ---------------------------------------------------------------- NAPSAC (grid)
 // Grid neighbours: cell = ((int)(x1/cs), (int)(y1/cs), (int)(x2/cs), (int)(y2/cs)) with fp32

@@ -359,8 +359,27 @@ struct MultiRound {
     usac_record *out;           // [A]: the merged record (running given) or the round's record
     const uint32_t *growth;     // nullable: the PROSAC sampler (items' clock / term_len) over the growth
                                 // functions, n_total values, problem p's at growth + offsets[p]
+    const struct MultiSprt *sprt;  // nullable: SPRT verification (kernels_multi_sprt.hip) in place of the score launch
 };
 hipError_t launch_multi_round(hipStream_t st, const MultiRound &r);
+// SPRT verification of a round's slots (kernels_multi_sprt.hip): the throughput SPRT of launch_score_sprt
+// with one test per active entry.  pool_pts: N_total float4, problem p's slice in its pool's order;
+// consts: [A], entry a's test; stats: [A], zeroed by the launcher; surv: A * spk * R *
+// multi_sprt_survivor_bytes() of scratch, surv_n: one uint32 (zeroed by the launcher); starts (nullable):
+// [A * spk * R], each slot's first pool position, UINT32_MAX on an empty F slot; tail: some active
+// problem has more than 64 points (the tail kernel is launched).  counts / sums: a rejected slot reads
+// (-1, 0), an accepted one (inliers over all n_p points, (float)inliers).
+struct MultiSprt {
+    const float4 *pool_pts;
+    const SprtConsts *consts;
+    usac_multi_sprt_stats *stats;
+    void *surv;
+    uint32_t *surv_n;
+    uint32_t *starts;
+    int tail;
+};
+hipError_t launch_multi_sprt_score(hipStream_t st, const MultiRound &r);
+size_t multi_sprt_survivor_bytes();
 // the samples launch_multi_round's solve kernels draw (same device function), out: A x R x m local
 // indices; growth == nullptr: the uniform sampler
 hipError_t launch_multi_draw(hipStream_t st, int estimator, const uint32_t *offsets, const MultiItem *items, uint32_t A,

@@ -30,6 +30,12 @@ LO-RANSAC of every round's new bests on the device) is alternated with MultiCont
 --sampler prosac, with MultiContext.run_prosac -- on the same inputs; with --polish both include the
 polish.  Reported for both: the --sampler prosac mode's figures; for the LO run also the mean LO calls,
 fits, improvements and capped calls per pair.  No loop over single contexts in this mode.
+
+--sprt compares the SPRT run with the run without it: MultiContext.run_sprt is alternated with
+MultiContext.run -- or, with --sampler prosac, with MultiContext.run_prosac -- on the same inputs; with
+--polish both include the polish.  Reported for both: rounds, hypotheses, mean best inliers; for the SPRT
+run also the point tests done over slots x n_p, the tests designed per pair and the accepted / rejected
+slots; and, separately, the one-time cost of set_sprt_pool, which is not part of a run.
 """
 import argparse
 import ctypes
@@ -294,6 +300,71 @@ def main_lo(a, mc, model, est):
     return 0
 
 
+def main_sprt(a, mc, model, est):
+    """--sprt: MultiContext.run_sprt against the same run without SPRT (run, or run_prosac with --sampler
+    prosac) on the same inputs, alternated, host-timed, medians and spreads as in main().  The pools and the
+    pool-ordered copy (set_sprt_pool: one host shuffle per pair plus the gather) are built once, outside
+    the runs, and timed separately."""
+    prosac = a.sampler == "prosac"
+    base = usac.Model(model.threshold, mc.m, model.desired_prob, 5, est,
+                      usac.SAMPLER.Prosac if prosac else usac.SAMPLER.Uniform)
+    base.max_iterations, base.batch, base.seed = model.max_iterations, model.batch, model.seed
+    base.setDLTMode(model.dlt_mode)
+    smodel = usac.Model(model.threshold, mc.m, model.desired_prob, 5, est, base.sampler)
+    smodel.max_iterations, smodel.batch, smodel.seed = model.max_iterations, model.batch, model.seed
+    smodel.setDLTMode(model.dlt_mode)
+    smodel.setSprt(True)
+    run_base = mc.run_prosac if prosac else mc.run
+
+    def summary(res, ms):
+        rounds = [r["rounds"] for r in res]
+        d = {"ms": round(statistics.median(ms), 3), "spread_ms": round(max(ms) - min(ms), 3),
+             "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
+             "mean_rounds": round(float(np.mean(rounds)), 2), "launch_rounds": int(max(rounds)),
+             "hypotheses": int(sum(r["hypotheses"] for r in res)),
+             "mean_best_inliers": round(float(np.mean([r["best"]["inliers"] for r in res])), 2)}
+        if a.polish:
+            d["mean_polished_inliers"] = round(float(np.mean([r["polished"]["inliers"] for r in res])), 2)
+        return d
+
+    t0 = time.perf_counter()
+    mc.set_sprt_pool()
+    setup_ms = (time.perf_counter() - t0) * 1e3
+    for _ in range(a.warmup):
+        rs, rb = mc.run_sprt(smodel, polish=a.polish), run_base(base, polish=a.polish)
+    ts, tb = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        rs = mc.run_sprt(smodel, polish=a.polish)
+        t1 = time.perf_counter()
+        rb = run_base(base, polish=a.polish)
+        t2 = time.perf_counter()
+        ts.append((t1 - t0) * 1e3)
+        tb.append((t2 - t1) * 1e3)
+    line = {"bench": "multi_sprt", "sampler": a.sampler, "estimator": a.estimator, "pairs": a.pairs,
+            "points": a.points, "round": a.R, "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio,
+            "dlt": a.dlt, "reps": a.reps, "polish": bool(a.polish), "set_sprt_pool_ms": round(setup_ms, 3),
+            "with_sprt": summary(rs, ts), "without_sprt": summary(rb, tb)}
+    # slots x n_p of the SPRT run: every hypothesis slot (F: 3 per hypothesis, empty ones included)
+    slots_points = sum(r["hypotheses"] * mc.spk * int(n) for r, n in zip(rs, mc.sizes))
+    w = line["with_sprt"]
+    w["points_tested_share"] = round(sum(r["sprt"]["points_tested"] for r in rs) / slots_points, 5)
+    w["mean_tests_designed"] = round(float(np.mean([r["sprt"]["tests"] for r in rs])), 2)
+    w["accepted"] = int(sum(r["sprt"]["accepted"] for r in rs))
+    w["rejected"] = int(sum(r["sprt"]["rejected"] for r in rs))
+    line["ratio_sprt_over_without"] = round(w["ms"] / line["without_sprt"]["ms"], 2)
+    line["differs_beyond_spread"] = bool(abs(line["without_sprt"]["ms"] - w["ms"]) >
+                                         max(w["spread_ms"], line["without_sprt"]["spread_ms"]))
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    mc.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=512)
@@ -314,9 +385,14 @@ def main():
     ap.add_argument("--lo", choices=["lorsc", "florsc"], default=None,
                     help="MultiContext.run_lo (inner + iterative LO-RANSAC, unlimited / limited) against the same "
                          "run without LO; with --sampler prosac both use the PROSAC sampler")
+    ap.add_argument("--sprt", action="store_true",
+                    help="MultiContext.run_sprt (SPRT verification of every slot, one test per pair and round) against "
+                         "the same run without SPRT; with --sampler prosac both use the PROSAC sampler")
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
+    if a.sprt and a.lo:
+        ap.error("--sprt and --lo do not combine (usac_multi_run_sprt runs without LO)")
 
     est = usac.ESTIMATOR.Homography if a.estimator == "homography" else usac.ESTIMATOR.Fundamental
     thr, prob = 2.0, 0.95
@@ -327,6 +403,8 @@ def main():
     seeds = [model.seed + p for p in range(a.pairs)]
 
     mc = usac.MultiContext(est, sets)
+    if a.sprt:
+        return main_sprt(a, mc, model, est)
     if a.lo:
         return main_lo(a, mc, model, est)
     if a.sampler == "prosac":
