@@ -859,6 +859,48 @@ class MultiContext:
                 r["inlier_idx"] = idx
         return res
 
+    def _run_params(self, model_or_params):
+        if isinstance(model_or_params, _Params):
+            return model_or_params
+        p = _params(model_or_params)
+        p.seed = model_or_params.seed  # the default seeds are seed + p, never a random one
+        return p
+
+    def _run(self, name, model_or_params, seeds, polish, own=None, prosac=None):
+        """What the run methods share: usac_multi_<name>(handle, params, seeds, out[, own's array]
+        [, PROSAC's array][, polish results, mask]) and its list of P result dicts.  own: (key,
+        structure) of the method's own per-problem output.  prosac: the call takes PROSAC's array, and
+        its keys are returned "always" or under the PROSAC "sampler" only.  The polish arguments go to
+        every function but usac_multi_run."""
+        p = self._run_params(model_or_params)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != self.P:
+            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
+        out = (_MultiOutput * self.P)()
+        ex = (own[1] * self.P)() if own else None
+        pro = (_MultiProsacOutput * self.P)() if prosac else None
+        pol = (_MultiPolishOutput * self.P)() if polish else None
+        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if polish else None
+        args = [a for a in (ex, pro) if a is not None]
+        if name != "run":
+            args += [pol, _ptr(mask, ctypes.c_uint8)]
+        self._check(getattr(lib(), "usac_multi_" + name)(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, *args),
+                    "multi_" + name)
+        res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
+                "bound": int(o.bound), "status": int(o.status)} for o in out]
+        if own:
+            for r, q in zip(res, ex):
+                r[own[0]] = q.as_dict()
+        if prosac == "always" or (prosac and p.sampler == int(SAMPLER.Prosac)):
+            for r, q in zip(res, pro):
+                r.update(termination_length=int(q.termination_length), largest_sample_size=int(q.largest_sample_size),
+                         clock=int(q.clock), scans=int(q.scans))
+        if polish:
+            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
+                r["polished"] = po
+                r["inliers"] = idx
+        return res
+
     def run(self, model_or_params, seeds=None, polish=False):
         """usac_multi_run: batch-granular RANSAC with the standard termination criterion over all
         problems (uniform device sampler; no SPRT; LO: run_lo).  model_or_params: a Model or a
@@ -867,29 +909,7 @@ class MultiContext:
         adds the non-minimal polish of every best model at the run's threshold: each dict gains
         "polished" (polish()'s dict) and "inliers" (the polished model's inliers, ascending local
         indices)."""
-        if isinstance(model_or_params, _Params):
-            p = model_or_params
-        else:
-            p = _params(model_or_params)
-            p.seed = model_or_params.seed  # the default seeds are seed + p, never a random one
-        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
-        if sd is not None and sd.size != self.P:
-            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
-        out = (_MultiOutput * self.P)()
-        if polish:
-            pol = (_MultiPolishOutput * self.P)()
-            mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8)
-            self._check(lib().usac_multi_run_polished(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, pol,
-                                                      _ptr(mask, ctypes.c_uint8)), "multi_run_polished")
-        else:
-            self._check(lib().usac_multi_run(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out), "multi_run")
-        res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
-                "bound": int(o.bound), "status": int(o.status)} for o in out]
-        if polish:
-            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
-                r["polished"] = po
-                r["inliers"] = idx
-        return res
+        return self._run("run_polished" if polish else "run", model_or_params, seeds, polish)
 
     def draw_samples(self, R, seeds, first_hyp=0, problems=None, clock=None, term_len=None):
         """usac_multi_draw_samples (for tests): the samples a round's solve kernels draw, A x R x m local
@@ -913,37 +933,12 @@ class MultiContext:
                                                   _ptr(out, ctypes.c_int32)), "multi_draw_samples")
         return out
 
-    def _run_params(self, model_or_params):
-        if isinstance(model_or_params, _Params):
-            return model_or_params
-        p = _params(model_or_params)
-        p.seed = model_or_params.seed  # the default seeds are seed + p, never a random one
-        return p
-
     def run_prosac(self, model_or_params, seeds=None, polish=False):
         """usac_multi_run_prosac: run() with the PROSAC sampler and PROSAC's termination criterion per
         problem; every point set sorted by descending quality.  Returns run()'s dicts plus
         termination_length, largest_sample_size, clock (the sampler's hypCount at the end) and scans;
         polish=True adds "polished" and "inliers" as run() does."""
-        p = self._run_params(model_or_params)
-        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
-        if sd is not None and sd.size != self.P:
-            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
-        out = (_MultiOutput * self.P)()
-        pro = (_MultiProsacOutput * self.P)()
-        pol = (_MultiPolishOutput * self.P)() if polish else None
-        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if polish else None
-        self._check(lib().usac_multi_run_prosac(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, pro, pol,
-                                                _ptr(mask, ctypes.c_uint8)), "multi_run_prosac")
-        res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
-                "bound": int(o.bound), "status": int(o.status), "termination_length": int(q.termination_length),
-                "largest_sample_size": int(q.largest_sample_size), "clock": int(q.clock), "scans": int(q.scans)}
-               for o, q in zip(out, pro)]
-        if polish:
-            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
-                r["polished"] = po
-                r["inliers"] = idx
-        return res
+        return self._run("run_prosac", model_or_params, seeds, polish, prosac="always")
 
     def prosac_scan(self, model_or_params, models, hyp_count, largest, reset=False):
         """usac_multi_prosac_scan (for tests): one PROSAC termination scan of every problem with models
@@ -995,28 +990,7 @@ class MultiContext:
         round's new bests on the device (model.lo = InItLORsc / InItFLORsc).  Returns run()'s dicts plus
         "lo" (the problem's LO counters and threshold); with PROSAC also run_prosac()'s keys; polish=True
         adds "polished" and "inliers" as run() does."""
-        p = self._run_params(model_or_params)
-        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
-        if sd is not None and sd.size != self.P:
-            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
-        out = (_MultiOutput * self.P)()
-        lo = (_MultiLoOutput * self.P)()
-        pro = (_MultiProsacOutput * self.P)()
-        pol = (_MultiPolishOutput * self.P)() if polish else None
-        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if polish else None
-        self._check(lib().usac_multi_run_lo(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, lo, pro, pol,
-                                            _ptr(mask, ctypes.c_uint8)), "multi_run_lo")
-        res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
-                "bound": int(o.bound), "status": int(o.status), "lo": q.as_dict()} for o, q in zip(out, lo)]
-        if p.sampler == int(SAMPLER.Prosac):
-            for r, q in zip(res, pro):
-                r.update(termination_length=int(q.termination_length), largest_sample_size=int(q.largest_sample_size),
-                         clock=int(q.clock), scans=int(q.scans))
-        if polish:
-            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
-                r["polished"] = po
-                r["inliers"] = idx
-        return res
+        return self._run("run_lo", model_or_params, seeds, polish, own=("lo", _MultiLoOutput), prosac="sampler")
 
     def set_sprt_pool(self, seeds=None):
         """usac_multi_sprt_setup: the problems' SPRT pools (the reference's shuffle after srandom(seeds[p]),
@@ -1066,28 +1040,7 @@ class MultiContext:
         dicts plus "sprt" (epsilon, delta, A of the last test, tests designed, accepted, rejected,
         points_tested); with PROSAC also run_prosac()'s keys; polish=True adds "polished" and "inliers"
         as run() does."""
-        p = self._run_params(model_or_params)
-        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
-        if sd is not None and sd.size != self.P:
-            raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
-        out = (_MultiOutput * self.P)()
-        sp = (_MultiSprtOutput * self.P)()
-        pro = (_MultiProsacOutput * self.P)()
-        pol = (_MultiPolishOutput * self.P)() if polish else None
-        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if polish else None
-        self._check(lib().usac_multi_run_sprt(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, sp, pro, pol,
-                                              _ptr(mask, ctypes.c_uint8)), "multi_run_sprt")
-        res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
-                "bound": int(o.bound), "status": int(o.status), "sprt": q.as_dict()} for o, q in zip(out, sp)]
-        if p.sampler == int(SAMPLER.Prosac):
-            for r, q in zip(res, pro):
-                r.update(termination_length=int(q.termination_length), largest_sample_size=int(q.largest_sample_size),
-                         clock=int(q.clock), scans=int(q.scans))
-        if polish:
-            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
-                r["polished"] = po
-                r["inliers"] = idx
-        return res
+        return self._run("run_sprt", model_or_params, seeds, polish, own=("sprt", _MultiSprtOutput), prosac="sampler")
 
     def inliers(self, models, thr):
         """Ascending inlier indices (local to each problem) of each problem's model (P x 9), by the

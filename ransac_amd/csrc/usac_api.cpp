@@ -3982,14 +3982,22 @@ void usac_lo_destroy(usac_lo *h) {
 // round over (active problem, hypothesis tile), and a batch-granular RANSAC whose host loop only
 // reads the active problems' records once per round, evaluates the standard termination criterion
 // and uploads the compacted active list.  One stream; every buffer is sized once per call, for
-// (active problems) x R, none inside the round loop.  ABI 17 (usac_multi_run_prosac): the same loop
-// with the PROSAC sampler in closed form (usac_prosac.hpp) and PROSAC's termination scan split between
-// k_multi_prosac_scan, which stores its candidates into pinned host memory, and
-// ProsacTerminationCriteria::applyCandidates.  ABI 18 (usac_multi_run_lo): either loop with k_multi_lo
-// (kernels_nonmin.hip) between the round's merge and the scan / the record copy.  ABI 19
-// (usac_multi_run_sprt): either loop with the round's score launch replaced by SPRT verification
-// (kernels_multi_sprt.hip), one test per problem and round, re-designed on the host between rounds
-// (usac::SprtRounds) from the statistics that come down with the records.
+// (active problems) x R, none inside the round loop.  There is one such loop, multi_run_driver, with
+// three options read from the params; usac_multi_run, _run_polished, _run_prosac, _run_lo and _run_sprt
+// check their arguments and call it:
+//   PROSAC (ABI 17): the PROSAC sampler in closed form (usac_prosac.hpp) and PROSAC's termination scan,
+//     split between k_multi_prosac_scan, which stores its candidates into pinned host memory, and
+//     ProsacTerminationCriteria::applyCandidates;
+//   LO (ABI 18): k_multi_lo (kernels_nonmin.hip) between the round's merge and the scan / the record copy;
+//   SPRT (ABI 19): the round's score launch replaced by SPRT verification (kernels_multi_sprt.hip), one
+//     test per problem and round, re-designed on the host between rounds (usac::SprtRounds) from the
+//     statistics that come down with the records.  LO and SPRT do not combine.
+
+// a pinned staging block (PinnedPool) that only grows
+struct PinBlock {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
 
 struct usac_multi {
     int device = 0;
@@ -4001,17 +4009,14 @@ struct usac_multi {
     DevBuf pol_lists, pol_out;  // the polish: two inlier lists per problem (2 x N_total), P results
     DevBuf lo_state;            // LO (ABI 18): per problem the threshold, the draw counter, the counters
     bool lo_state_set = false;  // usac_multi_lo: the state of an earlier call is there to continue
-    void *pin = nullptr;  // pinned staging: the active list up, the records down
-    size_t pin_bytes = 0;
-    void *pol_pin = nullptr;  // pinned staging of the polish: P results and the mask down
-    size_t pol_pin_bytes = 0;
+    PinBlock pin;               // pinned staging: the active list up, the records down
+    PinBlock pol_pin;           // pinned staging of the polish: P results and the mask down
     // PROSAC (built at the first PROSAC call): the problems' growth functions and pristine non-random
     // minima (N_total values each, the points' offsets), the working copy the scan kernel raises, the
     // pinned block it stores candidates and their numbers into, and the per-problem host halves
     DevBuf growth, non_random0, non_random;
     std::vector<std::shared_ptr<const std::vector<uint32_t>>> growth_host;  // per problem, shared by shape
-    void *pro_pin = nullptr;  // (N_total / 2 + P) candidate pairs, then P numbers
-    size_t pro_pin_bytes = 0;
+    PinBlock pro_pin;  // (N_total / 2 + P) candidate pairs, then P numbers
     std::vector<std::unique_ptr<usac::ProsacTerminationCriteria>> pterm;
     // SPRT (ABI 19): the pool-ordered copy of the points and its index (usac_multi_sprt_setup), per
     // launch the active entries' tests (their statistics sit behind the records in `out`), the survivor
@@ -4019,8 +4024,7 @@ struct usac_multi {
     // the records and statistics down
     DevBuf sprt_pts, sprt_idx, sprt_consts, sprt_surv, sprt_surv_n, sprt_starts;
     bool sprt_ready = false, sprt_tail = false;
-    void *sprt_pin = nullptr;
-    size_t sprt_pin_bytes = 0;
+    PinBlock sprt_pin;
     std::string err;
 };
 
@@ -4029,6 +4033,16 @@ namespace {
 int fail(usac_multi *mc, int code, const std::string &msg) {
     if (mc) mc->err = msg;
     return code;
+}
+
+// at least `need` bytes in a pinned block; growing it moves it, so its users take the pointer afterwards
+int pin_grow(usac_multi *mc, PinBlock &b, size_t need) {
+    if (need <= b.bytes) return USAC_OK;
+    if (b.p) PinnedPool::get().give_back(b.p, b.bytes);
+    b.bytes = 0;
+    b.p = PinnedPool::get().take(need, &b.bytes);
+    if (!b.p) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
+    return USAC_OK;
 }
 
 bool multi_round_ok(uint32_t R) { return R >= 64 && R <= 8192 && R % 64 == 0; }
@@ -4046,17 +4060,10 @@ int multi_ensure(usac_multi *mc, uint32_t A, uint32_t R, bool host_samples) {
         HIP_TRY(mc, mc->list.reserve(sizeof(uint32_t) * S));
         HIP_TRY(mc, mc->list_n.reserve(sizeof(uint32_t) * (size_t)A));
     }
-    const size_t need = (sizeof(usac::MultiItem) + sizeof(usac_record)) * (size_t)A;
-    if (need > mc->pin_bytes) {
-        if (mc->pin) PinnedPool::get().give_back(mc->pin, mc->pin_bytes);
-        mc->pin_bytes = 0;
-        mc->pin = PinnedPool::get().take(need, &mc->pin_bytes);
-        if (!mc->pin) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
-    }
-    return USAC_OK;
+    return pin_grow(mc, mc->pin, (sizeof(usac::MultiItem) + sizeof(usac_record)) * (size_t)A);
 }
 
-usac::MultiItem *multi_items_pin(usac_multi *mc) { return static_cast<usac::MultiItem *>(mc->pin); }
+usac::MultiItem *multi_items_pin(usac_multi *mc) { return static_cast<usac::MultiItem *>(mc->pin.p); }
 usac_record *multi_records_pin(usac_multi *mc, uint32_t A_cap) {
     return reinterpret_cast<usac_record *>(multi_items_pin(mc) + A_cap);
 }
@@ -4143,13 +4150,9 @@ int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, c
                                           mask ? mc->mask.as<uint8_t>() : nullptr));
     // results and mask come down through pinned staging, then into the caller's (pageable) buffers
     const size_t out_bytes = sizeof(usac_multi_polish_output) * (size_t)P, need = out_bytes + (mask ? mc->n_total : 0);
-    if (need > mc->pol_pin_bytes) {
-        if (mc->pol_pin) PinnedPool::get().give_back(mc->pol_pin, mc->pol_pin_bytes);
-        mc->pol_pin_bytes = 0;
-        mc->pol_pin = PinnedPool::get().take(need, &mc->pol_pin_bytes);
-        if (!mc->pol_pin) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
-    }
-    uint8_t *stage = static_cast<uint8_t *>(mc->pol_pin);
+    int rc = pin_grow(mc, mc->pol_pin, need);
+    if (rc) return rc;
+    uint8_t *stage = static_cast<uint8_t *>(mc->pol_pin.p);
     HIP_TRY(mc, hipMemcpyAsync(stage, mc->pol_out.p, out_bytes, hipMemcpyDeviceToHost, mc->stream));
     if (mask) HIP_TRY(mc, hipMemcpyAsync(stage + out_bytes, mc->mask.p, mc->n_total, hipMemcpyDeviceToHost, mc->stream));
     HIP_TRY(mc, stream_wait(mc->stream));
@@ -4157,15 +4160,14 @@ int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, c
     if (mask) memcpy(mask, stage + out_bytes, mc->n_total);
     for (uint32_t p = 0; p < P; p++) {
         if (out[p].status != usac::kMultiPolishDefer) continue;
-        const int rc = multi_polish_single(mc, p, hstart + (size_t)p * hstride, thr, out + p,
-                                           mask ? mask + mc->offsets[p] : nullptr);
+        rc = multi_polish_single(mc, p, hstart + (size_t)p * hstride, thr, out + p, mask ? mask + mc->offsets[p] : nullptr);
         if (rc) return rc;
     }
     return USAC_OK;
 }
 
 // ---- PROSAC for multi-problem batches (ABI 17)
-uint32_t *multi_cand_pin(usac_multi *mc) { return static_cast<uint32_t *>(mc->pro_pin); }
+uint32_t *multi_cand_pin(usac_multi *mc) { return static_cast<uint32_t *>(mc->pro_pin.p); }
 uint32_t *multi_cand_n_pin(usac_multi *mc) {
     return multi_cand_pin(mc) + 2 * usac::multi_cand_capacity(mc->n_total, mc->P);
 }
@@ -4188,9 +4190,8 @@ int multi_prosac_ensure(usac_multi *mc) {
     HIP_TRY(mc, mc->non_random.reserve(bytes));
     HIP_TRY(mc, hipMemcpy(mc->growth.p, g.data(), bytes, hipMemcpyHostToDevice));
     HIP_TRY(mc, hipMemcpy(mc->non_random0.p, nr.data(), bytes, hipMemcpyHostToDevice));
-    const size_t need = sizeof(uint32_t) * (2 * usac::multi_cand_capacity(mc->n_total, mc->P) + mc->P);
-    if (!mc->pro_pin) mc->pro_pin = PinnedPool::get().take(need, &mc->pro_pin_bytes);
-    if (!mc->pro_pin) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
+    const int rc = pin_grow(mc, mc->pro_pin, sizeof(uint32_t) * (2 * usac::multi_cand_capacity(mc->n_total, mc->P) + mc->P));
+    if (rc) return rc;
     mc->growth_host.swap(tabs);
     return USAC_OK;
 }
@@ -4342,19 +4343,13 @@ int multi_sprt_ensure(usac_multi *mc, uint32_t A, uint32_t R, bool starts) {
     HIP_TRY(mc, mc->out.reserve((sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A));
     HIP_TRY(mc, mc->sprt_surv.reserve(usac::multi_sprt_survivor_bytes() * S));
     if (starts) HIP_TRY(mc, mc->sprt_starts.reserve(sizeof(uint32_t) * S));
-    const size_t need = (sizeof(usac::SprtConsts) + sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A;
-    if (need > mc->sprt_pin_bytes) {
-        if (mc->sprt_pin) PinnedPool::get().give_back(mc->sprt_pin, mc->sprt_pin_bytes);
-        mc->sprt_pin_bytes = 0;
-        mc->sprt_pin = PinnedPool::get().take(need, &mc->sprt_pin_bytes);
-        if (!mc->sprt_pin) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
-    }
-    return USAC_OK;
+    return pin_grow(mc, mc->sprt_pin,
+                    (sizeof(usac::SprtConsts) + sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A);
 }
 static_assert(sizeof(usac_record) % 8 == 0 && sizeof(usac::SprtConsts) % 8 == 0 && sizeof(usac_multi_sprt_stats) == 32,
               "the records, then the statistics, 8-byte aligned");
 
-usac::SprtConsts *multi_sprt_consts_pin(usac_multi *mc) { return static_cast<usac::SprtConsts *>(mc->sprt_pin); }
+usac::SprtConsts *multi_sprt_consts_pin(usac_multi *mc) { return static_cast<usac::SprtConsts *>(mc->sprt_pin.p); }
 // the down area behind A_cap tests: the launch's A records, then its A statistics
 usac_record *multi_sprt_down_pin(usac_multi *mc, uint32_t A_cap) {
     return reinterpret_cast<usac_record *>(multi_sprt_consts_pin(mc) + A_cap);
@@ -4371,6 +4366,245 @@ usac::MultiSprt multi_sprt_args(usac_multi *mc, uint32_t A, bool starts) {
     s.starts = starts ? mc->sprt_starts.as<uint32_t>() : nullptr;
     s.tail = mc->sprt_tail ? 1 : 0;
     return s;
+}
+
+// ---- the round hooks (usac_multi_hypothesize_score, its SPRT variant, usac_multi_draw_samples)
+// problems == NULL: all P problems in order, else the n_problems listed; A: the number of entries
+int multi_listed(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t &A) {
+    if (!problems && n_problems != 0 && n_problems != mc->P)
+        return fail(mc, USAC_ERR_ARG, "problems == NULL means all problems: n_problems must be P or 0");
+    A = problems ? n_problems : mc->P;
+    if (A == 0 || A > usac::kMultiMaxActive) return fail(mc, USAC_ERR_ARG, "n_problems out of range");
+    return USAC_OK;
+}
+
+// entry by entry, in this order: the problem index, the caller's own check own(a, p) (0: fine), and the
+// entry's R x m sample indices if samples are given
+template <class Own>
+int multi_check_entries(usac_multi *mc, const uint32_t *problems, uint32_t A, const int32_t *samples, uint32_t R,
+                        Own own) {
+    for (uint32_t a = 0; a < A; a++) {
+        const uint32_t p = problems ? problems[a] : a;
+        if (p >= mc->P) return fail(mc, USAC_ERR_ARG, "problem index out of range");
+        const int rc = own(a, p);
+        if (rc) return rc;
+        if (!samples) continue;
+        const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
+        const int32_t *s = samples + (size_t)a * R * mc->m;
+        for (size_t i = 0; i < (size_t)R * mc->m; i++)
+            if (s[i] < 0 || (uint32_t)s[i] >= n) return fail(mc, USAC_ERR_ARG, "sample index out of range");
+    }
+    return USAC_OK;
+}
+
+// the score hooks' checks that precede the per-entry ones
+int multi_hook_args(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, const int32_t *samples, uint32_t R,
+                    const uint64_t *seeds, int dlt_mode, uint32_t &A) {
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
+    if (dlt_mode != USAC_DLT_THIN && dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    const int rc = multi_listed(mc, problems, n_problems, A);
+    if (rc) return rc;
+    if (!samples && !seeds) return fail(mc, USAC_ERR_ARG, "seeds are required with the device sampler");
+    return USAC_OK;
+}
+
+// the score hooks' uploads (after multi_ensure): the entries' items, the host samples if given
+int multi_hook_upload(usac_multi *mc, const uint32_t *problems, uint32_t A, const int32_t *samples, uint32_t R,
+                      const uint64_t *seeds) {
+    usac::MultiItem *items = multi_items_pin(mc);
+    for (uint32_t a = 0; a < A; a++) items[a] = usac::MultiItem{problems ? problems[a] : a, 0u, seeds ? seeds[a] : 0ull};
+    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
+                               mc->stream));
+    if (samples)
+        HIP_TRY(mc, hipMemcpyAsync(mc->samples.p, samples, sizeof(int32_t) * (size_t)A * R * mc->m, hipMemcpyHostToDevice,
+                                   mc->stream));
+    return USAC_OK;
+}
+
+// the score hooks' results down (each nullable); the caller waits for the stream
+int multi_hook_down(usac_multi *mc, uint32_t A, uint32_t R, int32_t *counts, float *sums, usac_record *best) {
+    const size_t S = (size_t)A * R * mc->spk;
+    if (counts) HIP_TRY(mc, hipMemcpyAsync(counts, mc->counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, mc->stream));
+    if (sums) HIP_TRY(mc, hipMemcpyAsync(sums, mc->sums.p, sizeof(float) * S, hipMemcpyDeviceToHost, mc->stream));
+    if (best)
+        HIP_TRY(mc, hipMemcpyAsync(best, mc->out.p, sizeof(usac_record) * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
+    return USAC_OK;
+}
+
+// ---- the batch-granular run: one loop, three options
+// what a run fills besides usac_multi_output (each nullable): the LO counters, PROSAC's final state, the
+// SPRT totals (each only with its option), the polish of the final records and its inlier mask
+struct MultiRunOutputs {
+    usac_multi_lo_output *lo = nullptr;
+    usac_multi_prosac_output *pro = nullptr;
+    usac_multi_sprt_output *sprt = nullptr;
+    usac_multi_polish_output *pol = nullptr;
+    uint8_t *mask = nullptr;
+};
+
+// PROSAC's end of a round of R hypotheses from `first` for active entry a: item `it` is what the round
+// sampled under, rec its record after the round; largest (the sampler's largest_sample_size), bound (the
+// last scan's) and scans are the problem's own.  A new record was scanned by the kernel: its candidates are
+// applied.  Returns the next round's termination length and clock.
+struct ProsacNext {
+    uint32_t term_len, clock;
+};
+ProsacNext multi_prosac_round_end(usac_multi *mc, uint32_t a, const usac::MultiItem &it, const usac_record &rec,
+                                  uint64_t first, uint32_t R, uint32_t &largest, uint32_t &bound, uint32_t &scans) {
+    const uint32_t p = it.problem, n = mc->offsets[p + 1] - mc->offsets[p];
+    const uint32_t *g = mc->growth_host[p]->data();
+    // the round's sampler: PROSAC lanes [0, n_prosac), drawn under (clock, term_len) of its start
+    const uint32_t n_prosac = usac::prosac_round_lanes(g, n, it.clock, it.term_len, R);
+    uint32_t L = it.term_len;
+    if (rec.valid && rec.hyp_index >= first) {
+        const uint32_t j = (uint32_t)(rec.hyp_index - first);
+        const uint32_t at = usac::prosac_largest_at(g, n, mc->m, it.clock, n_prosac, largest, j);
+        bound = multi_apply_candidates(mc, a, p, (uint32_t)rec.hyp_index, at);
+        L = mc->pterm[p]->terminationLength();
+        scans++;
+    }
+    largest = usac::prosac_largest_at(g, n, mc->m, it.clock, n_prosac, largest, R - 1);
+    return ProsacNext{L, it.clock + n_prosac};
+}
+
+// The run behind usac_multi_run, _run_polished, _run_prosac, _run_lo and _run_sprt, which have checked
+// that the params ask for what they offer: prosac (the sampler and its termination), lo (k_multi_lo after
+// every round) and sprt (verification instead of scoring; not with lo) are read from prm.  Per round:
+// the active list (with sprt: and the entries' tests) up, the round, LO, the PROSAC scan, one copy of
+// the records (with sprt: and the statistics behind them) down, one wait; then per entry the bound, and
+// the entry is finished or kept.  Every check comes before the first change of the context's state.
+int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
+                     const MultiRunOutputs &outs) {
+    const bool prosac = prm->sampler == USAC_SAMPLER_PROSAC, sprt = prm->sprt != 0;
+    const bool lo = prm->lo == USAC_LO_INITLORSC || prm->lo == USAC_LO_INITFLORSC;
+    if (lo && sprt) return fail(mc, USAC_ERR_UNSUPPORTED, "no LO with SPRT");
+    const uint32_t R = prm->batch ? prm->batch : 256u;
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
+    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    const uint32_t P = mc->P, m = mc->m;
+    if (prosac)
+        for (uint32_t p = 0; p < P; p++)
+            if (mc->offsets[p + 1] - mc->offsets[p] <= 20)
+                return fail(mc, USAC_ERR_ARG, "PROSAC needs > 20 points per problem (prosac_termination_criteria.hpp:158-163)");
+    double margin = 0, climb = 0;
+    if (sprt && !multi_sprt_cert(margin, climb))
+        return fail(mc, USAC_ERR_ARG, "SPRT certificate: margin >= 1e-7 and 0 < climb <= 700");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    // the buffers; a run starts with fresh LO and PROSAC state
+    int rc = multi_ensure(mc, P, R, false);
+    if (!rc && lo) rc = multi_lo_ensure(mc, prm, true);
+    if (!rc && sprt) rc = multi_sprt_ensure(mc, P, R, false);
+    if (!rc && prosac && !(rc = multi_prosac_ensure(mc))) rc = multi_prosac_reset(mc, prm);
+    if (rc) return rc;
+    // every problem's running record starts invalid (all zero), as a round without a model leaves it
+    HIP_TRY(mc, hipMemsetAsync(mc->running.p, 0, sizeof(usac_record) * (size_t)P, mc->stream));
+    usac::MultiItem *items = multi_items_pin(mc);
+    // with sprt the records and, behind them, the statistics come down in one copy, into their own staging
+    usac::SprtConsts *kc = sprt ? multi_sprt_consts_pin(mc) : nullptr;
+    usac_record *recs = sprt ? multi_sprt_down_pin(mc, P) : multi_records_pin(mc, P);
+    const size_t down = sizeof(usac_record) + (sprt ? sizeof(usac_multi_sprt_stats) : 0);
+    // PROSAC, per problem: the sampler's largest_sample_size, the last scan's bound, the scans
+    std::vector<uint32_t> largest(prosac ? P : 0, m), pbound(prosac ? P : 0, prm->max_iterations), scans(prosac ? P : 0, 0);
+    // SPRT, per problem: the test history and the bound, the run's totals
+    std::vector<usac::SprtRounds> tests;
+    tests.reserve(sprt ? P : 0);
+    std::vector<usac_multi_sprt_output> tot(sprt ? P : 0, usac_multi_sprt_output{});
+    for (uint32_t p = 0; p < P; p++) {
+        const uint64_t seed = seeds ? seeds[p] : (uint64_t)prm->seed + p;
+        const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
+        items[p] = prosac ? usac::MultiItem{p, 1u, seed, n, 0u} : usac::MultiItem{p, 0u, seed, 0u, 0u};
+        out[p] = usac_multi_output{};
+        if (!sprt) continue;
+        tests.emplace_back(mc->estimator, n, m, prm->max_iterations);
+        tests.back().reserve_tests((size_t)prm->max_iterations / R + 2);  // at most one test per round
+    }
+    const usac::StandardTerminationCriteria term(prm->desired_prob, m, 0, prm->max_iterations);
+    uint32_t A = P;
+    for (uint32_t round = 0; A > 0; round++) {
+        const uint64_t first = (uint64_t)round * R, done = first + R;
+        HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
+                                   mc->stream));
+        usac::MultiRound r = multi_round(mc, A, R, first, prm->threshold, prm->dlt_mode);
+        r.running = mc->running.as<usac_record>();
+        if (prosac) r.growth = mc->growth.as<uint32_t>();
+        const usac::MultiSprt ms = sprt ? multi_sprt_args(mc, A, false) : usac::MultiSprt{};
+        if (sprt) {  // every active problem's current test
+            for (uint32_t a = 0; a < A; a++) {
+                const uint32_t p = items[a].problem;
+                const usac::Sprt::History &t = tests[p].test();
+                kc[a] = multi_sprt_consts(t.epsilon, t.delta, t.A, mc->offsets[p + 1] - mc->offsets[p], margin, climb);
+            }
+            HIP_TRY(mc, hipMemcpyAsync(mc->sprt_consts.p, kc, sizeof(usac::SprtConsts) * (size_t)A, hipMemcpyHostToDevice,
+                                       mc->stream));
+            r.sprt = &ms;
+        }
+        HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
+        // LO of the round's new bests; the scan and the record copy see the LO'd records
+        if (lo)
+            HIP_TRY(mc, usac::launch_multi_lo(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), A,
+                                              multi_lo_args(mc, prm, first, false)));
+        if (prosac) HIP_TRY(mc, multi_launch_scan(mc, A, first, prm->threshold));
+        HIP_TRY(mc, hipMemcpyAsync(recs, mc->out.p, down * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
+        HIP_TRY(mc, stream_wait(mc->stream));
+        const usac_multi_sprt_stats *stats = reinterpret_cast<const usac_multi_sprt_stats *>(recs + A);  // with sprt
+        uint32_t keep = 0;
+        for (uint32_t a = 0; a < A; a++) {
+            const usac::MultiItem it = items[a];
+            const uint32_t p = it.problem, n = mc->offsets[p + 1] - mc->offsets[p];
+            ProsacNext nx{0u, 0u};
+            if (prosac) nx = multi_prosac_round_end(mc, a, it, recs[a], first, R, largest[p], pbound[p], scans[p]);
+            uint32_t bnd = prosac ? pbound[p] : term.getUpBoundIterations((uint32_t)recs[a].inliers, n);
+            if (sprt) {  // the sampler's bound counts in a round that improved the record only (SprtRounds::update)
+                usac_multi_sprt_output &so = tot[p];
+                so.accepted += stats[a].accepted;
+                so.rejected += stats[a].rejected_head + stats[a].rejected_tail;
+                so.points_tested += stats[a].points_tested;
+                tests[p].update((uint32_t)done, stats[a].head_inliers, stats[a].head_points,
+                                recs[a].valid && recs[a].hyp_index >= first, (uint32_t)recs[a].inliers, bnd);
+                bnd = tests[p].bound();
+            }
+            if (done >= std::min(prm->max_iterations, bnd)) {
+                usac_multi_output &o = out[p];
+                o.best = recs[a];
+                o.hypotheses = (uint32_t)done;
+                o.rounds = round + 1;
+                o.bound = bnd;
+                o.status = recs[a].inliers > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
+                if (prosac && outs.pro) outs.pro[p] = usac_multi_prosac_output{nx.term_len, largest[p], nx.clock, scans[p]};
+            } else {
+                items[keep++] = prosac ? usac::MultiItem{p, nx.clock, it.seed, nx.term_len, 0u} : it;
+            }
+        }
+        A = keep;
+    }
+    if (lo && (rc = multi_lo_fetch(mc, outs.lo))) return rc;
+    if (sprt && outs.sprt)
+        for (uint32_t p = 0; p < P; p++) {
+            const usac::Sprt::History &t = tests[p].test();
+            tot[p].epsilon = t.epsilon;
+            tot[p].delta = t.delta;
+            tot[p].A = t.A;
+            tot[p].tests = (uint32_t)tests[p].histories();
+            outs.sprt[p] = tot[p];
+        }
+    if (!outs.pol) return USAC_OK;
+    // the run's final records are the device's running records (a problem without a model: all
+    // zero, which the polish reports as USAC_ERR_NO_MODEL): their model fields are the start models
+    static_assert(offsetof(usac_record, model) % sizeof(float) == 0 && sizeof(usac_record) % sizeof(float) == 0,
+                  "usac_record's model as a strided float array");
+    static_assert(offsetof(usac_multi_output, best) % sizeof(float) == 0 && sizeof(usac_multi_output) % sizeof(float) == 0,
+                  "usac_multi_output's model as a strided float array");
+    return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
+                               sizeof(usac_record) / sizeof(float), out[0].best.model,
+                               sizeof(usac_multi_output) / sizeof(float), prm->threshold, outs.pol, outs.mask);
+}
+
+// usac_multi_run with or without the polish (usac_multi_run_polished)
+int multi_run_uniform(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
+                      usac_multi_polish_output *pol, uint8_t *mask) {
+    if (prm->sprt || prm->lo != USAC_LO_NONE || prm->sampler != USAC_SAMPLER_UNIFORM)
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run: uniform sampler only, no SPRT, no LO (LO: usac_multi_run_lo)");
+    return multi_run_driver(mc, prm, seeds, out, MultiRunOutputs{nullptr, nullptr, nullptr, pol, mask});
 }
 
 }  // namespace
@@ -4447,10 +4681,8 @@ void usac_multi_destroy(usac_multi *mc) {
     if (!mc) return;
     (void)hipSetDevice(mc->device);
     if (mc->stream) (void)hipStreamSynchronize(mc->stream);
-    if (mc->pin) PinnedPool::get().give_back(mc->pin, mc->pin_bytes);
-    if (mc->pol_pin) PinnedPool::get().give_back(mc->pol_pin, mc->pol_pin_bytes);
-    if (mc->pro_pin) PinnedPool::get().give_back(mc->pro_pin, mc->pro_pin_bytes);
-    if (mc->sprt_pin) PinnedPool::get().give_back(mc->sprt_pin, mc->sprt_pin_bytes);
+    for (PinBlock *b : {&mc->pin, &mc->pol_pin, &mc->pro_pin, &mc->sprt_pin})
+        if (b->p) PinnedPool::get().give_back(b->p, b->bytes);
     for (DevBuf *b : {&mc->growth, &mc->non_random0, &mc->non_random}) b->release();
     for (DevBuf *b : {&mc->sprt_pts, &mc->sprt_idx, &mc->sprt_consts, &mc->sprt_surv, &mc->sprt_surv_n, &mc->sprt_starts})
         b->release();
@@ -4469,94 +4701,24 @@ int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint3
                                  const int32_t *samples, uint32_t R, const uint64_t *seeds, uint64_t first_hyp,
                                  float thr, int dlt_mode, int32_t *counts, float *sums, usac_record *best) {
     if (!mc) return USAC_ERR_ARG;
-    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
-    if (dlt_mode != USAC_DLT_THIN && dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
-    if (!problems && n_problems != 0 && n_problems != mc->P)
-        return fail(mc, USAC_ERR_ARG, "problems == NULL means all problems: n_problems must be P or 0");
-    const uint32_t A = problems ? n_problems : mc->P;
-    if (A == 0 || A > usac::kMultiMaxActive) return fail(mc, USAC_ERR_ARG, "n_problems out of range");
-    if (!samples && !seeds) return fail(mc, USAC_ERR_ARG, "seeds are required with the device sampler");
-    for (uint32_t a = 0; a < A; a++) {
-        const uint32_t p = problems ? problems[a] : a;
-        if (p >= mc->P) return fail(mc, USAC_ERR_ARG, "problem index out of range");
-        if (!samples) continue;
-        const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
-        const int32_t *s = samples + (size_t)a * R * mc->m;
-        for (size_t i = 0; i < (size_t)R * mc->m; i++)
-            if (s[i] < 0 || (uint32_t)s[i] >= n) return fail(mc, USAC_ERR_ARG, "sample index out of range");
-    }
+    uint32_t A = 0;
+    int rc = multi_hook_args(mc, problems, n_problems, samples, R, seeds, dlt_mode, A);
+    if (rc || (rc = multi_check_entries(mc, problems, A, samples, R, [](uint32_t, uint32_t) -> int { return USAC_OK; })))
+        return rc;
     HIP_TRY(mc, hipSetDevice(mc->device));
-    int rc = multi_ensure(mc, A, R, samples != nullptr);
-    if (rc) return rc;
-    usac::MultiItem *items = multi_items_pin(mc);
-    for (uint32_t a = 0; a < A; a++) items[a] = usac::MultiItem{problems ? problems[a] : a, 0u, seeds ? seeds[a] : 0ull};
-    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
-                               mc->stream));
-    const size_t G = (size_t)A * R, S = G * mc->spk;
-    if (samples)
-        HIP_TRY(mc, hipMemcpyAsync(mc->samples.p, samples, sizeof(int32_t) * G * mc->m, hipMemcpyHostToDevice,
-                                   mc->stream));
+    if ((rc = multi_ensure(mc, A, R, samples != nullptr)) || (rc = multi_hook_upload(mc, problems, A, samples, R, seeds)))
+        return rc;
     usac::MultiRound r = multi_round(mc, A, R, first_hyp, thr, dlt_mode);
     r.samples_in = samples ? mc->samples.as<int32_t>() : nullptr;
     HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
-    if (counts) HIP_TRY(mc, hipMemcpyAsync(counts, mc->counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, mc->stream));
-    if (sums) HIP_TRY(mc, hipMemcpyAsync(sums, mc->sums.p, sizeof(float) * S, hipMemcpyDeviceToHost, mc->stream));
-    if (best)
-        HIP_TRY(mc, hipMemcpyAsync(best, mc->out.p, sizeof(usac_record) * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
+    if ((rc = multi_hook_down(mc, A, R, counts, sums, best))) return rc;
     HIP_TRY(mc, stream_wait(mc->stream));
     return USAC_OK;
 }
 
 int usac_multi_run(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out) {
     if (!mc || !prm || !out) return USAC_ERR_ARG;
-    if (prm->sprt || prm->lo != USAC_LO_NONE || prm->sampler != USAC_SAMPLER_UNIFORM)
-        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run: uniform sampler only, no SPRT, no LO (LO: usac_multi_run_lo)");
-    const uint32_t R = prm->batch ? prm->batch : 256u;
-    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
-    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
-    const uint32_t P = mc->P;
-    HIP_TRY(mc, hipSetDevice(mc->device));
-    int rc = multi_ensure(mc, P, R, false);
-    if (rc) return rc;
-    // every problem's running record starts invalid (all zero), as a round without a model leaves it
-    HIP_TRY(mc, hipMemsetAsync(mc->running.p, 0, sizeof(usac_record) * (size_t)P, mc->stream));
-    usac::MultiItem *items = multi_items_pin(mc);
-    usac_record *recs = multi_records_pin(mc, P);
-    for (uint32_t p = 0; p < P; p++) {
-        items[p] = usac::MultiItem{p, 0u, seeds ? seeds[p] : (uint64_t)prm->seed + p};
-        out[p] = usac_multi_output{};
-    }
-    const usac::StandardTerminationCriteria term(prm->desired_prob, mc->m, 0, prm->max_iterations);
-    uint32_t A = P;
-    for (uint32_t round = 0; A > 0; round++) {
-        HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
-                                   mc->stream));
-        usac::MultiRound r = multi_round(mc, A, R, (uint64_t)round * R, prm->threshold, prm->dlt_mode);
-        r.running = mc->running.as<usac_record>();
-        HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
-        HIP_TRY(mc, hipMemcpyAsync(recs, mc->out.p, sizeof(usac_record) * (size_t)A,
-                                   hipMemcpyDeviceToHost, mc->stream));
-        HIP_TRY(mc, stream_wait(mc->stream));
-        const uint64_t done = ((uint64_t)round + 1) * R;
-        uint32_t keep = 0;
-        for (uint32_t a = 0; a < A; a++) {
-            const uint32_t p = items[a].problem;
-            const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
-            const uint32_t bound = term.getUpBoundIterations((uint32_t)recs[a].inliers, n);
-            if (done >= std::min(prm->max_iterations, bound)) {
-                usac_multi_output &o = out[p];
-                o.best = recs[a];
-                o.hypotheses = (uint32_t)done;
-                o.rounds = round + 1;
-                o.bound = bound;
-                o.status = recs[a].inliers > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
-            } else {
-                items[keep++] = items[a];  // the compacted active list of the next round
-            }
-        }
-        A = keep;
-    }
-    return USAC_OK;
+    return multi_run_uniform(mc, prm, seeds, out, nullptr, nullptr);
 }
 
 int usac_multi_inliers(usac_multi *mc, const float *models, float thr, uint8_t *mask, int32_t *counts) {
@@ -4598,17 +4760,7 @@ int usac_multi_polish(usac_multi *mc, const float *models, float thr, usac_multi
 int usac_multi_run_polished(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
                             usac_multi_polish_output *pol, uint8_t *mask) {
     if (!mc || !prm || !out || !pol) return USAC_ERR_ARG;
-    const int rc = usac_multi_run(mc, prm, seeds, out);
-    if (rc) return rc;
-    // the run's final records are the device's running records (a problem without a model: all
-    // zero, which the polish reports as USAC_ERR_NO_MODEL): their model fields are the start models
-    static_assert(offsetof(usac_record, model) % sizeof(float) == 0 && sizeof(usac_record) % sizeof(float) == 0,
-                  "usac_record's model as a strided float array");
-    static_assert(offsetof(usac_multi_output, best) % sizeof(float) == 0 && sizeof(usac_multi_output) % sizeof(float) == 0,
-                  "usac_multi_output's model as a strided float array");
-    return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
-                               sizeof(usac_record) / sizeof(float), out[0].best.model,
-                               sizeof(usac_multi_output) / sizeof(float), prm->threshold, pol, mask);
+    return multi_run_uniform(mc, prm, seeds, out, pol, mask);  // the run, then the polish of its final records
 }
 
 // ---- PROSAC (ABI 17)
@@ -4618,10 +4770,9 @@ int usac_multi_draw_samples(usac_multi *mc, const uint32_t *problems, uint32_t n
     if (!mc) return USAC_ERR_ARG;
     if (!seeds || !out || (clock && !term_len)) return fail(mc, USAC_ERR_ARG, "seeds, out and (with clock) term_len");
     if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
-    if (!problems && n_problems != 0 && n_problems != mc->P)
-        return fail(mc, USAC_ERR_ARG, "problems == NULL means all problems: n_problems must be P or 0");
-    const uint32_t A = problems ? n_problems : mc->P;
-    if (A == 0 || A > usac::kMultiMaxActive) return fail(mc, USAC_ERR_ARG, "n_problems out of range");
+    uint32_t A = 0;
+    int rc = multi_listed(mc, problems, n_problems, A);
+    if (rc) return rc;
     for (uint32_t a = 0; a < A; a++) {
         const uint32_t p = problems ? problems[a] : a;
         if (p >= mc->P) return fail(mc, USAC_ERR_ARG, "problem index out of range");
@@ -4631,8 +4782,7 @@ int usac_multi_draw_samples(usac_multi *mc, const uint32_t *problems, uint32_t n
             return fail(mc, USAC_ERR_ARG, "clock >= 1 and sample size <= term_len <= n_p");
     }
     HIP_TRY(mc, hipSetDevice(mc->device));
-    int rc = multi_ensure(mc, A, R, true);
-    if (rc) return rc;
+    if ((rc = multi_ensure(mc, A, R, true))) return rc;
     if (clock && (rc = multi_prosac_ensure(mc))) return rc;
     usac::MultiItem *items = multi_items_pin(mc);
     for (uint32_t a = 0; a < A; a++)
@@ -4689,72 +4839,7 @@ int usac_multi_run_prosac(usac_multi *mc, const usac_params *prm, const uint64_t
     if (prm->sprt || prm->lo != USAC_LO_NONE)
         return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run_prosac: no SPRT, no LO (LO: usac_multi_run_lo)");
     if (prm->sampler != USAC_SAMPLER_PROSAC) return fail(mc, USAC_ERR_ARG, "usac_multi_run_prosac: the PROSAC sampler");
-    const uint32_t R = prm->batch ? prm->batch : 256u;
-    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
-    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
-    const uint32_t P = mc->P, m = mc->m;
-    for (uint32_t p = 0; p < P; p++)
-        if (mc->offsets[p + 1] - mc->offsets[p] <= 20)
-            return fail(mc, USAC_ERR_ARG, "PROSAC needs > 20 points per problem (prosac_termination_criteria.hpp:158-163)");
-    HIP_TRY(mc, hipSetDevice(mc->device));
-    int rc = multi_ensure(mc, P, R, false);
-    if (rc || (rc = multi_prosac_ensure(mc)) || (rc = multi_prosac_reset(mc, prm))) return rc;
-    HIP_TRY(mc, hipMemsetAsync(mc->running.p, 0, sizeof(usac_record) * (size_t)P, mc->stream));
-    usac::MultiItem *items = multi_items_pin(mc);
-    usac_record *recs = multi_records_pin(mc, P);
-    // per problem: the sampler's largest_sample_size, the last scan's bound, the scans
-    std::vector<uint32_t> largest(P, m), bound(P, prm->max_iterations), scans(P, 0);
-    for (uint32_t p = 0; p < P; p++) {
-        items[p] = usac::MultiItem{p, 1u, seeds ? seeds[p] : (uint64_t)prm->seed + p, mc->offsets[p + 1] - mc->offsets[p], 0u};
-        out[p] = usac_multi_output{};
-    }
-    uint32_t A = P;
-    for (uint32_t round = 0; A > 0; round++) {
-        const uint64_t first = (uint64_t)round * R, done = first + R;
-        HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
-                                   mc->stream));
-        usac::MultiRound r = multi_round(mc, A, R, first, prm->threshold, prm->dlt_mode);
-        r.running = mc->running.as<usac_record>();
-        r.growth = mc->growth.as<uint32_t>();
-        HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
-        HIP_TRY(mc, multi_launch_scan(mc, A, first, prm->threshold));
-        HIP_TRY(mc, hipMemcpyAsync(recs, mc->out.p, sizeof(usac_record) * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
-        HIP_TRY(mc, stream_wait(mc->stream));
-        uint32_t keep = 0;
-        for (uint32_t a = 0; a < A; a++) {
-            const usac::MultiItem it = items[a];
-            const uint32_t p = it.problem, n = mc->offsets[p + 1] - mc->offsets[p];
-            const uint32_t *g = mc->growth_host[p]->data();
-            // the round's sampler: PROSAC lanes [0, n_prosac), drawn under (clock, term_len) of its start
-            const uint32_t n_prosac = usac::prosac_round_lanes(g, n, it.clock, it.term_len, R);
-            uint32_t L = it.term_len;
-            if (recs[a].valid && recs[a].hyp_index >= first) {  // a new best: the kernel scanned it
-                const uint32_t j = (uint32_t)(recs[a].hyp_index - first);
-                const uint32_t at = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], j);
-                bound[p] = multi_apply_candidates(mc, a, p, (uint32_t)recs[a].hyp_index, at);
-                L = mc->pterm[p]->terminationLength();
-                scans[p]++;
-            }
-            largest[p] = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], R - 1);
-            const uint32_t T = it.clock + n_prosac;
-            if (done >= std::min(prm->max_iterations, bound[p])) {
-                usac_multi_output &o = out[p];
-                o.best = recs[a];
-                o.hypotheses = (uint32_t)done;
-                o.rounds = round + 1;
-                o.bound = bound[p];
-                o.status = recs[a].inliers > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
-                if (pro) pro[p] = usac_multi_prosac_output{L, largest[p], T, scans[p]};
-            } else {
-                items[keep++] = usac::MultiItem{p, T, it.seed, L, 0u};
-            }
-        }
-        A = keep;
-    }
-    if (!pol) return USAC_OK;
-    return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
-                               sizeof(usac_record) / sizeof(float), out[0].best.model,
-                               sizeof(usac_multi_output) / sizeof(float), prm->threshold, pol, mask);
+    return multi_run_driver(mc, prm, seeds, out, MultiRunOutputs{nullptr, pro, nullptr, pol, mask});
 }
 
 // ---- LO-RANSAC (ABI 18)
@@ -4791,86 +4876,7 @@ int usac_multi_run_lo(usac_multi *mc, const usac_params *prm, const uint64_t *se
     if (rc) return rc;
     if (prm->sampler != USAC_SAMPLER_UNIFORM && prm->sampler != USAC_SAMPLER_PROSAC)
         return fail(mc, USAC_ERR_ARG, "usac_multi_run_lo: the uniform or the PROSAC sampler");
-    const bool prosac = prm->sampler == USAC_SAMPLER_PROSAC;
-    const uint32_t R = prm->batch ? prm->batch : 256u;
-    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
-    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
-    const uint32_t P = mc->P, m = mc->m;
-    if (prosac)
-        for (uint32_t p = 0; p < P; p++)
-            if (mc->offsets[p + 1] - mc->offsets[p] <= 20)
-                return fail(mc, USAC_ERR_ARG, "PROSAC needs > 20 points per problem (prosac_termination_criteria.hpp:158-163)");
-    HIP_TRY(mc, hipSetDevice(mc->device));
-    if ((rc = multi_ensure(mc, P, R, false)) || (rc = multi_lo_ensure(mc, prm, true))) return rc;
-    if (prosac && ((rc = multi_prosac_ensure(mc)) || (rc = multi_prosac_reset(mc, prm)))) return rc;
-    HIP_TRY(mc, hipMemsetAsync(mc->running.p, 0, sizeof(usac_record) * (size_t)P, mc->stream));
-    usac::MultiItem *items = multi_items_pin(mc);
-    usac_record *recs = multi_records_pin(mc, P);
-    // PROSAC, per problem: the sampler's largest_sample_size, the last scan's bound, the scans
-    std::vector<uint32_t> largest(prosac ? P : 0, m), bound(prosac ? P : 0, prm->max_iterations), scans(prosac ? P : 0, 0);
-    for (uint32_t p = 0; p < P; p++) {
-        const uint64_t seed = seeds ? seeds[p] : (uint64_t)prm->seed + p;
-        items[p] = prosac ? usac::MultiItem{p, 1u, seed, mc->offsets[p + 1] - mc->offsets[p], 0u}
-                          : usac::MultiItem{p, 0u, seed, 0u, 0u};
-        out[p] = usac_multi_output{};
-    }
-    const usac::StandardTerminationCriteria term(prm->desired_prob, m, 0, prm->max_iterations);
-    uint32_t A = P;
-    for (uint32_t round = 0; A > 0; round++) {
-        const uint64_t first = (uint64_t)round * R, done = first + R;
-        HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
-                                   mc->stream));
-        usac::MultiRound r = multi_round(mc, A, R, first, prm->threshold, prm->dlt_mode);
-        r.running = mc->running.as<usac_record>();
-        if (prosac) r.growth = mc->growth.as<uint32_t>();
-        HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
-        // LO of the round's new bests; the scan and the record copy see the LO'd records
-        HIP_TRY(mc, usac::launch_multi_lo(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), A,
-                                          multi_lo_args(mc, prm, first, false)));
-        if (prosac) HIP_TRY(mc, multi_launch_scan(mc, A, first, prm->threshold));
-        HIP_TRY(mc, hipMemcpyAsync(recs, mc->out.p, sizeof(usac_record) * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
-        HIP_TRY(mc, stream_wait(mc->stream));
-        uint32_t keep = 0;
-        for (uint32_t a = 0; a < A; a++) {
-            const usac::MultiItem it = items[a];
-            const uint32_t p = it.problem, n = mc->offsets[p + 1] - mc->offsets[p];
-            uint32_t bnd, L = 0, T = 0;
-            if (prosac) {  // usac_multi_run_prosac's round end
-                const uint32_t *g = mc->growth_host[p]->data();
-                const uint32_t n_prosac = usac::prosac_round_lanes(g, n, it.clock, it.term_len, R);
-                L = it.term_len;
-                if (recs[a].valid && recs[a].hyp_index >= first) {
-                    const uint32_t j = (uint32_t)(recs[a].hyp_index - first);
-                    const uint32_t at = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], j);
-                    bound[p] = multi_apply_candidates(mc, a, p, (uint32_t)recs[a].hyp_index, at);
-                    L = mc->pterm[p]->terminationLength();
-                    scans[p]++;
-                }
-                largest[p] = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], R - 1);
-                T = it.clock + n_prosac;
-                bnd = bound[p];
-            } else {
-                bnd = term.getUpBoundIterations((uint32_t)recs[a].inliers, n);
-            }
-            if (done >= std::min(prm->max_iterations, bnd)) {
-                usac_multi_output &o = out[p];
-                o.best = recs[a];
-                o.hypotheses = (uint32_t)done;
-                o.rounds = round + 1;
-                o.bound = bnd;
-                o.status = recs[a].inliers > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
-                if (prosac && pro) pro[p] = usac_multi_prosac_output{L, largest[p], T, scans[p]};
-            } else {
-                items[keep++] = prosac ? usac::MultiItem{p, T, it.seed, L, 0u} : it;
-            }
-        }
-        A = keep;
-    }
-    if ((rc = multi_lo_fetch(mc, lo))) return rc;
-    if (!pol) return USAC_OK;
-    return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
-                               sizeof(usac_record) / sizeof(float), out[0].best.model,
-                               sizeof(usac_multi_output) / sizeof(float), prm->threshold, pol, mask);
+    return multi_run_driver(mc, prm, seeds, out, MultiRunOutputs{lo, pro, nullptr, pol, mask});
 }
 
 // ---- SPRT (ABI 19)
@@ -4903,29 +4909,19 @@ int usac_multi_hypothesize_score_sprt(usac_multi *mc, const uint32_t *problems, 
                                       float thr, int dlt_mode, const double *eps_delta, int32_t *counts, float *sums,
                                       usac_record *best, usac_multi_sprt_stats *stats, uint32_t *starts) {
     if (!mc) return USAC_ERR_ARG;
-    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
-    if (dlt_mode != USAC_DLT_THIN && dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
-    if (!problems && n_problems != 0 && n_problems != mc->P)
-        return fail(mc, USAC_ERR_ARG, "problems == NULL means all problems: n_problems must be P or 0");
-    const uint32_t A = problems ? n_problems : mc->P;
-    if (A == 0 || A > usac::kMultiMaxActive) return fail(mc, USAC_ERR_ARG, "n_problems out of range");
-    if (!samples && !seeds) return fail(mc, USAC_ERR_ARG, "seeds are required with the device sampler");
+    uint32_t A = 0;
+    int rc = multi_hook_args(mc, problems, n_problems, samples, R, seeds, dlt_mode, A);
+    if (rc) return rc;
     double margin, climb;
     if (!multi_sprt_cert(margin, climb)) return fail(mc, USAC_ERR_ARG, "SPRT certificate: margin >= 1e-7 and 0 < climb <= 700");
-    for (uint32_t a = 0; a < A; a++) {
-        const uint32_t p = problems ? problems[a] : a;
-        if (p >= mc->P) return fail(mc, USAC_ERR_ARG, "problem index out of range");
-        if (eps_delta) {
-            const double e = eps_delta[2 * a], d = eps_delta[2 * a + 1];
-            if ((e != 0 && !(e > 0 && e < 1)) || (d != 0 && !(d > 0 && d < 1)))
-                return fail(mc, USAC_ERR_ARG, "SPRT: epsilon and delta must be in (0, 1)");
-        }
-        if (!samples) continue;
-        const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
-        const int32_t *s = samples + (size_t)a * R * mc->m;
-        for (size_t i = 0; i < (size_t)R * mc->m; i++)
-            if (s[i] < 0 || (uint32_t)s[i] >= n) return fail(mc, USAC_ERR_ARG, "sample index out of range");
-    }
+    rc = multi_check_entries(mc, problems, A, samples, R, [&](uint32_t a, uint32_t) -> int {
+        if (!eps_delta) return USAC_OK;
+        const double e = eps_delta[2 * a], d = eps_delta[2 * a + 1];
+        if ((e != 0 && !(e > 0 && e < 1)) || (d != 0 && !(d > 0 && d < 1)))
+            return fail(mc, USAC_ERR_ARG, "SPRT: epsilon and delta must be in (0, 1)");
+        return USAC_OK;
+    });
+    if (rc) return rc;
     // the tests, before any device call (delta < epsilon with the defaults filled in)
     std::vector<usac::SprtConsts> kc(A);
     for (uint32_t a = 0; a < A; a++) {
@@ -4937,32 +4933,24 @@ int usac_multi_hypothesize_score_sprt(usac_multi *mc, const uint32_t *problems, 
         kc[a] = multi_sprt_consts(e, d, st.thresholdA(e, d), n, margin, climb);
     }
     HIP_TRY(mc, hipSetDevice(mc->device));
-    int rc = multi_ensure(mc, A, R, samples != nullptr);
-    if (rc || (rc = multi_sprt_ensure(mc, A, R, starts != nullptr))) return rc;
-    usac::MultiItem *items = multi_items_pin(mc);
-    for (uint32_t a = 0; a < A; a++) items[a] = usac::MultiItem{problems ? problems[a] : a, 0u, seeds ? seeds[a] : 0ull};
+    if ((rc = multi_ensure(mc, A, R, samples != nullptr)) || (rc = multi_sprt_ensure(mc, A, R, starts != nullptr)) ||
+        (rc = multi_hook_upload(mc, problems, A, samples, R, seeds)))
+        return rc;
     memcpy(multi_sprt_consts_pin(mc), kc.data(), sizeof(usac::SprtConsts) * (size_t)A);
-    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
-                               mc->stream));
     HIP_TRY(mc, hipMemcpyAsync(mc->sprt_consts.p, multi_sprt_consts_pin(mc), sizeof(usac::SprtConsts) * (size_t)A,
                                hipMemcpyHostToDevice, mc->stream));
-    const size_t G = (size_t)A * R, S = G * mc->spk;
-    if (samples)
-        HIP_TRY(mc, hipMemcpyAsync(mc->samples.p, samples, sizeof(int32_t) * G * mc->m, hipMemcpyHostToDevice,
-                                   mc->stream));
     usac::MultiRound r = multi_round(mc, A, R, first_hyp, thr, dlt_mode);
     r.samples_in = samples ? mc->samples.as<int32_t>() : nullptr;
     const usac::MultiSprt ms = multi_sprt_args(mc, A, starts != nullptr);
     r.sprt = &ms;
     HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
-    if (counts) HIP_TRY(mc, hipMemcpyAsync(counts, mc->counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, mc->stream));
-    if (sums) HIP_TRY(mc, hipMemcpyAsync(sums, mc->sums.p, sizeof(float) * S, hipMemcpyDeviceToHost, mc->stream));
-    if (best)
-        HIP_TRY(mc, hipMemcpyAsync(best, mc->out.p, sizeof(usac_record) * (size_t)A, hipMemcpyDeviceToHost, mc->stream));
+    if ((rc = multi_hook_down(mc, A, R, counts, sums, best))) return rc;
     if (stats)
         HIP_TRY(mc, hipMemcpyAsync(stats, ms.stats, sizeof(usac_multi_sprt_stats) * (size_t)A, hipMemcpyDeviceToHost,
                                    mc->stream));
-    if (starts) HIP_TRY(mc, hipMemcpyAsync(starts, mc->sprt_starts.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, mc->stream));
+    if (starts)
+        HIP_TRY(mc, hipMemcpyAsync(starts, mc->sprt_starts.p, sizeof(uint32_t) * (size_t)A * R * mc->spk, hipMemcpyDeviceToHost,
+                                   mc->stream));
     HIP_TRY(mc, stream_wait(mc->stream));
     return USAC_OK;
 }
@@ -4976,121 +4964,7 @@ int usac_multi_run_sprt(usac_multi *mc, const usac_params *prm, const uint64_t *
     if (!prm->sprt) return fail(mc, USAC_ERR_ARG, "usac_multi_run_sprt: params->sprt must be set");
     if (prm->sampler != USAC_SAMPLER_UNIFORM && prm->sampler != USAC_SAMPLER_PROSAC)
         return fail(mc, USAC_ERR_ARG, "usac_multi_run_sprt: the uniform or the PROSAC sampler");
-    const bool prosac = prm->sampler == USAC_SAMPLER_PROSAC;
-    const uint32_t R = prm->batch ? prm->batch : 256u;
-    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
-    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
-    const uint32_t P = mc->P, m = mc->m;
-    if (prosac)
-        for (uint32_t p = 0; p < P; p++)
-            if (mc->offsets[p + 1] - mc->offsets[p] <= 20)
-                return fail(mc, USAC_ERR_ARG, "PROSAC needs > 20 points per problem (prosac_termination_criteria.hpp:158-163)");
-    double margin, climb;
-    if (!multi_sprt_cert(margin, climb)) return fail(mc, USAC_ERR_ARG, "SPRT certificate: margin >= 1e-7 and 0 < climb <= 700");
-    HIP_TRY(mc, hipSetDevice(mc->device));
-    int rc = multi_ensure(mc, P, R, false);
-    if (rc || (rc = multi_sprt_ensure(mc, P, R, false))) return rc;
-    if (prosac && ((rc = multi_prosac_ensure(mc)) || (rc = multi_prosac_reset(mc, prm)))) return rc;
-    HIP_TRY(mc, hipMemsetAsync(mc->running.p, 0, sizeof(usac_record) * (size_t)P, mc->stream));
-    usac::MultiItem *items = multi_items_pin(mc);
-    usac::SprtConsts *kc = multi_sprt_consts_pin(mc);
-    usac_record *recs = multi_sprt_down_pin(mc, P);
-    // PROSAC, per problem: the sampler's largest_sample_size, the last scan's bound, the scans
-    std::vector<uint32_t> largest(prosac ? P : 0, m), pbound(prosac ? P : 0, prm->max_iterations), scans(prosac ? P : 0, 0);
-    // SPRT, per problem: the test history and the bound, the run's totals
-    std::vector<usac::SprtRounds> tests;
-    tests.reserve(P);
-    std::vector<usac_multi_sprt_output> tot(P, usac_multi_sprt_output{});
-    for (uint32_t p = 0; p < P; p++) {
-        const uint64_t seed = seeds ? seeds[p] : (uint64_t)prm->seed + p;
-        const uint32_t n = mc->offsets[p + 1] - mc->offsets[p];
-        items[p] = prosac ? usac::MultiItem{p, 1u, seed, n, 0u} : usac::MultiItem{p, 0u, seed, 0u, 0u};
-        out[p] = usac_multi_output{};
-        tests.emplace_back(mc->estimator, n, m, prm->max_iterations);
-        tests.back().reserve_tests((size_t)prm->max_iterations / R + 2);  // at most one test per round
-    }
-    const usac::StandardTerminationCriteria term(prm->desired_prob, m, 0, prm->max_iterations);
-    uint32_t A = P;
-    for (uint32_t round = 0; A > 0; round++) {
-        const uint64_t first = (uint64_t)round * R, done = first + R;
-        for (uint32_t a = 0; a < A; a++) {  // every active problem's current test
-            const uint32_t p = items[a].problem;
-            const usac::Sprt::History &t = tests[p].test();
-            kc[a] = multi_sprt_consts(t.epsilon, t.delta, t.A, mc->offsets[p + 1] - mc->offsets[p], margin, climb);
-        }
-        HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)A, hipMemcpyHostToDevice,
-                                   mc->stream));
-        HIP_TRY(mc, hipMemcpyAsync(mc->sprt_consts.p, kc, sizeof(usac::SprtConsts) * (size_t)A, hipMemcpyHostToDevice,
-                                   mc->stream));
-        usac::MultiRound r = multi_round(mc, A, R, first, prm->threshold, prm->dlt_mode);
-        r.running = mc->running.as<usac_record>();
-        if (prosac) r.growth = mc->growth.as<uint32_t>();
-        const usac::MultiSprt ms = multi_sprt_args(mc, A, false);
-        r.sprt = &ms;
-        HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
-        if (prosac) HIP_TRY(mc, multi_launch_scan(mc, A, first, prm->threshold));
-        // the A records and, behind them, the A statistics: one copy
-        HIP_TRY(mc, hipMemcpyAsync(recs, mc->out.p, (sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A,
-                                   hipMemcpyDeviceToHost, mc->stream));
-        HIP_TRY(mc, stream_wait(mc->stream));
-        const usac_multi_sprt_stats *stats = reinterpret_cast<const usac_multi_sprt_stats *>(recs + A);
-        uint32_t keep = 0;
-        for (uint32_t a = 0; a < A; a++) {
-            const usac::MultiItem it = items[a];
-            const uint32_t p = it.problem, n = mc->offsets[p + 1] - mc->offsets[p];
-            const bool improved = recs[a].valid && recs[a].hyp_index >= first;
-            uint32_t tb = 0, L = 0, T = 0;
-            if (prosac) {  // usac_multi_run_prosac's round end
-                const uint32_t *g = mc->growth_host[p]->data();
-                const uint32_t n_prosac = usac::prosac_round_lanes(g, n, it.clock, it.term_len, R);
-                L = it.term_len;
-                if (improved) {
-                    const uint32_t j = (uint32_t)(recs[a].hyp_index - first);
-                    const uint32_t at = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], j);
-                    pbound[p] = multi_apply_candidates(mc, a, p, (uint32_t)recs[a].hyp_index, at);
-                    L = mc->pterm[p]->terminationLength();
-                    scans[p]++;
-                }
-                largest[p] = usac::prosac_largest_at(g, n, m, it.clock, n_prosac, largest[p], R - 1);
-                T = it.clock + n_prosac;
-                tb = pbound[p];
-            } else if (improved) {
-                tb = term.getUpBoundIterations((uint32_t)recs[a].inliers, n);
-            }
-            usac_multi_sprt_output &so = tot[p];
-            so.accepted += stats[a].accepted;
-            so.rejected += stats[a].rejected_head + stats[a].rejected_tail;
-            so.points_tested += stats[a].points_tested;
-            tests[p].update((uint32_t)done, stats[a].head_inliers, stats[a].head_points, improved,
-                            (uint32_t)recs[a].inliers, tb);
-            const uint32_t bnd = tests[p].bound();
-            if (done >= std::min(prm->max_iterations, bnd)) {
-                usac_multi_output &o = out[p];
-                o.best = recs[a];
-                o.hypotheses = (uint32_t)done;
-                o.rounds = round + 1;
-                o.bound = bnd;
-                o.status = recs[a].inliers > 0 ? USAC_OK : USAC_ERR_NO_MODEL;
-                if (prosac && pro) pro[p] = usac_multi_prosac_output{L, largest[p], T, scans[p]};
-            } else {
-                items[keep++] = prosac ? usac::MultiItem{p, T, it.seed, L, 0u} : it;
-            }
-        }
-        A = keep;
-    }
-    if (sprt)
-        for (uint32_t p = 0; p < P; p++) {
-            const usac::Sprt::History &t = tests[p].test();
-            tot[p].epsilon = t.epsilon;
-            tot[p].delta = t.delta;
-            tot[p].A = t.A;
-            tot[p].tests = (uint32_t)tests[p].histories();
-            sprt[p] = tot[p];
-        }
-    if (!pol) return USAC_OK;
-    return multi_polish_device(mc, mc->running.as<float>() + offsetof(usac_record, model) / sizeof(float),
-                               sizeof(usac_record) / sizeof(float), out[0].best.model,
-                               sizeof(usac_multi_output) / sizeof(float), prm->threshold, pol, mask);
+    return multi_run_driver(mc, prm, seeds, out, MultiRunOutputs{nullptr, pro, sprt, pol, mask});
 }
 
 }  // extern "C"
