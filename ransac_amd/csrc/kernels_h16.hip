@@ -269,13 +269,15 @@ __device__ __forceinline__ void h16_drain(uint32_t cnt, uint32_t head, const uin
 // (hypothesis t, component r) with i = (rho & 3) + 4 (rho >> 3), t = 5 ((rho >> 2) & 1) + i / 3, r = i % 3
 // (i < 15; row i = 15 of each lane half is spare), so that the D register q of lane half hf holds
 // (hypothesis 5 hf + q / 3, component q % 3): each lane owns whole (ex, ey, zr) triples of five
-// hypotheses of each tile for its point.
+// hypotheses of each tile for its point.  U = 1 always: the blocks of a trip run one after the other
+// (the parameter stays in the kernel's name, which the bench and the profile summaries match on).
 template <int NA, int U, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_score_h16(const half8 *__restrict__ feat, const float4 *__restrict__ pts,
                                                    uint32_t n, const half8 *__restrict__ rows,
                                                    const float *__restrict__ fm, const float *__restrict__ models,
                                                    uint32_t B, float thr, double fxs, uint32_t *__restrict__ cpart,
                                                    unsigned long long *__restrict__ spart) {
+    static_assert(U == 1, "one form of the block loop");
     constexpr int HW = 10 * NA;
     constexpr uint32_t Q = h16_queue<NA>();
     __shared__ uint32_t sQ[4][Q];
@@ -323,14 +325,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             }
         }
     }
-    // U 32-point blocks per iteration (their MFMAs issue back to back, then all the tests), the next
-    // iteration's blocks' features loaded while this iteration's tiles are tested
-    half8 bn[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const uint32_t bu = b0 + u < nblk ? b0 + u : nblk - 1;  // used only when b0 + u < b1 <= nblk
-        bn[u] = feat[(size_t)bu * 64 + lane];
-    }
     if (lane < HW) {
         sC[wave][lane] = 0;
         sS[wave][lane] = 0;
@@ -338,72 +332,78 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     // the drains' view of the model table: the wave's first column, and its last hypothesis' slot
     const uint32_t hbc = hb < B ? hb : B - 1, hlast = B - 1 - hbc;
     const float *__restrict__ mw = models + hbc;
-    uint32_t qn = 0, qh = 0;
+    uint32_t qt = 0, qh = 0;  // ring tail and head, unwrapped (the ring's size divides 2^32): qt - qh entries wait
     const f32x16 zero = {};
-    wave_lds_sync();
-    for (uint32_t blk = b0; blk < b1; blk += U) {
-        half8 bf[U];
+    // The features as a buffer: a block's load takes the lane's byte offset (loop-invariant) and the
+    // block's byte offset as a scalar, so no vector address arithmetic is left in the loop (a pointer
+    // form keeps a 64-bit per-lane base and adds the block to it).  Reads past the last block would
+    // return zeros; none is issued.
+    const __amdgpu_buffer_rsrc_t fr =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<half8 *>(feat), 0, (int)(nblk * 1024u), 0x00020000);
+    const uint32_t loff = lane * 16;
+    auto load = [&](uint32_t blk) -> half8 {
+        return __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(fr, loff, blk * 1024u, 0));
+    };
+    // One 32-point block: its NA MFMAs, the refill of its feature registers for two blocks on (issued
+    // behind the MFMAs that read them), the tests, the append of the kept pairs.
+    auto block = [&](half8 &bf, const uint32_t blk) {
+        f32x16 acc[NA];
 #pragma unroll
-        for (int u = 0; u < U; u++) {
-            bf[u] = bn[u];
-            if (blk + U + u < b1) bn[u] = feat[(size_t)(blk + U + u) * 64 + lane];
-        }
-        f32x16 acc[U][NA];
+        for (int a = 0; a < NA; a++) acc[a] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[a], bf, zero, 0, 0, 0);
+        if (blk + 2 < b1) bf = load(blk + 2);
+        uint64_t msk[NA][5], any = 0;
+        bool keep[NA][5];
 #pragma unroll
-        for (int u = 0; u < U; u++)
+        for (int a = 0; a < NA; a++)
 #pragma unroll
-            for (int a = 0; a < NA; a++) acc[u][a] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[a], bf[u], zero, 0, 0, 0);
-        uint64_t msk[U][NA][5], any = 0;
-        bool keep[U][NA][5];
-#pragma unroll
-        for (int u = 0; u < U; u++)
+            for (int j = 0; j < 5; j++) {
+                // keep iff |ex| <= R and |ey| <= R, R = |zr| + F: two compares with |.| source
+                // modifiers (a max would first canonicalise both operands in IEEE mode).  The lane's
+                // own predicate stays beside the ballot (the same lane mask): the append runs under
+                // it as its exec mask.
+                const float R = fabsf(acc[a][3 * j + 2]) + F[a][j];
+                const bool kx = fabsf(acc[a][3 * j]) <= R, ky = fabsf(acc[a][3 * j + 1]) <= R;
+                keep[a][j] = kx && ky;
+                // (a ballot of each compare: a ballot of the combined predicate costs two more VALU)
+                msk[a][j] = __builtin_amdgcn_ballot_w64(kx) & __builtin_amdgcn_ballot_w64(ky);
+                any |= msk[a][j];
+            }
+        if (__builtin_expect(any != 0, 0)) {  // append the kept pairs, draining full groups of 64 per block
+            // the entry of slot 10 a + 5 hf + j: the lane's part once per block, (10 a + j) << 25 a literal
+            const uint32_t ent = ((5u * hf) << 25) | (blk * 32 + (lane & 31));
 #pragma unroll
             for (int a = 0; a < NA; a++)
 #pragma unroll
                 for (int j = 0; j < 5; j++) {
-                    // keep iff |ex| <= R and |ey| <= R, R = |zr| + F: two compares with |.| source
-                    // modifiers (a max would first canonicalise both operands in IEEE mode); a block
-                    // past the chunk's end keeps nothing.  The lane's own predicate stays beside the
-                    // ballot (the same lane mask): the append runs under it as its exec mask.
-                    const float R = fabsf(acc[u][a][3 * j + 2]) + F[a][j];
-                    const bool live = blk + u < b1, kx = fabsf(acc[u][a][3 * j]) <= R,
-                               ky = fabsf(acc[u][a][3 * j + 1]) <= R;
-                    keep[u][a][j] = live && kx && ky;
-                    // (a ballot of each compare: a ballot of the combined predicate costs two more VALU)
-                    msk[u][a][j] = live ? __builtin_amdgcn_ballot_w64(kx) & __builtin_amdgcn_ballot_w64(ky) : 0;
-                    any |= msk[u][a][j];
-                }
-        if (__builtin_expect(any != 0, 0)) {  // append the kept pairs, draining full groups of 64 per block
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                // the entry of slot 10 a + 5 hf + j: the lane's part once per block, (10 a + j) << 25 a literal
-                const uint32_t ent = ((5u * hf) << 25) | ((blk + u) * 32 + (lane & 31));
-#pragma unroll
-                for (int a = 0; a < NA; a++)
-#pragma unroll
-                    for (int j = 0; j < 5; j++) {
-                        const uint64_t mk = msk[u][a][j];
-                        if (!mk) continue;  // (uniform: an empty mask costs a scalar compare and a branch)
-                        if (keep[u][a][j]) {  // position = ring tail + kept lanes below (the tail seeds the count)
-                            const uint32_t qi = __builtin_amdgcn_mbcnt_hi(
-                                (uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, qh + qn));
-                            sQ[wave][qi & (Q - 1)] = ent + ((uint32_t)(10 * a + j) << 25);
-                        }
-                        qn += (uint32_t)__builtin_popcountll(mk);
+                    const uint64_t mk = msk[a][j];
+                    if (!mk) continue;  // (uniform: an empty mask costs a scalar compare and a branch)
+                    if (keep[a][j]) {  // position = ring tail + kept lanes below (the tail seeds the count)
+                        const uint32_t qi =
+                            __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, qt));
+                        sQ[wave][qi & (Q - 1)] = ent + ((uint32_t)(10 * a + j) << 25);
                     }
-                while (qn >= 64) {
-                    h16_drain<Q>(64, qh, sQ[wave], mw, B, hlast, sC[wave], sS[wave], pts, T, thr, fxs);
-                    qh = (qh + 64) & (Q - 1);
-                    qn -= 64;
+                    qt += (uint32_t)__builtin_popcountll(mk);
                 }
+            while (qt - qh >= 64) {
+                h16_drain<Q>(64, qh, sQ[wave], mw, B, hlast, sC[wave], sS[wave], pts, T, thr, fxs);
+                qh += 64;
             }
         }
+    };
+    // Two blocks per trip, one after the other, each from its own feature registers: no copy from a
+    // prefetch register into the MFMA operand and half the loop control per block; at most NA
+    // accumulator tiles live (not round 5's two-block form, which issued both blocks' MFMAs first).
+    // The first loads are unconditional at a clamped block (used only when the block is below b1 <= nblk).
+    half8 fa = load(b0 < nblk ? b0 : nblk - 1), fb = load(b0 + 1 < nblk ? b0 + 1 : nblk - 1);
+    wave_lds_sync();
+    for (uint32_t blk = b0; blk < b1; blk += 2) {
+        block(fa, blk);
+        if (blk + 1 < b1) block(fb, blk + 1);
     }
-    while (qn) {
-        const uint32_t d = qn < 64 ? qn : 64;
+    while (qt != qh) {
+        const uint32_t d = qt - qh < 64 ? qt - qh : 64;
         h16_drain<Q>(d, qh, sQ[wave], mw, B, hlast, sC[wave], sS[wave], pts, T, thr, fxs);
-        qh = (qh + d) & (Q - 1);
-        qn -= d;
+        qh += d;
     }
     wave_lds_sync();
     if (lane < HW && hb + lane < B) {
@@ -450,7 +450,6 @@ hipError_t launch_score_h16(hipStream_t st, const void *feat, const float4 *pts,
     const double fxs = ldexp(1.0, fx);
     unsigned long long *sp = static_cast<unsigned long long *>(part);  // 8-byte words first (alignment)
     uint32_t *cp = reinterpret_cast<uint32_t *>(sp + (size_t)chunks * B);
-    static const int uu = getenv("USAC_H16_U") ? atoi(getenv("USAC_H16_U")) : 1;  // blocks per iteration
     // min waves per SIMD: 8 (64 VGPRs, no spills) -- same-box cfg2 559-570 vs 551-555 M hyp/s at 7
     static const int wpe = getenv("USAC_H16_WPE") ? atoi(getenv("USAC_H16_WPE")) : 8;
 #define H16(NA_, U_, W_)                                                                                            \
@@ -459,8 +458,6 @@ hipError_t launch_score_h16(hipStream_t st, const void *feat, const float4 *pts,
                        fxs, cp, sp)
     if (na == 4)
         H16(4, 1, 1);
-    else if (uu == 2)
-        H16(2, 2, 1);
     else if (wpe == 8)
         H16(2, 1, 8);
     else
