@@ -322,7 +322,8 @@ struct usac_ctx {
     void *perm_zeroed = nullptr;  // the perm block whose region counters were zeroed
     DevBuf hf_part;         // fast-kernel partials of a point range split over workgroups
     float rec_thr = -1.f;   // threshold the record bands were built for
-    float4 ext = {0, 0, 0, 0};  // dataset box: max |x1|, |y1|, |x2|, |y2| (fast-kernel bounds)
+    float4 ext = {0, 0, 0, 0};  // dataset box: max |x1|, |y1|, |x2|, |y2| over the finite rows (fast-kernel bounds)
+    float4 grid_ext = {0, 0, 0, 0};  // the same over every row, infinite coordinates included (ensure_grid)
     // the matrix-core prefilter scorer of homographies (kernels_h16.hip): dataset constants, fp16
     // point features (built on first use), per-batch rows / slacks and chunk partials; h16 = 1 when
     // usable (USAC_H16=0 turns it off: the lanes-over-hypotheses k_score_hf then scores every batch)
@@ -574,7 +575,7 @@ int ensure_grid(usac_ctx *c, int cs) {
     if (c->grid_cs == cs) return USAC_OK;
     if (c->cols != 4) return fail(c, USAC_ERR_ARG, "grid neighbours need 4-column points (SURVEY Q17)");
     if (cs <= 0) return fail(c, USAC_ERR_ARG, "grid cell_size must be > 0");
-    const float e[4] = {c->ext.x, c->ext.y, c->ext.z, c->ext.w};
+    const float e[4] = {c->grid_ext.x, c->grid_ext.y, c->grid_ext.z, c->grid_ext.w};
     int lo[4], bits[4];
     bool packable = true;
     for (int j = 0; j < 4; j++) {
@@ -1924,14 +1925,27 @@ int usac_create(usac_ctx **out, int device, int estimator, const float *pts, uin
         e = c->pts.reserve(sizeof(float) * (size_t)n * cols);
         if (e != hipSuccess) { rc = fail(c, USAC_ERR_HIP, "hipMalloc points failed"); break; }
         e = hipMemcpy(c->pts.p, pts, sizeof(float) * (size_t)n * cols, hipMemcpyHostToDevice);
-        if (cols == 4) {  // dataset box for the score kernel's error bounds (NaN rows skipped)
-            float mx[4] = {0, 0, 0, 0};
-            for (uint32_t i = 0; i < n; i++)
+        if (cols == 4) {
+            // The dataset box of the score kernels' error bounds: over the rows whose four coordinates are
+            // finite.  A row with a NaN or an infinite coordinate is never an inlier of the reference and
+            // needs no bound (DESIGN.md "Guard band"); one infinite coordinate in the box would switch off
+            // stage A and both matrix-core prefilters for the whole set.  The grid's box keeps every
+            // coordinate that compares (NaN does not): an infinite one sends it to the host build.
+            float mx[4] = {0, 0, 0, 0}, ga[4] = {0, 0, 0, 0};
+            for (uint32_t i = 0; i < n; i++) {
+                float v[4];
+                bool fin = true;
                 for (int k = 0; k < 4; k++) {
-                    const float v = fabsf(pts[4 * (size_t)i + k]);
-                    if (v > mx[k]) mx[k] = v;
+                    v[k] = fabsf(pts[4 * (size_t)i + k]);
+                    if (v[k] > ga[k]) ga[k] = v[k];
+                    fin = fin && std::isfinite(v[k]);
                 }
+                if (fin)
+                    for (int k = 0; k < 4; k++)
+                        if (v[k] > mx[k]) mx[k] = v[k];
+            }
             c->ext = make_float4(mx[0], mx[1], mx[2], mx[3]);
+            c->grid_ext = make_float4(ga[0], ga[1], ga[2], ga[3]);
             const char *h16env = getenv("USAC_H16");
             c->h16 = !h16env || atoi(h16env) != 0 ? 1 : 0;
             const char *e16env = getenv("USAC_E16");  // USAC_E16=0: k_score_f2 for every essential batch

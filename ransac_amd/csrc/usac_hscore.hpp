@@ -83,9 +83,10 @@ __device__ __forceinline__ bool stage_a_reject(const HModel &M, float x1, float 
 }
 
 // Stage B -- both directions with the reference's projection order, v_rcp, v_sqrt, and the
-// guard-band test; lanes inside the band / non-finite / (EXACT_SUM) inliers re-evaluate the
-// exact reference expression.  Adds to (cnt, sum): the exact err (EXACT_SUM, so Σ is the
-// reference's sequential fp32 sum) or S ~= 2 err (throughput mode, halved at the end).
+// guard-band test; lanes inside the band / non-finite / below the normal range (a squared distance
+// or a reciprocal under 2^-126) / (EXACT_SUM) inliers re-evaluate the exact reference expression.
+// Adds to (cnt, sum): the exact err (EXACT_SUM, so Σ is the reference's sequential fp32 sum) or
+// S ~= 2 err (throughput mode, halved at the end).
 template <bool EXACT_SUM>
 __device__ __forceinline__ void stage_b(const HModel &M, float x1, float y1, float x2, float y2, float band, float T,
                                         float thr, int &cnt, float &sum) {
@@ -105,7 +106,11 @@ __device__ __forceinline__ void stage_b(const HModel &M, float x1, float y1, flo
     const float d1 = __builtin_fmaf(dx1, dx1, dy1 * dy1);
     const float S = __builtin_amdgcn_sqrtf(d2) + __builtin_amdgcn_sqrtf(d1);
     const float diff = S - T;
-    const bool sure = (fabsf(diff) > band) & (S < INFINITY);
+    // v_sqrt_f32 reads a denormal argument as 0 and v_rcp_f32 returns 0 where 1 / Z is denormal: the band
+    // covers neither (its terms are relative), so a squared distance or a reciprocal below 2^-126 is not
+    // "sure" (a distance below 2^-63, |Z| >= 2^126; the minimum skips a NaN, which S carries anyway)
+    const float low = __builtin_fminf(__builtin_fminf(d2, d1), __builtin_fminf(fabsf(r2), fabsf(r1)));
+    const bool sure = (fabsf(diff) > band) & (S < INFINITY) & (low >= 1.17549435e-38f);
     bool inl = sure & (diff < 0.f);
     float add = S;
     if (EXACT_SUM ? (!sure || inl) : !sure) {

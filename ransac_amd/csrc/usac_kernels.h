@@ -64,7 +64,8 @@ hipError_t launch_score_h(hipStream_t st, int chunks, const float4 *pts, uint32_
                           float thr, int32_t *counts, float *sums);
 
 hipError_t launch_prepare_rec(hipStream_t st, const float4 *pts, uint32_t n, float thr, float4 *rec);
-// ext = dataset box {max|x1|, max|y1|, max|x2|, max|y2|} (stage-A error bounds)
+// ext = dataset box {max|x1|, max|y1|, max|x2|, max|y2|} over the rows with four finite coordinates
+// (stage-A error bounds; a non-finite row needs none: the reference never counts it)
 // perm (nullable, B + 2 uint32): hypothesis pre-sort scratch (k_presort_h)
 // ysplit > 1 (throughput mode): every 64-hypothesis tile's points over chunks x ysplit waves in
 // ysplit workgroups, partials in yscratch (8 B x ysplit x B) added in order by a second launch
