@@ -61,7 +61,12 @@
  *                                  usac_lo_draw / usac_multi_lo exposing its parts;
  *                                  ABI 19: usac_multi_run_sprt, SPRT verification of every slot on the
  *                                  device with one test per problem and round, with usac_multi_sprt_setup /
- *                                  usac_multi_hypothesize_score_sprt / usac_multi_sprt_update exposing its parts
+ *                                  usac_multi_hypothesize_score_sprt / usac_multi_sprt_update exposing its parts;
+ *                                  ABI 20: usac_multi_run_napsac, the grid NAPSAC sampler per problem over
+ *                                  grid neighbours built for all problems in one launch (one workgroup per
+ *                                  problem), optionally with LO and the polish, with usac_multi_grid /
+ *                                  usac_multi_draw_samples_napsac / usac_multi_hypothesize_score_napsac
+ *                                  exposing its parts
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -76,7 +81,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 19
+#define USAC_ABI_VERSION 20
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -802,6 +807,45 @@ int usac_multi_sprt_update(int estimator, uint32_t n_points, uint32_t m, uint32_
 int usac_multi_run_sprt(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
                         usac_multi_sprt_output *sprt, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
                         uint8_t *mask);
+
+/* ---- NAPSAC for multi-problem batches (ABI 20) ---------------------------------------- */
+/* usac_grid_neighbors for every problem: the CSR of NearestNeighbors::getGridNearestNeighbors over each
+ * problem's points for cell_size (> 0), built in one launch (one workgroup per problem; a problem of more
+ * than 4000 points, or with a coordinate x for which !(|x| / cell_size < 1e9), is built on the host --
+ * the same CSR) and kept in the context until another size is asked for.  Indices are local to each
+ * problem and the arrays are problem-local at the points' offsets: cell, rank, members, eligible (points
+ * with >= m neighbours, ascending; n_eligible[p] of them): N_total values each, problem p's at
+ * offsets[p]; start: N_total + P values, problem p's n_cells[p] + 1 entries at offsets[p] + p.  Values
+ * past a problem's n_eligible / n_cells + 1 entries are unspecified.  Every output is nullable. */
+int usac_multi_grid(usac_multi *mc, int cell_size, uint32_t *n_cells, uint32_t *cell, uint32_t *rank,
+                    uint32_t *start, int32_t *members, int32_t *eligible, uint32_t *n_eligible);
+
+/* usac_multi_draw_samples with the NAPSAC device sampler over the grid of cell_size: for each listed
+ * problem what a usac_ctx over its points draws after usac_set_cell_size(cell_size) and
+ * usac_set_device_sampler(USAC_SAMPLER_NAPSAC) -- the initial point uniform over the eligible points,
+ * m - 1 consecutive grid neighbours from a random phase; uniform samples for a problem without an
+ * eligible point.  out: n_problems x R x m indices local to each problem. */
+int usac_multi_draw_samples_napsac(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t R,
+                                   const uint64_t *seeds, uint64_t first_hyp, int cell_size, int32_t *out);
+
+/* usac_multi_hypothesize_score with that sampler (seeds required; no host samples). */
+int usac_multi_hypothesize_score_napsac(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t R,
+                                        const uint64_t *seeds, uint64_t first_hyp, float thr, int dlt_mode,
+                                        int cell_size, int32_t *counts, float *sums, usac_record *best);
+
+/* usac_multi_run with the NAPSAC sampler (params->sampler = USAC_SAMPLER_NAPSAC, ->neighbors =
+ * USAC_NEIGHBORS_GRID, ->cell_size > 0) and the standard termination criterion, optionally with LO
+ * (params->lo = USAC_LO_INITLORSC / _INITFLORSC, as usac_multi_run_lo: the LO draws do not depend on the
+ * main sampler) and the polish.  Deviations from the glibc-stream Ransac::run with NAPSAC: the device
+ * stream's random phase in place of the reference's persistent per-point cursor (as the single context's
+ * throughput sampler), batch-granular termination, and those of usac_multi_run / usac_multi_run_lo.
+ * USAC_ERR_ARG for another sampler, cell_size <= 0, a bad batch or dlt_mode, the LO parameters
+ * usac_multi_run_lo refuses, NULL mc, params or out; USAC_ERR_UNSUPPORTED for ->neighbors other than
+ * USAC_NEIGHBORS_GRID (KNN NAPSAC is not built), params->sprt, USAC_LO_GC -- all before any device call
+ * (the grid build included).  out / pol / mask as usac_multi_run_prosac's; lo (nullable): P LO states,
+ * written only with LO. */
+int usac_multi_run_napsac(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
+                          usac_multi_lo_output *lo, usac_multi_polish_output *pol, uint8_t *mask);
 
 /* ---- self-test hooks (ABI 13) ------------------------------------------------------- */
 /* The essential 5-point solver's root step alone (five_points.cpp:139-157: rpoly_ak1's real zeros

@@ -739,6 +739,57 @@ public:
         return out;
     }
 
+    // one problem's grid neighbours: the CSR of Context's grid neighbours over its points (cells in order of
+    // first appearance, members ascending) and the points with >= sampleSize() neighbours; local indices
+    struct GridCsr {
+        std::vector<uint32_t> cell, rank, start;
+        std::vector<int32_t> members, eligible;
+    };
+
+    // usac_multi_grid: every problem's grid neighbours for cell_size, built in one launch and kept in the
+    // context until another size is asked for
+    std::vector<GridCsr> gridNeighbors(int cell_size) const {
+        const unsigned int P = problems();
+        const size_t N = offsets_[P];
+        std::vector<uint32_t> nc(P), ne(P), cell(N), rank(N), start(N + P);
+        std::vector<int32_t> members(N), eligible(N);
+        check(usac_multi_grid(mc_, cell_size, nc.data(), cell.data(), rank.data(), start.data(), members.data(),
+                              eligible.data(), ne.data()),
+              "MultiContext::gridNeighbors");
+        std::vector<GridCsr> out(P);
+        for (unsigned int p = 0; p < P; p++) {
+            const size_t a = offsets_[p], b = offsets_[p + 1];
+            out[p].cell.assign(cell.begin() + a, cell.begin() + b);
+            out[p].rank.assign(rank.begin() + a, rank.begin() + b);
+            out[p].start.assign(start.begin() + a + p, start.begin() + a + p + nc[p] + 1);
+            out[p].members.assign(members.begin() + a, members.begin() + b);
+            out[p].eligible.assign(eligible.begin() + a, eligible.begin() + a + ne[p]);
+        }
+        return out;
+    }
+
+    // one problem's result of runNapsac: run()'s output and, with LO, the LO counters (empty otherwise)
+    struct Napsac {
+        std::vector<usac_multi_output> run;
+        std::vector<usac_multi_lo_output> lo;
+    };
+
+    // usac_multi_run_napsac: run() with the grid NAPSAC sampler per problem (model.sampler = Napsac,
+    // model.neighborsType = Grid, model.cell_size) and, with model.lo = InItLORsc / InItFLORsc, runLo()'s LO
+    Napsac runNapsac(const Model &model, const std::vector<uint64_t> &seeds = std::vector<uint64_t>()) const {
+        usac_params p = model.params();
+        p.seed = model.seed;
+        const unsigned int P = problems();
+        if (!seeds.empty() && seeds.size() != P) throw Error(USAC_ERR_ARG, "runNapsac: one seed per problem");
+        Napsac out;
+        out.run.resize(P);
+        if (p.lo != USAC_LO_NONE) out.lo.resize(P);
+        check(usac_multi_run_napsac(mc_, &p, seeds.empty() ? nullptr : seeds.data(), out.run.data(),
+                                    out.lo.empty() ? nullptr : out.lo.data(), nullptr, nullptr),
+              "MultiContext::runNapsac");
+        return out;
+    }
+
 private:
     void splitMask(const std::vector<uint8_t> &mask, std::vector<std::vector<int> > *out) const {
         const unsigned int P = problems();

@@ -200,6 +200,7 @@ ABI_SYMBOLS = [
     "usac_prosac_schedule", "usac_multi_draw_samples", "usac_multi_run_prosac", "usac_multi_prosac_scan",
     "usac_lo_draw", "usac_multi_lo", "usac_multi_run_lo",
     "usac_multi_sprt_setup", "usac_multi_hypothesize_score_sprt", "usac_multi_sprt_update", "usac_multi_run_sprt",
+    "usac_multi_grid", "usac_multi_draw_samples_napsac", "usac_multi_hypothesize_score_napsac", "usac_multi_run_napsac",
 ]
 
 
@@ -330,6 +331,14 @@ def lib():
                                    [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]),
         "usac_multi_run_sprt": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
                                                _P(_MultiSprtOutput), _P(_MultiProsacOutput), _P(_MultiPolishOutput), u8p]),
+        "usac_multi_grid": (ctypes.c_int, [_vp, ctypes.c_int, u32p, u32p, u32p, u32p, i32p, i32p, u32p]),
+        "usac_multi_draw_samples_napsac": (ctypes.c_int, [_vp, u32p, ctypes.c_uint32, ctypes.c_uint32,
+                                                          _P(ctypes.c_uint64), ctypes.c_uint64, ctypes.c_int, i32p]),
+        "usac_multi_hypothesize_score_napsac": (ctypes.c_int, [_vp, u32p, ctypes.c_uint32, ctypes.c_uint32,
+                                                               _P(ctypes.c_uint64), ctypes.c_uint64, ctypes.c_float,
+                                                               ctypes.c_int, ctypes.c_int, i32p, f32p, _P(Record)]),
+        "usac_multi_run_napsac": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
+                                                 _P(_MultiLoOutput), _P(_MultiPolishOutput), u8p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -869,7 +878,7 @@ class MultiContext:
     def _run(self, name, model_or_params, seeds, polish, own=None, prosac=None):
         """What the run methods share: usac_multi_<name>(handle, params, seeds, out[, own's array]
         [, PROSAC's array][, polish results, mask]) and its list of P result dicts.  own: (key,
-        structure) of the method's own per-problem output.  prosac: the call takes PROSAC's array, and
+        structure[, wanted]) of the method's own per-problem output (not wanted: NULL is passed).  prosac: the call takes PROSAC's array, and
         its keys are returned "always" or under the PROSAC "sampler" only.  The polish arguments go to
         every function but usac_multi_run."""
         p = self._run_params(model_or_params)
@@ -877,18 +886,18 @@ class MultiContext:
         if sd is not None and sd.size != self.P:
             raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
         out = (_MultiOutput * self.P)()
-        ex = (own[1] * self.P)() if own else None
+        ex = (own[1] * self.P)() if own and (len(own) < 3 or own[2]) else None  # own[2] False: a NULL argument
         pro = (_MultiProsacOutput * self.P)() if prosac else None
         pol = (_MultiPolishOutput * self.P)() if polish else None
         mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if polish else None
-        args = [a for a in (ex, pro) if a is not None]
+        args = ([ex] if own else []) + ([pro] if prosac else [])
         if name != "run":
             args += [pol, _ptr(mask, ctypes.c_uint8)]
         self._check(getattr(lib(), "usac_multi_" + name)(self._h, ctypes.byref(p), _ptr(sd, ctypes.c_uint64), out, *args),
                     "multi_" + name)
         res = [{"best": o.best.as_dict(), "hypotheses": int(o.hypotheses), "rounds": int(o.rounds),
                 "bound": int(o.bound), "status": int(o.status)} for o in out]
-        if own:
+        if ex is not None:
             for r, q in zip(res, ex):
                 r[own[0]] = q.as_dict()
         if prosac == "always" or (prosac and p.sampler == int(SAMPLER.Prosac)):
@@ -1041,6 +1050,67 @@ class MultiContext:
         points_tested); with PROSAC also run_prosac()'s keys; polish=True adds "polished" and "inliers"
         as run() does."""
         return self._run("run_sprt", model_or_params, seeds, polish, own=("sprt", _MultiSprtOutput), prosac="sampler")
+
+    def grid_neighbors(self, cell_size):
+        """usac_multi_grid: Context.grid_neighbors for every problem, built in one launch and kept for
+        cell_size -> a list of P dicts of the problem's CSR: cell, rank, start (n_cells + 1), members, and
+        eligible (points with >= m neighbours); indices local to the problem."""
+        N, P = int(self.offsets[-1]), self.P
+        nc, ne = np.zeros(P, dtype=np.uint32), np.zeros(P, dtype=np.uint32)
+        cell, rank = np.zeros(N, dtype=np.uint32), np.zeros(N, dtype=np.uint32)
+        start = np.zeros(N + P, dtype=np.uint32)
+        members, elig = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32)
+        u32, i32 = ctypes.c_uint32, ctypes.c_int32
+        self._check(lib().usac_multi_grid(self._h, int(cell_size), _ptr(nc, u32), _ptr(cell, u32), _ptr(rank, u32),
+                                          _ptr(start, u32), _ptr(members, i32), _ptr(elig, i32), _ptr(ne, u32)),
+                    "multi_grid")
+        out = []
+        for p in range(P):
+            a, b = int(self.offsets[p]), int(self.offsets[p + 1])
+            out.append({"cell": cell[a:b].copy(), "rank": rank[a:b].copy(),
+                        "start": start[a + p:a + p + int(nc[p]) + 1].copy(), "members": members[a:b].copy(),
+                        "eligible": elig[a:a + int(ne[p])].copy()})
+        return out
+
+    def draw_samples_napsac(self, R, seeds, cell_size, first_hyp=0, problems=None):
+        """usac_multi_draw_samples_napsac (for tests): the samples a NAPSAC round's solve kernels draw over
+        the grid of cell_size, A x R x m local indices -- per problem Context.draw_samples after
+        set_cell_size(cell_size) and set_device_sampler(SAMPLER.Napsac)."""
+        A = self.P if problems is None else len(problems)
+        pr = None if problems is None else np.ascontiguousarray(problems, dtype=np.uint32)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd.size != A:
+            raise ValueError("seeds: one per listed problem (%d), got %d" % (A, sd.size))
+        out = np.zeros((A, R, self.m), dtype=np.int32)
+        self._check(lib().usac_multi_draw_samples_napsac(self._h, _ptr(pr, ctypes.c_uint32), A, R,
+                                                         _ptr(sd, ctypes.c_uint64), first_hyp, int(cell_size),
+                                                         _ptr(out, ctypes.c_int32)), "multi_draw_samples_napsac")
+        return out
+
+    def hypothesize_score_napsac(self, R, seeds, cell_size, first_hyp=0, thr=2.0, problems=None, per_hypothesis=True):
+        """usac_multi_hypothesize_score_napsac: hypothesize_score() with the NAPSAC device sampler over the
+        grid of cell_size (seeds required).  Returns what hypothesize_score() returns."""
+        A = self.P if problems is None else len(problems)
+        pr = None if problems is None else np.ascontiguousarray(problems, dtype=np.uint32)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd.size != A:
+            raise ValueError("seeds: one per listed problem (%d), got %d" % (A, sd.size))
+        c = np.zeros((A, R * self.spk), dtype=np.int32) if per_hypothesis else None
+        s = np.zeros((A, R * self.spk), dtype=np.float32) if per_hypothesis else None
+        best = (Record * max(A, 1))()
+        self._check(lib().usac_multi_hypothesize_score_napsac(
+            self._h, _ptr(pr, ctypes.c_uint32), A, R, _ptr(sd, ctypes.c_uint64), first_hyp, ctypes.c_float(thr),
+            int(self.dlt_mode), int(cell_size), _ptr(c, ctypes.c_int32), _ptr(s, ctypes.c_float), best),
+            "multi_hypothesize_score_napsac")
+        return c, s, [best[i].as_dict() for i in range(A)]
+
+    def run_napsac(self, model_or_params, seeds=None, polish=False):
+        """usac_multi_run_napsac: run() with the grid NAPSAC sampler per problem (model.sampler Napsac,
+        neighbours Grid, model.cell_size) and the standard termination criterion; model.lo = InItLORsc /
+        InItFLORsc adds run_lo()'s LO.  Returns run()'s dicts, plus "lo" when the model asks for LO;
+        polish=True adds "polished" and "inliers" as run() does."""
+        p = self._run_params(model_or_params)
+        return self._run("run_napsac", p, seeds, polish, own=("lo", _MultiLoOutput, p.lo != int(LocOpt.NullLO)))
 
     def inliers(self, models, thr):
         """Ascending inlier indices (local to each problem) of each problem's model (P x 9), by the

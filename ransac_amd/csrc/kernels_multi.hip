@@ -8,6 +8,7 @@
 //   items    : A x MultiItem, the launch's active list (problem id, its sampler seed and, for the
 //              PROSAC sampler, the round's clock and termination length);
 //   growth   : PROSAC only, N_total uint32: problem p's growth function at growth + offsets[p];
+//   grid     : NAPSAC only, the problems' grid neighbours (MultiGrid, kernels_multi_grid.hip);
 //   models   : per-launch SoA slab over the A * R hypotheses of the launch, hypothesis h of
 //              active entry a at g = a * R + h -- H: [18][A R] (H then H^-1), F: [9][3 A R] with
 //              slot 3 g + j = the j-th valid model of the sample (seven_points.cpp root order);
@@ -17,7 +18,8 @@
 // Every per-hypothesis step is the single-problem path's device math (usac_device.hpp), so a
 // problem's models, counts and sums equal those of a usac_ctx over its points bit for bit: the
 // sample of (seed, global hypothesis index) by draw_sample over n_p (or, in the PROSAC
-// instantiations, by multi_sample's closed-form PROSAC rule on the same stream), the thin-QR DLT with the
+// instantiations, by stream_sample's closed-form PROSAC rule on the same stream; in the NAPSAC ones, by
+// draw_sample's NAPSAC branch over the problem's grid), the thin-QR DLT with the
 // row-Jacobi fall-back (or the 7-point chain), and the ONE-CHUNK score: each lane walks its
 // problem's points in order, so Σ is the reference's sequential fp32 sum.  R is a multiple of
 // 64: a wave never spans two problems, so the problem id, the point base and every point are
@@ -39,6 +41,18 @@ __device__ __forceinline__ DevSampler uniform_sampler(uint64_t seed) {
     return ds;
 }
 
+// The sampler of an instantiation and the kernels' last argument under it: the growth functions
+// (PROSAC; unused by the uniform sampler) or the problems' grids (NAPSAC, kernels_multi_grid.hip).
+enum : int { kUniform = 0, kProsac = 1, kNapsac = 2 };
+template <int SAMPLER>
+struct SamplerArg {
+    using type = const uint32_t *__restrict__;
+};
+template <>
+struct SamplerArg<kNapsac> {
+    using type = MultiGrid;
+};
+
 // Lane h's sample of a round.  Uniform: draw_sample over n_p.  PROSAC (usac_prosac.hpp's closed form
 // over the problem's growth function g, the item's clock T and termination length L): t = T + h,
 //   t > T_N        : M distinct indices of [0, n)        (the reference past its growth table)
@@ -47,9 +61,13 @@ __device__ __forceinline__ DevSampler uniform_sampler(uint64_t seed) {
 //   otherwise      : M - 1 distinct indices of [0, s(t) - 2] and point s(t) - 1
 // from the (seed, global hypothesis index) stream either way: the first M - 1 draws are
 // draw_unique's over the branch's range, the last one is its M-th step or the fixed point.
+// NAPSAC: draw_sample's NAPSAC branch over the problem's slices of the grid CSR (block-uniform bases):
+// the initial point uniform over the eligible points, M - 1 consecutive neighbours from a random
+// phase, uniform samples for a problem without an eligible point -- what a usac_ctx over the
+// problem's points draws after usac_set_cell_size and usac_set_device_sampler(NAPSAC).
 template <int M, bool PROSAC>
-__device__ __forceinline__ void multi_sample(const MultiItem &it, const uint32_t *__restrict__ g, uint32_t n,
-                                             uint64_t hyp, uint32_t h, int32_t (&s)[M]) {
+__device__ __forceinline__ void stream_sample(const MultiItem &it, const uint32_t *__restrict__ g, uint32_t n,
+                                              uint64_t hyp, uint32_t h, int32_t (&s)[M]) {
     if constexpr (!PROSAC) {
         draw_sample<M>(uniform_sampler(it.seed), hyp, n, s);
     } else {
@@ -84,6 +102,24 @@ __device__ __forceinline__ void multi_sample(const MultiItem &it, const uint32_t
     }
 }
 
+template <int M, int SAMPLER>
+__device__ __forceinline__ void multi_sample(const MultiItem &it, const typename SamplerArg<SAMPLER>::type &aux,
+                                             uint32_t base, uint32_t n, uint64_t hyp, uint32_t h, int32_t (&s)[M]) {
+    if constexpr (SAMPLER == kNapsac) {
+        DevSampler ds{};
+        ds.seed = it.seed;
+        ds.nap_n_eligible = aux.n_eligible[it.problem];
+        ds.nap_cell = aux.cell + base;
+        ds.nap_rank = aux.rank + base;
+        ds.nap_start = aux.start + base + it.problem;
+        ds.nap_members = aux.members + base;
+        ds.nap_eligible = aux.eligible + base;
+        draw_sample<M>(ds, hyp, n, s);
+    } else {
+        stream_sample<M, SAMPLER == kProsac>(it, aux + base, n, hyp, h, s);
+    }
+}
+
 // as kernels.hip store_h: H = v / v[8] in fp64, one cast, H^-1 by inv3x3
 __device__ __forceinline__ void multi_store_h(float *__restrict__ models, size_t stride, size_t g, const double *v) {
     float H[9], Hi[9];
@@ -112,13 +148,13 @@ __device__ __forceinline__ void multi_dlt_system(const float4 *__restrict__ pts,
 // grid (R / 64, A).  Thin mode: dlt4_thin_qr, and the lanes it refuses solve the rebuilt system by
 // row_jacobi + pick_vector in the same kernel (what k_solve_h4_jac does for k_solve_h4's list);
 // nullspace mode: the row Jacobi for every lane.
-template <bool NULLSPACE, bool PROSAC>
+template <bool NULLSPACE, int SAMPLER>
 __global__ __launch_bounds__(64) void k_multi_solve_h4(const float4 *__restrict__ pts_all,
                                                        const uint32_t *__restrict__ offsets,
                                                        const MultiItem *__restrict__ items,
                                                        const int32_t *__restrict__ samples_in, uint32_t R,
                                                        uint64_t first_hyp, float *__restrict__ models,
-                                                       const uint32_t *__restrict__ growth) {
+                                                       const typename SamplerArg<SAMPLER>::type aux) {
     const uint32_t a = blockIdx.y;
     const MultiItem it = items[a];
     const uint32_t base = offsets[it.problem], n = offsets[it.problem + 1] - base;
@@ -130,7 +166,7 @@ __global__ __launch_bounds__(64) void k_multi_solve_h4(const float4 *__restrict_
 #pragma unroll
         for (int i = 0; i < 4; i++) s[i] = samples_in[4 * g + i];
     } else {
-        multi_sample<4, PROSAC>(it, growth + base, n, first_hyp + h, h, s);
+        multi_sample<4, SAMPLER>(it, aux, base, n, first_hyp + h, h, s);
     }
     double W[8][9];
     double v[9];
@@ -150,7 +186,7 @@ __global__ __launch_bounds__(64) void k_multi_solve_h4(const float4 *__restrict_
 // ------------------------------------------------------------------------ solve (F, 7-pt)
 // grid (R / 64, A): k_solve_f7's chain per lane, slots 3 g + j, the occupied slots appended to
 // the active entry's list (wave-aggregated atomic on list_n[a], zeroed by the launcher).
-template <bool PROSAC>
+template <int SAMPLER>
 __global__ __launch_bounds__(64) void k_multi_solve_f7(const float4 *__restrict__ pts_all,
                                                        const uint32_t *__restrict__ offsets,
                                                        const MultiItem *__restrict__ items,
@@ -158,7 +194,7 @@ __global__ __launch_bounds__(64) void k_multi_solve_f7(const float4 *__restrict_
                                                        uint64_t first_hyp, float *__restrict__ models,
                                                        int32_t *__restrict__ counts, float *__restrict__ sums,
                                                        uint32_t *__restrict__ list, uint32_t *__restrict__ list_n,
-                                                       const uint32_t *__restrict__ growth) {
+                                                       const typename SamplerArg<SAMPLER>::type aux) {
     const uint32_t a = blockIdx.y;
     const MultiItem it = items[a];
     const uint32_t base = offsets[it.problem], n = offsets[it.problem + 1] - base;
@@ -173,7 +209,7 @@ __global__ __launch_bounds__(64) void k_multi_solve_f7(const float4 *__restrict_
 #pragma unroll
             for (int i = 0; i < 7; i++) s[i] = samples_in[7 * g + i];
         } else {
-            multi_sample<7, PROSAC>(it, growth + base, n, first_hyp + h, h, s);
+            multi_sample<7, SAMPLER>(it, aux, base, n, first_hyp + h, h, s);
         }
         double W[7][9];
 #pragma unroll
@@ -414,13 +450,19 @@ __global__ __launch_bounds__(256) void k_multi_mask(const float4 *__restrict__ p
 
 // ------------------------------------------------------------------------ launchers
 hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
-    if (r.A == 0 || r.R == 0 || r.R % 64) return hipErrorInvalidValue;
+    if (r.A == 0 || r.R == 0 || r.R % 64 || (r.growth && r.grid)) return hipErrorInvalidValue;
     const dim3 grid(r.R / 64, r.A);
     if (r.estimator == USAC_HOMOGRAPHY) {
-        auto *solve = r.growth ? (r.nullspace ? k_multi_solve_h4<true, true> : k_multi_solve_h4<false, true>)
-                               : (r.nullspace ? k_multi_solve_h4<true, false> : k_multi_solve_h4<false, false>);
-        hipLaunchKernelGGL(solve, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R, r.first_hyp,
-                           r.models, r.growth);
+        if (r.grid) {
+            auto *solve = r.nullspace ? k_multi_solve_h4<true, kNapsac> : k_multi_solve_h4<false, kNapsac>;
+            hipLaunchKernelGGL(solve, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R, r.first_hyp,
+                               r.models, *r.grid);
+        } else {
+            auto *solve = r.growth ? (r.nullspace ? k_multi_solve_h4<true, kProsac> : k_multi_solve_h4<false, kProsac>)
+                                   : (r.nullspace ? k_multi_solve_h4<true, kUniform> : k_multi_solve_h4<false, kUniform>);
+            hipLaunchKernelGGL(solve, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R, r.first_hyp,
+                               r.models, r.growth);
+        }
         if (r.sprt) {
             const hipError_t e = launch_multi_sprt_score(st, r);
             if (e != hipSuccess) return e;
@@ -433,9 +475,14 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
     } else if (r.estimator == USAC_FUNDAMENTAL) {
         hipError_t e = hipMemsetAsync(r.list_n, 0, sizeof(uint32_t) * r.A, st);
         if (e != hipSuccess) return e;
-        auto *solve = r.growth ? k_multi_solve_f7<true> : k_multi_solve_f7<false>;
-        hipLaunchKernelGGL(solve, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R, r.first_hyp,
-                           r.models, r.counts, r.sums, r.list, r.list_n, r.growth);
+        if (r.grid) {
+            hipLaunchKernelGGL(k_multi_solve_f7<kNapsac>, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in,
+                               r.R, r.first_hyp, r.models, r.counts, r.sums, r.list, r.list_n, *r.grid);
+        } else {
+            auto *solve = r.growth ? k_multi_solve_f7<kProsac> : k_multi_solve_f7<kUniform>;
+            hipLaunchKernelGGL(solve, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.samples_in, r.R, r.first_hyp,
+                               r.models, r.counts, r.sums, r.list, r.list_n, r.growth);
+        }
         if (r.sprt) {
             e = launch_multi_sprt_score(st, r);
             if (e != hipSuccess) return e;
@@ -452,29 +499,34 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
 }
 
 // the samples alone: grid (R / 64, A), lane h of entry a writes its m indices
-template <int M, bool PROSAC>
+template <int M, int SAMPLER>
 __global__ __launch_bounds__(64) void k_multi_draw(const uint32_t *__restrict__ offsets,
                                                    const MultiItem *__restrict__ items, uint32_t R,
-                                                   uint64_t first_hyp, const uint32_t *__restrict__ growth,
+                                                   uint64_t first_hyp, const typename SamplerArg<SAMPLER>::type aux,
                                                    int32_t *__restrict__ out) {
     const uint32_t a = blockIdx.y;
     const MultiItem it = items[a];
     const uint32_t base = offsets[it.problem], n = offsets[it.problem + 1] - base;
     const uint32_t h = blockIdx.x * 64 + threadIdx.x;
     int32_t s[M];
-    multi_sample<M, PROSAC>(it, growth + base, n, first_hyp + h, h, s);
+    multi_sample<M, SAMPLER>(it, aux, base, n, first_hyp + h, h, s);
     int32_t *__restrict__ o = out + ((size_t)a * R + h) * M;
 #pragma unroll
     for (int i = 0; i < M; i++) o[i] = s[i];
 }
 
 hipError_t launch_multi_draw(hipStream_t st, int estimator, const uint32_t *offsets, const MultiItem *items, uint32_t A,
-                             uint32_t R, uint64_t first_hyp, const uint32_t *growth, int32_t *out) {
-    if (A == 0 || R == 0 || R % 64) return hipErrorInvalidValue;
+                             uint32_t R, uint64_t first_hyp, const uint32_t *growth, const MultiGrid *mg, int32_t *out) {
+    if (A == 0 || R == 0 || R % 64 || (growth && mg)) return hipErrorInvalidValue;
     const dim3 grid(R / 64, A);
     if (estimator != USAC_HOMOGRAPHY && estimator != USAC_FUNDAMENTAL) return hipErrorInvalidValue;
-    auto *draw4 = growth ? k_multi_draw<4, true> : k_multi_draw<4, false>;
-    auto *draw7 = growth ? k_multi_draw<7, true> : k_multi_draw<7, false>;
+    if (mg) {
+        auto *draw = estimator == USAC_HOMOGRAPHY ? k_multi_draw<4, kNapsac> : k_multi_draw<7, kNapsac>;
+        hipLaunchKernelGGL(draw, grid, dim3(64), 0, st, offsets, items, R, first_hyp, *mg, out);
+        return hipGetLastError();
+    }
+    auto *draw4 = growth ? k_multi_draw<4, kProsac> : k_multi_draw<4, kUniform>;
+    auto *draw7 = growth ? k_multi_draw<7, kProsac> : k_multi_draw<7, kUniform>;
     hipLaunchKernelGGL(estimator == USAC_HOMOGRAPHY ? draw4 : draw7, grid, dim3(64), 0, st, offsets, items, R,
                        first_hyp, growth, out);
     return hipGetLastError();

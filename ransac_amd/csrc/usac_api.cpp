@@ -3991,21 +3991,24 @@ void usac_lo_destroy(usac_lo *h) {
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- multi-problem batches (ABI 15 .. 19)
+// ---------------------------------------------------------------- multi-problem batches (ABI 15 .. 20)
 // P independent two-view problems in one context (kernels_multi.hip): the usac_hypothesize_score
 // round over (active problem, hypothesis tile), and a batch-granular RANSAC whose host loop only
 // reads the active problems' records once per round, evaluates the standard termination criterion
 // and uploads the compacted active list.  One stream; every buffer is sized once per call, for
 // (active problems) x R, none inside the round loop.  There is one such loop, multi_run_driver, with
-// three options read from the params; usac_multi_run, _run_polished, _run_prosac, _run_lo and _run_sprt
-// check their arguments and call it:
+// four options read from the params; usac_multi_run, _run_polished, _run_prosac, _run_lo, _run_sprt and
+// _run_napsac check their arguments and call it:
 //   PROSAC (ABI 17): the PROSAC sampler in closed form (usac_prosac.hpp) and PROSAC's termination scan,
 //     split between k_multi_prosac_scan, which stores its candidates into pinned host memory, and
 //     ProsacTerminationCriteria::applyCandidates;
 //   LO (ABI 18): k_multi_lo (kernels_nonmin.hip) between the round's merge and the scan / the record copy;
 //   SPRT (ABI 19): the round's score launch replaced by SPRT verification (kernels_multi_sprt.hip), one
 //     test per problem and round, re-designed on the host between rounds (usac::SprtRounds) from the
-//     statistics that come down with the records.  LO and SPRT do not combine.
+//     statistics that come down with the records.  LO and SPRT do not combine;
+//   NAPSAC (ABI 20): the solve kernels' NAPSAC instantiation over the problems' grid neighbours, built for
+//     all problems in one launch (kernels_multi_grid.hip) and kept for the cell size; the standard
+//     termination criterion; with LO, not with SPRT.
 
 // a pinned staging block (PinnedPool) that only grows
 struct PinBlock {
@@ -4039,6 +4042,11 @@ struct usac_multi {
     DevBuf sprt_pts, sprt_idx, sprt_consts, sprt_surv, sprt_surv_n, sprt_starts;
     bool sprt_ready = false, sprt_tail = false;
     PinBlock sprt_pin;
+    // NAPSAC (ABI 20): the problems' grid neighbours for cell size grid_cs (0 = none), one block in
+    // usac::MultiGrid's layout (multi_grid_args), and the host copy of [status | n_cells | n_eligible]
+    DevBuf grid;
+    int grid_cs = 0;
+    std::vector<uint32_t> grid_counts;  // 3 P
     std::string err;
 };
 
@@ -4382,6 +4390,72 @@ usac::MultiSprt multi_sprt_args(usac_multi *mc, uint32_t A, bool starts) {
     return s;
 }
 
+// ---- NAPSAC for multi-problem batches (ABI 20)
+// mc->grid in usac::MultiGrid's layout: cell, rank, members, eligible (n_total each), start (n_total + P),
+// then status, n_cells, n_eligible (P each, contiguous: one copy brings them down)
+usac::MultiGrid multi_grid_args(usac_multi *mc) {
+    const size_t N = mc->n_total, P = mc->P;
+    uint32_t *w = mc->grid.as<uint32_t>();
+    usac::MultiGrid g{};
+    g.cell = w;
+    g.rank = w + N;
+    g.members = reinterpret_cast<int32_t *>(w + 2 * N);
+    g.eligible = reinterpret_cast<int32_t *>(w + 3 * N);
+    g.start = w + 4 * N;
+    g.status = w + 5 * N + P;
+    g.n_cells = g.status + P;
+    g.n_eligible = g.n_cells + P;
+    return g;
+}
+
+// The grid of one problem past k_multi_grid's caps: usac::GridNeighbors over its points (any n_p, any
+// coordinate), uploaded into the problem's slices in the device layout (as host_grid does)
+int multi_grid_single(usac_multi *mc, const usac::MultiGrid &g, uint32_t p, int cs) {
+    const uint32_t base = mc->offsets[p], n = mc->offsets[p + 1] - base;
+    std::vector<float> pts(4 * (size_t)n);
+    HIP_TRY(mc, hipMemcpy(pts.data(), mc->pts.as<float>() + 4 * (size_t)base, sizeof(float) * 4 * (size_t)n,
+                          hipMemcpyDeviceToHost));
+    const usac::GridNeighbors h(pts.data(), n, cs);
+    const uint32_t nc = (uint32_t)h.starts().size() - 1;
+    std::vector<int32_t> elig;
+    for (uint32_t i = 0; i < n; i++)
+        if (h.count(i) >= mc->m) elig.push_back((int32_t)i);
+    HIP_TRY(mc, hipMemcpy(g.cell + base, h.cells().data(), 4 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(mc, hipMemcpy(g.rank + base, h.ranks().data(), 4 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(mc, hipMemcpy(g.members + base, h.members().data(), 4 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(mc, hipMemcpy(g.start + base + p, h.starts().data(), 4 * ((size_t)nc + 1), hipMemcpyHostToDevice));
+    if (!elig.empty()) HIP_TRY(mc, hipMemcpy(g.eligible + base, elig.data(), 4 * elig.size(), hipMemcpyHostToDevice));
+    uint32_t *cnt = mc->grid_counts.data();
+    cnt[mc->P + p] = nc;
+    cnt[2 * (size_t)mc->P + p] = (uint32_t)elig.size();
+    HIP_TRY(mc, hipMemcpy(g.n_cells + p, &cnt[mc->P + p], 4, hipMemcpyHostToDevice));
+    HIP_TRY(mc, hipMemcpy(g.n_eligible + p, &cnt[2 * (size_t)mc->P + p], 4, hipMemcpyHostToDevice));
+    return USAC_OK;
+}
+
+// the problems' grid neighbours for cell size cs, kept until another size is asked for: one launch, one
+// copy of the counts down, then the problems the kernel deferred on the host
+int multi_grid_ensure(usac_multi *mc, int cs) {
+    if (cs <= 0) return fail(mc, USAC_ERR_ARG, "grid cell_size must be > 0");
+    if (mc->grid_cs == cs) return USAC_OK;
+    const size_t N = mc->n_total, P = mc->P;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    HIP_TRY(mc, mc->grid.reserve(sizeof(uint32_t) * (5 * N + 4 * P)));
+    int rc = pin_grow(mc, mc->pin, sizeof(uint32_t) * 3 * P);
+    if (rc) return rc;
+    mc->grid_cs = 0;
+    const usac::MultiGrid g = multi_grid_args(mc);
+    HIP_TRY(mc, usac::launch_multi_grid(mc->stream, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), mc->P, cs, mc->m, g));
+    HIP_TRY(mc, hipMemcpyAsync(mc->pin.p, g.status, sizeof(uint32_t) * 3 * P, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    const uint32_t *down = static_cast<const uint32_t *>(mc->pin.p);
+    mc->grid_counts.assign(down, down + 3 * P);
+    for (uint32_t p = 0; p < mc->P; p++)
+        if (mc->grid_counts[p] == usac::kMultiGridDefer && (rc = multi_grid_single(mc, g, p, cs))) return rc;
+    mc->grid_cs = cs;
+    return USAC_OK;
+}
+
 // ---- the round hooks (usac_multi_hypothesize_score, its SPRT variant, usac_multi_draw_samples)
 // problems == NULL: all P problems in order, else the n_problems listed; A: the number of entries
 int multi_listed(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t &A) {
@@ -4481,17 +4555,20 @@ ProsacNext multi_prosac_round_end(usac_multi *mc, uint32_t a, const usac::MultiI
     return ProsacNext{L, it.clock + n_prosac};
 }
 
-// The run behind usac_multi_run, _run_polished, _run_prosac, _run_lo and _run_sprt, which have checked
-// that the params ask for what they offer: prosac (the sampler and its termination), lo (k_multi_lo after
-// every round) and sprt (verification instead of scoring; not with lo) are read from prm.  Per round:
+// The run behind usac_multi_run, _run_polished, _run_prosac, _run_lo, _run_sprt and _run_napsac, which have
+// checked that the params ask for what they offer: prosac (the sampler and its termination), napsac (the
+// sampler over the problems' grids, built before the loop), lo (k_multi_lo after every round) and sprt
+// (verification instead of scoring; not with lo or napsac) are read from prm.  Per round:
 // the active list (with sprt: and the entries' tests) up, the round, LO, the PROSAC scan, one copy of
 // the records (with sprt: and the statistics behind them) down, one wait; then per entry the bound, and
 // the entry is finished or kept.  Every check comes before the first change of the context's state.
 int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
                      const MultiRunOutputs &outs) {
     const bool prosac = prm->sampler == USAC_SAMPLER_PROSAC, sprt = prm->sprt != 0;
+    const bool napsac = prm->sampler == USAC_SAMPLER_NAPSAC;
     const bool lo = prm->lo == USAC_LO_INITLORSC || prm->lo == USAC_LO_INITFLORSC;
     if (lo && sprt) return fail(mc, USAC_ERR_UNSUPPORTED, "no LO with SPRT");
+    if (napsac && (sprt || prm->cell_size <= 0)) return fail(mc, USAC_ERR_ARG, "NAPSAC: cell_size > 0, no SPRT");
     const uint32_t R = prm->batch ? prm->batch : 256u;
     if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
     if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
@@ -4505,7 +4582,9 @@ int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *see
         return fail(mc, USAC_ERR_ARG, "SPRT certificate: margin >= 1e-7 and 0 < climb <= 700");
     HIP_TRY(mc, hipSetDevice(mc->device));
     // the buffers; a run starts with fresh LO and PROSAC state
-    int rc = multi_ensure(mc, P, R, false);
+    int rc = napsac ? multi_grid_ensure(mc, prm->cell_size) : USAC_OK;
+    const usac::MultiGrid mg = napsac ? multi_grid_args(mc) : usac::MultiGrid{};
+    if (!rc) rc = multi_ensure(mc, P, R, false);
     if (!rc && lo) rc = multi_lo_ensure(mc, prm, true);
     if (!rc && sprt) rc = multi_sprt_ensure(mc, P, R, false);
     if (!rc && prosac && !(rc = multi_prosac_ensure(mc))) rc = multi_prosac_reset(mc, prm);
@@ -4541,6 +4620,7 @@ int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *see
         usac::MultiRound r = multi_round(mc, A, R, first, prm->threshold, prm->dlt_mode);
         r.running = mc->running.as<usac_record>();
         if (prosac) r.growth = mc->growth.as<uint32_t>();
+        if (napsac) r.grid = &mg;
         const usac::MultiSprt ms = sprt ? multi_sprt_args(mc, A, false) : usac::MultiSprt{};
         if (sprt) {  // every active problem's current test
             for (uint32_t a = 0; a < A; a++) {
@@ -4697,7 +4777,7 @@ void usac_multi_destroy(usac_multi *mc) {
     if (mc->stream) (void)hipStreamSynchronize(mc->stream);
     for (PinBlock *b : {&mc->pin, &mc->pol_pin, &mc->pro_pin, &mc->sprt_pin})
         if (b->p) PinnedPool::get().give_back(b->p, b->bytes);
-    for (DevBuf *b : {&mc->growth, &mc->non_random0, &mc->non_random}) b->release();
+    for (DevBuf *b : {&mc->growth, &mc->non_random0, &mc->non_random, &mc->grid}) b->release();
     for (DevBuf *b : {&mc->sprt_pts, &mc->sprt_idx, &mc->sprt_consts, &mc->sprt_surv, &mc->sprt_surv_n, &mc->sprt_starts})
         b->release();
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
@@ -4806,7 +4886,7 @@ int usac_multi_draw_samples(usac_multi *mc, const uint32_t *problems, uint32_t n
                                mc->stream));
     HIP_TRY(mc, usac::launch_multi_draw(mc->stream, mc->estimator, mc->offs.as<uint32_t>(),
                                         mc->items.as<usac::MultiItem>(), A, R, first_hyp,
-                                        clock ? mc->growth.as<uint32_t>() : nullptr, mc->samples.as<int32_t>()));
+                                        clock ? mc->growth.as<uint32_t>() : nullptr, nullptr, mc->samples.as<int32_t>()));
     HIP_TRY(mc, hipMemcpyAsync(out, mc->samples.p, sizeof(int32_t) * (size_t)A * R * mc->m, hipMemcpyDeviceToHost,
                                mc->stream));
     HIP_TRY(mc, stream_wait(mc->stream));
@@ -4979,6 +5059,86 @@ int usac_multi_run_sprt(usac_multi *mc, const usac_params *prm, const uint64_t *
     if (prm->sampler != USAC_SAMPLER_UNIFORM && prm->sampler != USAC_SAMPLER_PROSAC)
         return fail(mc, USAC_ERR_ARG, "usac_multi_run_sprt: the uniform or the PROSAC sampler");
     return multi_run_driver(mc, prm, seeds, out, MultiRunOutputs{nullptr, pro, sprt, pol, mask});
+}
+
+// ---- NAPSAC (ABI 20)
+int usac_multi_grid(usac_multi *mc, int cell_size, uint32_t *n_cells, uint32_t *cell, uint32_t *rank, uint32_t *start,
+                    int32_t *members, int32_t *eligible, uint32_t *n_eligible) {
+    if (!mc) return USAC_ERR_ARG;
+    const int rc = multi_grid_ensure(mc, cell_size);
+    if (rc) return rc;
+    const size_t N = mc->n_total, P = mc->P;
+    const usac::MultiGrid g = multi_grid_args(mc);
+    if (n_cells) memcpy(n_cells, mc->grid_counts.data() + P, sizeof(uint32_t) * P);
+    if (n_eligible) memcpy(n_eligible, mc->grid_counts.data() + 2 * P, sizeof(uint32_t) * P);
+    if (cell) HIP_TRY(mc, hipMemcpyAsync(cell, g.cell, 4 * N, hipMemcpyDeviceToHost, mc->stream));
+    if (rank) HIP_TRY(mc, hipMemcpyAsync(rank, g.rank, 4 * N, hipMemcpyDeviceToHost, mc->stream));
+    if (start) HIP_TRY(mc, hipMemcpyAsync(start, g.start, 4 * (N + P), hipMemcpyDeviceToHost, mc->stream));
+    if (members) HIP_TRY(mc, hipMemcpyAsync(members, g.members, 4 * N, hipMemcpyDeviceToHost, mc->stream));
+    if (eligible) HIP_TRY(mc, hipMemcpyAsync(eligible, g.eligible, 4 * N, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return USAC_OK;
+}
+
+int usac_multi_draw_samples_napsac(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t R,
+                                   const uint64_t *seeds, uint64_t first_hyp, int cell_size, int32_t *out) {
+    if (!mc) return USAC_ERR_ARG;
+    if (!seeds || !out) return fail(mc, USAC_ERR_ARG, "seeds and out");
+    if (cell_size <= 0) return fail(mc, USAC_ERR_ARG, "grid cell_size must be > 0");
+    if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
+    uint32_t A = 0;
+    int rc = multi_listed(mc, problems, n_problems, A);
+    if (rc || (rc = multi_check_entries(mc, problems, A, nullptr, R, [](uint32_t, uint32_t) -> int { return USAC_OK; })))
+        return rc;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    if ((rc = multi_grid_ensure(mc, cell_size)) || (rc = multi_ensure(mc, A, R, true)) ||
+        (rc = multi_hook_upload(mc, problems, A, nullptr, R, seeds)))
+        return rc;
+    const usac::MultiGrid mg = multi_grid_args(mc);
+    HIP_TRY(mc, usac::launch_multi_draw(mc->stream, mc->estimator, mc->offs.as<uint32_t>(),
+                                        mc->items.as<usac::MultiItem>(), A, R, first_hyp, nullptr, &mg,
+                                        mc->samples.as<int32_t>()));
+    HIP_TRY(mc, hipMemcpyAsync(out, mc->samples.p, sizeof(int32_t) * (size_t)A * R * mc->m, hipMemcpyDeviceToHost,
+                               mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return USAC_OK;
+}
+
+int usac_multi_hypothesize_score_napsac(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t R,
+                                        const uint64_t *seeds, uint64_t first_hyp, float thr, int dlt_mode,
+                                        int cell_size, int32_t *counts, float *sums, usac_record *best) {
+    if (!mc) return USAC_ERR_ARG;
+    if (cell_size <= 0) return fail(mc, USAC_ERR_ARG, "grid cell_size must be > 0");
+    uint32_t A = 0;
+    int rc = multi_hook_args(mc, problems, n_problems, nullptr, R, seeds, dlt_mode, A);
+    if (rc || (rc = multi_check_entries(mc, problems, A, nullptr, R, [](uint32_t, uint32_t) -> int { return USAC_OK; })))
+        return rc;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    if ((rc = multi_grid_ensure(mc, cell_size)) || (rc = multi_ensure(mc, A, R, false)) ||
+        (rc = multi_hook_upload(mc, problems, A, nullptr, R, seeds)))
+        return rc;
+    const usac::MultiGrid mg = multi_grid_args(mc);
+    usac::MultiRound r = multi_round(mc, A, R, first_hyp, thr, dlt_mode);
+    r.grid = &mg;
+    HIP_TRY(mc, usac::launch_multi_round(mc->stream, r));
+    if ((rc = multi_hook_down(mc, A, R, counts, sums, best))) return rc;
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return USAC_OK;
+}
+
+int usac_multi_run_napsac(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
+                          usac_multi_lo_output *lo, usac_multi_polish_output *pol, uint8_t *mask) {
+    if (!mc || !prm || !out) return USAC_ERR_ARG;
+    if (prm->sampler != USAC_SAMPLER_NAPSAC) return fail(mc, USAC_ERR_ARG, "usac_multi_run_napsac: the NAPSAC sampler");
+    if (prm->neighbors != USAC_NEIGHBORS_GRID)
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run_napsac: grid neighbours only (no KNN NAPSAC)");
+    if (prm->cell_size <= 0) return fail(mc, USAC_ERR_ARG, "usac_multi_run_napsac: cell_size must be > 0");
+    if (prm->sprt) return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run_napsac: no SPRT with NAPSAC");
+    if (prm->lo != USAC_LO_NONE) {
+        const int rc = multi_lo_check(mc, prm, "usac_multi_run_napsac");
+        if (rc) return rc;
+    }
+    return multi_run_driver(mc, prm, seeds, out, MultiRunOutputs{prm->lo != USAC_LO_NONE ? lo : nullptr, nullptr, nullptr, pol, mask});
 }
 
 }  // extern "C"

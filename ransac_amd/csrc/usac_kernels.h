@@ -361,7 +361,23 @@ struct MultiRound {
     const uint32_t *growth;     // nullable: the PROSAC sampler (items' clock / term_len) over the growth
                                 // functions, n_total values, problem p's at growth + offsets[p]
     const struct MultiSprt *sprt;  // nullable: SPRT verification (kernels_multi_sprt.hip) in place of the score launch
+    const struct MultiGrid *grid;  // nullable (not with growth): the NAPSAC sampler over the problems' grids
 };
+// Grid neighbours of every problem (kernels_multi_grid.hip, one workgroup per problem): the CSR of
+// usac::GridNeighbors over each problem's points, problem-local at the points' offsets -- cell, rank,
+// members, eligible (points with >= m neighbours, ascending): n_total values each, problem p's at
+// offsets[p]; start: n_total + P, problem p's n_cells + 1 entries at offsets[p] + p; n_cells,
+// n_eligible, status: P each.  A problem past the caps (n_p > kMultiGridMax, or a coordinate with
+// !(|x| / cell_size < 1e9f)) gets status = kMultiGridDefer and no other output.
+constexpr uint32_t kMultiGridMax = 4000;  // 20 B of LDS per point: two workgroups share a CU's 160 KiB
+constexpr uint32_t kMultiGridDefer = 1;
+struct MultiGrid {
+    uint32_t *cell, *rank, *start;
+    int32_t *members, *eligible;
+    uint32_t *n_cells, *n_eligible, *status;
+};
+hipError_t launch_multi_grid(hipStream_t st, const float4 *pts, const uint32_t *offsets, uint32_t P, int cell_size,
+                             uint32_t m, const MultiGrid &g);
 hipError_t launch_multi_round(hipStream_t st, const MultiRound &r);
 // SPRT verification of a round's slots (kernels_multi_sprt.hip): the throughput SPRT of launch_score_sprt
 // with one test per active entry.  pool_pts: N_total float4, problem p's slice in its pool's order;
@@ -382,9 +398,9 @@ struct MultiSprt {
 hipError_t launch_multi_sprt_score(hipStream_t st, const MultiRound &r);
 size_t multi_sprt_survivor_bytes();
 // the samples launch_multi_round's solve kernels draw (same device function), out: A x R x m local
-// indices; growth == nullptr: the uniform sampler
+// indices; growth: the PROSAC sampler, grid: the NAPSAC sampler (not both), neither: the uniform sampler
 hipError_t launch_multi_draw(hipStream_t st, int estimator, const uint32_t *offsets, const MultiItem *items, uint32_t A,
-                             uint32_t R, uint64_t first_hyp, const uint32_t *growth, int32_t *out);
+                             uint32_t R, uint64_t first_hyp, const uint32_t *growth, const MultiGrid *grid, int32_t *out);
 // PROSAC termination scan (kernels_multi_prosac.hip), one workgroup per active entry, after the
 // round's argmax: a problem whose running record improved in this round (valid, hyp_index >=
 // first_hyp) gets the O(n) part of prosac_termination_criteria.hpp:148-201 under that model --

@@ -36,6 +36,17 @@ MultiContext.run -- or, with --sampler prosac, with MultiContext.run_prosac -- o
 --polish both include the polish.  Reported for both: rounds, hypotheses, mean best inliers; for the SPRT
 run also the point tests done over slots x n_p, the tests designed per pair and the accepted / rejected
 slots; and, separately, the one-time cost of set_sprt_pool, which is not part of a run.
+
+--sampler napsac [--cell-size N] [--cluster HW] compares the NAPSAC run with the uniform run:
+MultiContext.run_napsac (grid NAPSAC per pair over the cells of size N) is alternated with MultiContext.run
+on the same pairs; with --lo both runs include LO (run_napsac with the LO model against run_lo), with
+--polish both include the polish.  --cluster HW draws the homography pairs from
+synthetic.homography_points(..., cluster=(500, 500, HW)): the inliers sit in a box of half-width HW of
+the first image, so that cells hold inliers.  Reported for both: median ms and spread, rounds per pair,
+hypotheses, mean best inliers; for the NAPSAC run also the share of pairs without an eligible point
+(they draw uniform samples) and the mean eligible share; and, apart from the runs, the grid build of all
+pairs (usac_multi_grid with no output, after a build for another size), which a run pays once per cell
+size.  No loop over single contexts in this mode.
 """
 import argparse
 import ctypes
@@ -55,7 +66,10 @@ import ransac_amd as usac  # noqa: E402
 from ransac_amd import synthetic  # noqa: E402
 
 
-def make_pairs(estimator, pairs, points, ratio, quality_sorted=False):
+def make_pairs(estimator, pairs, points, ratio, quality_sorted=False, cluster=None):
+    if cluster is not None:
+        return [synthetic.homography_points(n=points, inlier_ratio=ratio, seed=1000 + p, cluster=(500, 500, cluster))[0]
+                for p in range(pairs)]
     if quality_sorted:
         if estimator == "homography":
             sets = []
@@ -365,6 +379,72 @@ def main_sprt(a, mc, model, est):
     return 0
 
 
+def main_napsac(a, mc, model, est):
+    """--sampler napsac: MultiContext.run_napsac against the uniform run (run, or run_lo with --lo) on the
+    same inputs, alternated, host-timed, medians and spreads as in main(); the grid build timed apart"""
+    nmodel = usac.Model(model.threshold, mc.m, model.desired_prob, 5, est, usac.SAMPLER.Napsac)
+    nmodel.max_iterations, nmodel.batch, nmodel.seed = model.max_iterations, model.batch, model.seed
+    nmodel.setDLTMode(model.dlt_mode)
+    nmodel.setNeighborsType(usac.NeighborsSearch.Grid)
+    nmodel.setCellSize(a.cell_size)
+    if a.lo:
+        nmodel.lo = model.lo = usac.LocOpt.InItLORsc if a.lo == "lorsc" else usac.LocOpt.InItFLORsc
+    run_base = mc.run_lo if a.lo else mc.run
+
+    def summary(res, ms):
+        rounds = [r["rounds"] for r in res]
+        d = {"ms": round(statistics.median(ms), 3), "spread_ms": round(max(ms) - min(ms), 3),
+             "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
+             "mean_rounds": round(float(np.mean(rounds)), 2), "launch_rounds": int(max(rounds)),
+             "hypotheses": int(sum(r["hypotheses"] for r in res)),
+             "mean_best_inliers": round(float(np.mean([r["best"]["inliers"] for r in res])), 2)}
+        if a.polish:
+            d["mean_polished_inliers"] = round(float(np.mean([r["polished"]["inliers"] for r in res])), 2)
+        return d
+
+    # the grid build of all pairs, apart from the runs: each timed build follows one for another size
+    L, build = usac.lib(), []
+    for _ in range(a.warmup + a.reps):
+        if L.usac_multi_grid(mc._h, a.cell_size + 1, None, None, None, None, None, None, None) != 0:
+            raise RuntimeError("usac_multi_grid failed")
+        t0 = time.perf_counter()
+        rc = L.usac_multi_grid(mc._h, a.cell_size, None, None, None, None, None, None, None)
+        build.append((time.perf_counter() - t0) * 1e3)
+        if rc != 0:
+            raise RuntimeError("usac_multi_grid failed")
+    build = build[a.warmup:]
+    elig = np.array([len(g["eligible"]) for g in mc.grid_neighbors(a.cell_size)])
+    for _ in range(a.warmup):
+        rn, ru = mc.run_napsac(nmodel, polish=a.polish), run_base(model, polish=a.polish)
+    tn, tu = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        rn = mc.run_napsac(nmodel, polish=a.polish)
+        t1 = time.perf_counter()
+        ru = run_base(model, polish=a.polish)
+        t2 = time.perf_counter()
+        tn.append((t1 - t0) * 1e3)
+        tu.append((t2 - t1) * 1e3)
+    line = {"bench": "multi_napsac", "estimator": a.estimator, "pairs": a.pairs, "points": a.points, "round": a.R,
+            "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio, "dlt": a.dlt, "reps": a.reps,
+            "polish": bool(a.polish), "lo": a.lo, "cell_size": a.cell_size, "cluster": a.cluster,
+            "grid_build_ms": round(statistics.median(build), 3), "grid_build_spread_ms": round(max(build) - min(build), 3),
+            "napsac": summary(rn, tn), "uniform": summary(ru, tu)}
+    line["napsac"]["share_no_eligible_point"] = round(float(np.mean(elig == 0)), 4)
+    line["napsac"]["mean_eligible_share"] = round(float(np.mean(elig / mc.sizes)), 4)
+    line["ratio_napsac_over_uniform"] = round(line["napsac"]["ms"] / line["uniform"]["ms"], 2)
+    line["napsac_faster_beyond_spread"] = bool(line["uniform"]["ms"] - line["napsac"]["ms"] >
+                                               max(line["napsac"]["spread_ms"], line["uniform"]["spread_ms"]))
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    mc.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=512)
@@ -380,8 +460,12 @@ def main():
     ap.add_argument("--polish", action="store_true",
                     help="time run + non-minimal polish: MultiContext.run(polish=True) against the multi run "
                          "alone and against the loop over contexts with the polish restated per context")
-    ap.add_argument("--sampler", choices=["uniform", "prosac"], default="uniform",
-                    help="prosac: quality-sorted inputs, MultiContext.run_prosac against the uniform multi run")
+    ap.add_argument("--sampler", choices=["uniform", "prosac", "napsac"], default="uniform",
+                    help="prosac: quality-sorted inputs, MultiContext.run_prosac against the uniform multi run; "
+                         "napsac: MultiContext.run_napsac against the uniform multi run")
+    ap.add_argument("--cell-size", type=int, default=50, help="--sampler napsac: the grid cell")
+    ap.add_argument("--cluster", type=float, default=None, metavar="HW",
+                    help="homography pairs whose inliers sit in the box (500 +- HW)^2 of the first image")
     ap.add_argument("--lo", choices=["lorsc", "florsc"], default=None,
                     help="MultiContext.run_lo (inner + iterative LO-RANSAC, unlimited / limited) against the same "
                          "run without LO; with --sampler prosac both use the PROSAC sampler")
@@ -393,16 +477,23 @@ def main():
         ap.error("--reps must be at least 5")
     if a.sprt and a.lo:
         ap.error("--sprt and --lo do not combine (usac_multi_run_sprt runs without LO)")
+    if a.sampler == "napsac" and a.sprt:
+        ap.error("--sampler napsac does not combine with --sprt (usac_multi_run_napsac runs without SPRT)")
+    if a.cluster is not None and a.estimator != "homography":
+        ap.error("--cluster applies to homography pairs")
 
     est = usac.ESTIMATOR.Homography if a.estimator == "homography" else usac.ESTIMATOR.Fundamental
     thr, prob = 2.0, 0.95
-    sets = make_pairs(a.estimator, a.pairs, a.points, a.inlier_ratio, quality_sorted=a.sampler == "prosac")
+    sets = make_pairs(a.estimator, a.pairs, a.points, a.inlier_ratio, quality_sorted=a.sampler == "prosac",
+                      cluster=a.cluster)
     model = usac.Model(thr, 4 if a.estimator == "homography" else 7, prob, 5, est, usac.SAMPLER.Uniform)
     model.max_iterations, model.batch, model.seed = a.max_iterations, a.R, 1
     model.setDLTMode(usac.DLT.NULLSPACE if a.dlt == "nullspace" else usac.DLT.THIN)
     seeds = [model.seed + p for p in range(a.pairs)]
 
     mc = usac.MultiContext(est, sets)
+    if a.sampler == "napsac":
+        return main_napsac(a, mc, model, est)
     if a.sprt:
         return main_sprt(a, mc, model, est)
     if a.lo:
