@@ -66,7 +66,9 @@
  *                                  grid neighbours built for all problems in one launch (one workgroup per
  *                                  problem), optionally with LO and the polish, with usac_multi_grid /
  *                                  usac_multi_draw_samples_napsac / usac_multi_hypothesize_score_napsac
- *                                  exposing its parts
+ *                                  exposing its parts;
+ *                                  ABI 21: usac_multi_create_essential, multi contexts of essential-matrix
+ *                                  problems (5-point solver): rounds, runs, masks, the polish and PROSAC
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -81,7 +83,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 20
+#define USAC_ABI_VERSION 21
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -487,7 +489,8 @@ int usac_merge_records(const usac_record *recs, uint32_t n, usac_record *best);
 
 /* ---- multi-problem batches (ABI 15; polish: ABI 16; PROSAC: ABI 17, below) ----------------------------
  * A multi context holds P independent two-view problems of one estimator (USAC_HOMOGRAPHY or
- * USAC_FUNDAMENTAL; line and essential: USAC_ERR_UNSUPPORTED) and runs them together: one launch
+ * USAC_FUNDAMENTAL; the essential matrix through usac_multi_create_essential, ABI 21; line:
+ * USAC_ERR_UNSUPPORTED) and runs them together: one launch
  * whose grid covers (problem, 64-hypothesis tile).  Points are one concatenated N_total x 4 fp32
  * array and offsets[P + 1] with offsets[0] = 0: problem p owns rows offsets[p] .. offsets[p + 1] - 1,
  * n_p >= the sample size.  Sample, hypothesis and inlier indices are local to the problem.
@@ -514,9 +517,26 @@ typedef struct usac_multi_output {
 } usac_multi_output;
 
 /* USAC_ERR_ARG for P == 0 or P > 65535, offsets[0] != 0, non-monotonic offsets or any n_p < m, and
- * USAC_ERR_UNSUPPORTED for the line and essential estimators -- all before any device call. */
+ * USAC_ERR_UNSUPPORTED for the line and essential estimators -- all before any device call.  A multi
+ * context of essential-matrix problems comes from usac_multi_create_essential. */
 int usac_multi_create(usac_multi **out, int device, int estimator, const float *pts, const uint32_t *offsets,
                       uint32_t P);
+/* usac_multi_create for the essential matrix (ABI 21): the points are calibrated coordinates (K^-1 x), as
+ * usac_create's for USAC_ESSENTIAL; m = 5, one slot per sample (S = 1; count -1, sum 0 on a sample without
+ * a model).  USAC_ERR_ARG as usac_multi_create's (P == 0 or > 65535, offsets, any n_p < 5, NULL pointers)
+ * -- before any device call.
+ * Per problem every result equals a usac_ctx of USAC_ESSENTIAL over its points bit for bit: the 5-point
+ * solver keeps the reference's candidate (rpoly's order) and scoring is the one-chunk exact form.
+ * On such a context work: usac_multi_hypothesize_score (dlt_mode is ignored), usac_multi_run,
+ * usac_multi_inliers, usac_multi_polish, usac_multi_run_polished, usac_multi_draw_samples,
+ * usac_multi_run_prosac and usac_multi_prosac_scan, with the contracts they have for H / F.
+ * USAC_ERR_UNSUPPORTED, before any device call: usac_multi_lo, usac_multi_run_lo, usac_multi_sprt_setup,
+ * usac_multi_hypothesize_score_sprt, usac_multi_run_sprt, usac_multi_grid,
+ * usac_multi_draw_samples_napsac, usac_multi_hypothesize_score_napsac and usac_multi_run_napsac.
+ * The solve's workspace is ~1.2 KB per sample; a round of more than 131 072 samples is solved in slices
+ * of whole problems (USAC_MULTI_E5_SLICE in the environment at creation lowers the cap, for tests);
+ * the results do not depend on the slice. */
+int usac_multi_create_essential(usac_multi **out, int device, const float *pts, const uint32_t *offsets, uint32_t P);
 void usac_multi_destroy(usac_multi *mc);
 const char *usac_multi_last_error(const usac_multi *mc);
 uint32_t usac_multi_num_problems(const usac_multi *mc);
@@ -524,7 +544,7 @@ uint32_t usac_multi_num_problems(const usac_multi *mc);
  * n_problems = P or 0).  samples: host n_problems x R x m indices local to each problem (out of
  * range: USAC_ERR_ARG), or NULL for the device sampler with seeds[i] for problems[i].  R: a multiple
  * of 64 in 64..8192 (a wave never spans two problems).  counts / sums (nullable): n_problems x R x S,
- * S = 3 for the fundamental solver, else 1.  best (nullable): n_problems records, each the round's
+ * S = 3 for the fundamental solver, else 1 (essential: count -1 on a sample without a model).  best (nullable): n_problems records, each the round's
  * best of its problem under Score::bigger with the earliest (sample, slot) on exact ties,
  * hyp_index = first_hyp + sample. */
 int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint32_t n_problems,

@@ -36,6 +36,7 @@
 #include <random>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "usac_gpu.h"
@@ -527,8 +528,8 @@ private:
     RansacOutput *out_ = nullptr;
 };
 
-// P independent two-view problems of one estimator (Homography / Fundamental) run together
-// (usac_multi_*, ABI 15): points concatenated, offsets[P + 1]; sample, hypothesis and inlier indices
+// P independent two-view problems of one estimator (Homography / Fundamental, or Essential through
+// MultiContext::essential) run together (usac_multi_*, ABI 15): points concatenated, offsets[P + 1]; sample, hypothesis and inlier indices
 // are local to each problem, and every per-problem result equals a Context over that problem's
 // points bit for bit.  Not copyable.
 class MultiContext {
@@ -546,15 +547,26 @@ public:
         const int rc = usac_multi_create(&mc_, device, (int)est, points, offsets.data(), P);
         if (rc != USAC_OK) throw Error(rc, "usac_multi_create failed");
     }
+    // P essential-matrix problems (usac_multi_create_essential, ABI 21): points are calibrated
+    // coordinates (K^-1 x), 5-point samples, one model slot per sample.  The constructor keeps
+    // refusing Essential.  No LO, SPRT or NAPSAC: those members throw USAC_ERR_UNSUPPORTED.
+    static MultiContext essential(const float *points, const std::vector<uint32_t> &offsets, int device = 0) {
+        MultiContext mc(offsets);
+        const uint32_t P = offsets.empty() ? 0u : (uint32_t)(offsets.size() - 1);
+        const int rc = usac_multi_create_essential(&mc.mc_, device, points, offsets.data(), P);
+        if (rc != USAC_OK) throw Error(rc, "usac_multi_create_essential failed");
+        return mc;
+    }
     ~MultiContext() {
         if (mc_) usac_multi_destroy(mc_);
     }
     MultiContext(const MultiContext &) = delete;
     MultiContext &operator=(const MultiContext &) = delete;
+    MultiContext(MultiContext &&o) : mc_(o.mc_), est_(o.est_), offsets_(std::move(o.offsets_)) { o.mc_ = nullptr; }
 
     usac_multi *get() const { return mc_; }
     unsigned int problems() const { return usac_multi_num_problems(mc_); }
-    unsigned int sampleSize() const { return est_ == Fundamental ? 7u : 4u; }
+    unsigned int sampleSize() const { return est_ == Fundamental ? 7u : est_ == Essential ? 5u : 4u; }
     unsigned int modelSlots() const { return est_ == Fundamental ? 3u : 1u; }
     unsigned int pointsSize(unsigned int p) const { return offsets_[p + 1] - offsets_[p]; }
     void check(int rc, const char *what) const {
@@ -798,6 +810,8 @@ private:
             for (uint32_t i = offsets_[p]; i < offsets_[p + 1]; i++)
                 if (mask[i]) (*out)[p].push_back((int)(i - offsets_[p]));
     }
+
+    explicit MultiContext(const std::vector<uint32_t> &offsets) : est_(Essential), offsets_(offsets) {}  // essential()
 
     usac_multi *mc_ = nullptr;
     ESTIMATOR est_;

@@ -201,6 +201,7 @@ ABI_SYMBOLS = [
     "usac_lo_draw", "usac_multi_lo", "usac_multi_run_lo",
     "usac_multi_sprt_setup", "usac_multi_hypothesize_score_sprt", "usac_multi_sprt_update", "usac_multi_run_sprt",
     "usac_multi_grid", "usac_multi_draw_samples_napsac", "usac_multi_hypothesize_score_napsac", "usac_multi_run_napsac",
+    "usac_multi_create_essential",
 ]
 
 
@@ -298,6 +299,7 @@ def lib():
         "usac_lo_iters": (ctypes.c_int, [_vp, u32p, u32p]),
         "usac_lo_destroy": (None, [_vp]),
         "usac_multi_create": (ctypes.c_int, [_P(_vp), ctypes.c_int, ctypes.c_int, f32p, u32p, ctypes.c_uint32]),
+        "usac_multi_create_essential": (ctypes.c_int, [_P(_vp), ctypes.c_int, f32p, u32p, ctypes.c_uint32]),
         "usac_multi_destroy": (None, [_vp]),
         "usac_multi_last_error": (ctypes.c_char_p, [_vp]),
         "usac_multi_num_problems": (ctypes.c_uint32, [_vp]),
@@ -762,14 +764,32 @@ class Context:
 
 
 class MultiContext:
-    """P independent two-view problems of one estimator (Homography or Fundamental) on one device,
-    run together (include/usac_gpu.h usac_multi_*): point_sets is a list of n_p x 4 arrays, stored as
-    one concatenated array plus offsets.  Sample, hypothesis and inlier indices are local to each
-    problem, and every per-problem result equals a Context over that problem's points bit for bit."""
+    """P independent two-view problems of one estimator on one device, run together
+    (include/usac_gpu.h usac_multi_*): point_sets is a list of n_p x 4 arrays, stored as one
+    concatenated array plus offsets.  Sample, hypothesis and inlier indices are local to each problem,
+    and every per-problem result equals a Context over that problem's points bit for bit.
+
+    MultiContext(estimator, point_sets) takes Homography or Fundamental.  Essential-matrix problems
+    come from MultiContext.essential(point_sets): calibrated coordinates (K^-1 x), 5-point samples, one
+    slot per sample (count -1 on a sample without a model).  On such a context hypothesize_score,
+    run (with and without polish), inliers, polish, draw_samples, run_prosac and prosac_scan work as
+    for H / F; the LO, SPRT and NAPSAC methods raise UsacError(-3)."""
 
     def __init__(self, estimator, point_sets, device=0):
+        self._create(ESTIMATOR(estimator), point_sets, device, False)
+
+    @classmethod
+    def essential(cls, point_sets, device=0):
+        """usac_multi_create_essential: a multi context of essential-matrix problems (the constructor
+        keeps refusing ESTIMATOR.Essential)."""
+        self = cls.__new__(cls)
+        self._create(ESTIMATOR.Essential, point_sets, device, True)
+        return self
+
+    def _create(self, estimator, point_sets, device, essential):
         L = lib()
-        self.estimator = ESTIMATOR(estimator)
+        self.estimator = estimator
+        self._h = None
         sets = [np.ascontiguousarray(p, dtype=np.float32) for p in point_sets]
         for p in sets:
             if p.ndim != 2 or p.shape[1] != 4:
@@ -781,15 +801,20 @@ class MultiContext:
         self.points = np.concatenate(sets, axis=0) if sets else np.zeros((0, 4), np.float32)
         self.points = np.ascontiguousarray(self.points, dtype=np.float32)
         self.dlt_mode = DLT.THIN
-        self._h = None
         h = _vp()
-        rc = L.usac_multi_create(ctypes.byref(h), device, int(self.estimator), _ptr(self.points, ctypes.c_float),
-                                 _ptr(self.offsets, ctypes.c_uint32), self.P)
+        if essential:
+            name = "usac_multi_create_essential"
+            rc = L.usac_multi_create_essential(ctypes.byref(h), device, _ptr(self.points, ctypes.c_float),
+                                               _ptr(self.offsets, ctypes.c_uint32), self.P)
+        else:
+            name = "usac_multi_create"
+            rc = L.usac_multi_create(ctypes.byref(h), device, int(self.estimator), _ptr(self.points, ctypes.c_float),
+                                     _ptr(self.offsets, ctypes.c_uint32), self.P)
         if rc != 0:
-            raise UsacError(rc, "usac_multi_create(device=%d, estimator=%s, P=%d) failed (bad arguments, or no "
-                                "usable GPU)" % (device, self.estimator.name, self.P))
+            raise UsacError(rc, "%s(device=%d, estimator=%s, P=%d) failed (bad arguments, or no "
+                                "usable GPU)" % (name, device, self.estimator.name, self.P))
         self._h = h
-        self.m = 7 if self.estimator == ESTIMATOR.Fundamental else 4
+        self.m = {ESTIMATOR.Fundamental: 7, ESTIMATOR.Essential: 5}.get(self.estimator, 4)
         self.spk = 3 if self.estimator == ESTIMATOR.Fundamental else 1
 
     def close(self):

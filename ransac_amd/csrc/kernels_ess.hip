@@ -23,6 +23,11 @@
 // for its slowest lane, and its work has a long tail (a 20-shift failure is ~20 000 K divisions) --
 // so it runs for those samples only.
 //
+// Multi-problem batches (DESIGN.md §8b "Essential"): launch_multi_solve_e5 runs the same pipeline over a
+// round's A x R samples of different problems -- k_multi_e5_basis, k_multi_e5_check and k_multi_e5_select
+// are the three stages that touch points, samples or the round's slabs; the other five are launched as
+// they are.
+//
 // Workspace (e5_workspace_bytes(B)): samples int32[5][B], N double[36][B], dets double[11][B],
 // roots double[10][B], nroots int32[B], pair list uint32[10B] + counter, candidate E
 // float[9][10B], flags int32[10B], order list uint32[B] + counter, deferred list uint32[B] +
@@ -34,6 +39,7 @@
 #include "usac_device_e5.hpp"
 #include "usac_rpoly.hpp"
 #include "usac_kernels.h"
+#include "usac_multi_sampler.hpp"
 
 #include <stdlib.h>
 
@@ -93,22 +99,10 @@ size_t e5_workspace_bytes(uint32_t B) {
            e5_align(sizeof(int32_t) * 10 * (size_t)B);
 }
 
-__global__ __launch_bounds__(64) void k_e5_basis(const float4 *__restrict__ pts, uint32_t n,
-                                                 const int32_t *__restrict__ samples_in, int32_t *samples_out,
-                                                 uint32_t B, DevSampler ds, uint64_t first_hyp, E5Work w) {
-    const uint32_t h = blockIdx.x * 64 + threadIdx.x;
-    if (h >= B) return;
-    int32_t s[5];
-    if (samples_in) {
-#pragma unroll
-        for (int i = 0; i < 5; i++) s[i] = samples_in[5 * (size_t)h + i];
-    } else {
-        draw_sample<5>(ds, first_hyp + h, n, s);
-        if (samples_out) {
-#pragma unroll
-            for (int i = 0; i < 5; i++) samples_out[5 * (size_t)h + i] = s[i];
-        }
-    }
+// the sample's 5 x 9 rows -> the 4-vector null basis N (five_points.cpp:36-66), and the sample itself
+// into the workspace (k_e5_check's cheirality test reads it back)
+__device__ __forceinline__ void e5_basis_of(const float4 *__restrict__ pts, const int32_t (&s)[5], uint32_t B,
+                                            uint32_t h, const E5Work &w) {
 #pragma unroll
     for (int i = 0; i < 5; i++) w.smp[(size_t)i * B + h] = s[i];
     double W[5][9], N[4][9];
@@ -136,6 +130,49 @@ __global__ __launch_bounds__(64) void k_e5_basis(const float4 *__restrict__ pts,
     for (int j = 0; j < 4; j++)
 #pragma unroll
         for (int k = 0; k < 9; k++) w.N[(size_t)(9 * j + k) * B + h] = N[j][k];
+}
+
+__global__ __launch_bounds__(64) void k_e5_basis(const float4 *__restrict__ pts, uint32_t n,
+                                                 const int32_t *__restrict__ samples_in, int32_t *samples_out,
+                                                 uint32_t B, DevSampler ds, uint64_t first_hyp, E5Work w) {
+    const uint32_t h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= B) return;
+    int32_t s[5];
+    if (samples_in) {
+#pragma unroll
+        for (int i = 0; i < 5; i++) s[i] = samples_in[5 * (size_t)h + i];
+    } else {
+        draw_sample<5>(ds, first_hyp + h, n, s);
+        if (samples_out) {
+#pragma unroll
+            for (int i = 0; i < 5; i++) samples_out[5 * (size_t)h + i] = s[i];
+        }
+    }
+    e5_basis_of(pts, s, B, h, w);
+}
+
+// multi-problem batches: grid (R / 64, entries of the slice), sample a R + h of the slice (B = entries x
+// R); items, samples_in: the slice's first entry's.  The sample as k_multi_solve_h4 / _f7 take it.
+template <int SAMPLER>
+__global__ __launch_bounds__(64) void k_multi_e5_basis(const float4 *__restrict__ pts_all,
+                                                       const uint32_t *__restrict__ offsets,
+                                                       const MultiItem *__restrict__ items,
+                                                       const int32_t *__restrict__ samples_in, uint32_t R,
+                                                       uint64_t first_hyp, E5Work w,
+                                                       const typename SamplerArg<SAMPLER>::type aux) {
+    const uint32_t a = blockIdx.y;
+    const MultiItem it = items[a];
+    const uint32_t base = offsets[it.problem], n = offsets[it.problem + 1] - base;
+    const uint32_t h = blockIdx.x * 64 + threadIdx.x;
+    const uint32_t g = a * R + h, B = gridDim.y * R;
+    int32_t s[5];
+    if (samples_in) {
+#pragma unroll
+        for (int i = 0; i < 5; i++) s[i] = samples_in[5 * (size_t)g + i];
+    } else {
+        multi_sample<5, SAMPLER>(it, aux, base, n, first_hyp + h, h, s);
+    }
+    e5_basis_of(pts_all + base, s, B, g, w);
 }
 
 __device__ __forceinline__ void e5_load_basis(const E5Work &w, uint32_t B, uint32_t h, double (&N)[4][9]) {
@@ -356,14 +393,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
-__global__ __launch_bounds__(64) void k_e5_check(const float4 *__restrict__ pts, uint32_t B, uint32_t maxpairs,
-                                                 E5Work w) {
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    const uint32_t np = *w.npairs;
-    if (i >= np || i >= maxpairs) return;
-    if (!w.xyok[i]) return;
-    const uint32_t rb = w.pairs[i];
-    const uint32_t r = rb / B, h = rb - r * B;
+// listed pair i = (root r, sample h): E, its SVD, cheirality over the sample's five points
+__device__ __forceinline__ void e5_check_pair(const float4 *__restrict__ pts, uint32_t B, uint32_t i, uint32_t rb,
+                                              uint32_t r, uint32_t h, const E5Work &w) {
     double N[4][9];
     e5_load_basis(w, B, h, N);
     const double zz = w.roots[(size_t)r * B + h];
@@ -391,29 +423,55 @@ __global__ __launch_bounds__(64) void k_e5_check(const float4 *__restrict__ pts,
     }
 }
 
-__global__ __launch_bounds__(64) void k_e5_select(uint32_t B, E5Work w, float *__restrict__ models,
-                                                  int32_t *__restrict__ counts, uint32_t *__restrict__ list,
-                                                  uint32_t *__restrict__ list_n) {
-    const uint32_t lane = threadIdx.x;
-    const uint32_t h = blockIdx.x * 64 + lane;
+__global__ __launch_bounds__(64) void k_e5_check(const float4 *__restrict__ pts, uint32_t B, uint32_t maxpairs,
+                                                 E5Work w) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    const uint32_t np = *w.npairs;
+    if (i >= np || i >= maxpairs) return;
+    if (!w.xyok[i]) return;
+    const uint32_t rb = w.pairs[i];
+    const uint32_t r = rb / B, h = rb - r * B;
+    e5_check_pair(pts, B, i, rb, r, h, w);
+}
+
+// multi-problem batches: the pair list is global and unordered, so each lane loads its sample's problem
+// (entry h / R of the slice) and point base itself
+__global__ __launch_bounds__(64) void k_multi_e5_check(const float4 *__restrict__ pts_all,
+                                                       const uint32_t *__restrict__ offsets,
+                                                       const MultiItem *__restrict__ items, uint32_t R, uint32_t B,
+                                                       uint32_t maxpairs, E5Work w) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    const uint32_t np = *w.npairs;
+    if (i >= np || i >= maxpairs) return;
+    if (!w.xyok[i]) return;
+    const uint32_t rb = w.pairs[i];
+    const uint32_t r = rb / B, h = rb - r * B;
+    e5_check_pair(pts_all + offsets[items[h / R].problem], B, i, rb, r, h, w);
+}
+
+// sample h's passing candidates: one -> its model, several -> listed for k_e5_order (which writes the
+// model); returns their number
+__device__ __forceinline__ int e5_select_sample(uint32_t B, uint32_t h, const E5Work &w, float *__restrict__ models) {
     int npass = 0, first = -1;
-    if (h < B) {
-        const int nr = w.nroots[h];
-        for (int r = 0; r < nr; r++)
-            if (w.flags[(size_t)r * B + h]) {
-                if (first < 0) first = r;
-                npass++;
-            }
-        if (npass == 1) {
-            const size_t rb = (size_t)first * B + h;
-#pragma unroll
-            for (int k = 0; k < 9; k++) models[(size_t)k * B + h] = w.cand[(size_t)k * 10 * B + rb];
-        } else if (npass > 1) {
-            w.multi[atomicAdd(w.nmulti, 1u)] = h;  // k_e5_order writes its model
+    const int nr = w.nroots[h];
+    for (int r = 0; r < nr; r++)
+        if (w.flags[(size_t)r * B + h]) {
+            if (first < 0) first = r;
+            npass++;
         }
-        counts[h] = npass ? 0 : -1;
+    if (npass == 1) {
+        const size_t rb = (size_t)first * B + h;
+#pragma unroll
+        for (int k = 0; k < 9; k++) models[(size_t)k * B + h] = w.cand[(size_t)k * 10 * B + rb];
+    } else if (npass > 1) {
+        w.multi[atomicAdd(w.nmulti, 1u)] = h;  // k_e5_order writes its model
     }
-    const uint32_t nvalid = npass ? 1u : 0u;
+    return npass;
+}
+
+// the wave's occupied slots behind *list_n (wave-aggregated atomic; every lane of the wave calls):
+// the calling lane's position, meaningful where nvalid
+__device__ __forceinline__ uint32_t e5_append_slot(uint32_t lane, uint32_t nvalid, uint32_t *__restrict__ list_n) {
     uint32_t incl = nvalid;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -424,7 +482,40 @@ __global__ __launch_bounds__(64) void k_e5_select(uint32_t B, E5Work w, float *_
     uint32_t base = 0;
     if (lane == 63 && total) base = atomicAdd(list_n, total);
     base = __shfl(base, 63, 64);
-    if (nvalid) list[base + incl - 1] = h;
+    return base + incl - 1;
+}
+
+__global__ __launch_bounds__(64) void k_e5_select(uint32_t B, E5Work w, float *__restrict__ models,
+                                                  int32_t *__restrict__ counts, uint32_t *__restrict__ list,
+                                                  uint32_t *__restrict__ list_n) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t h = blockIdx.x * 64 + lane;
+    int npass = 0;
+    if (h < B) {
+        npass = e5_select_sample(B, h, w, models);
+        counts[h] = npass ? 0 : -1;
+    }
+    const uint32_t nvalid = npass ? 1u : 0u;
+    const uint32_t pos = e5_append_slot(lane, nvalid, list_n);
+    if (nvalid) list[pos] = h;
+}
+
+// multi-problem batches: grid (R / 64, entries of the slice).  models: the slice's [9][B] (the round's
+// slab when one slice covers it, else a staging block copied into the slab); counts / sums / list /
+// list_n: the slice's first entry's in the round's slabs, slot0 its first slot.  A wave never spans two
+// entries (R is a multiple of 64): one atomic per wave on the entry's list_n.
+__global__ __launch_bounds__(64) void k_multi_e5_select(uint32_t R, E5Work w, float *__restrict__ models,
+                                                        uint32_t slot0, int32_t *__restrict__ counts,
+                                                        float *__restrict__ sums, uint32_t *__restrict__ list,
+                                                        uint32_t *__restrict__ list_n) {
+    const uint32_t lane = threadIdx.x, a = blockIdx.y;
+    const uint32_t h = a * R + blockIdx.x * 64 + lane, B = gridDim.y * R;
+    const int npass = e5_select_sample(B, h, w, models);
+    counts[h] = npass ? 0 : -1;  // an empty slot reads (-1, 0)
+    sums[h] = 0.f;
+    const uint32_t nvalid = npass ? 1u : 0u;
+    const uint32_t pos = e5_append_slot(lane, nvalid, list_n + a);
+    if (nvalid) list[(size_t)a * R + pos] = slot0 + h;
 }
 
 hipError_t launch_solve_e5(hipStream_t st, const float4 *pts, uint32_t n, const int32_t *samples_in,
@@ -458,6 +549,55 @@ hipError_t launch_solve_e5(hipStream_t st, const float4 *pts, uint32_t n, const 
     if (os != st) {
         if ((e = hipEventRecord(ev_out, os)) != hipSuccess) return e;
         if ((e = hipStreamWaitEvent(st, ev_out, 0)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// multi-problem batches (usac_kernels.h launch_multi_solve_e5): the workspace of a slice, then, when the
+// round takes several slices, the slice's model staging block [9][slice]
+size_t multi_e5_workspace_bytes(uint32_t A, uint32_t R, uint32_t slice) {
+    const size_t G = (size_t)A * R;
+    if (G <= slice) return e5_workspace_bytes((uint32_t)G);
+    return e5_align(e5_workspace_bytes(slice)) + sizeof(float) * 9 * (size_t)slice;
+}
+
+hipError_t launch_multi_solve_e5(hipStream_t st, const MultiRound &r) {
+    if (r.A == 0 || r.R == 0 || r.R % 64 || r.grid || !r.e5_ws || r.e5_slice < r.R || r.e5_slice % r.R ||
+        r.e5_slice > 0xFFFFFFFFu / 10)
+        return hipErrorInvalidValue;
+    const size_t G = (size_t)r.A * r.R;
+    hipError_t e = hipMemsetAsync(r.list_n, 0, sizeof(uint32_t) * r.A, st);
+    if (e != hipSuccess) return e;
+    const uint32_t per = r.e5_slice / r.R;  // entries per slice
+    const bool staged = r.A > per;
+    float *stage = reinterpret_cast<float *>(static_cast<char *>(r.e5_ws) + e5_align(e5_workspace_bytes(r.e5_slice)));
+    for (uint32_t a0 = 0; a0 < r.A; a0 += per) {
+        const uint32_t na = std::min(per, r.A - a0), B = na * r.R, g0 = a0 * r.R;
+        const E5Work w = e5_carve(r.e5_ws, B);
+        if ((e = hipMemsetAsync(w.npairs, 0, sizeof(uint32_t), st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(w.nmulti, 0, sizeof(uint32_t), st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(w.ndefer, 0, sizeof(uint32_t), st)) != hipSuccess) return e;
+        const dim3 ga(r.R / 64, na), g1(B / 64), g11(11 * (B / 64)), g10(10 * (B / 64));
+        const MultiItem *items = r.items + a0;
+        const int32_t *smp = r.samples_in ? r.samples_in + 5 * (size_t)g0 : nullptr;
+        float *models = staged ? stage : r.models;
+        auto *basis = r.growth ? k_multi_e5_basis<kProsac> : k_multi_e5_basis<kUniform>;
+        hipLaunchKernelGGL(basis, ga, dim3(64), 0, st, r.pts, r.offsets, items, smp, r.R, r.first_hyp, w, r.growth);
+        hipLaunchKernelGGL(k_e5_dets, g11, dim3(64), 0, st, B, w);
+        hipLaunchKernelGGL(k_e5_roots, g1, dim3(64), 0, st, B, w);
+        hipLaunchKernelGGL(k_e5_null, g10, dim3(64), 0, st, B, 10 * B, w);
+        hipLaunchKernelGGL(k_multi_e5_check, g10, dim3(64), 0, st, r.pts, r.offsets, items, r.R, B, 10 * B, w);
+        hipLaunchKernelGGL(k_multi_e5_select, ga, dim3(64), 0, st, r.R, w, models, g0, r.counts + g0, r.sums + g0,
+                           r.list + g0, r.list_n + a0);
+        // a multi context has one stream: the order kernels run on it (DESIGN.md §8b "Essential")
+        hipLaunchKernelGGL(k_e5_order, g1, dim3(64), 0, st, B, w, nullptr, e5_budget(), models);
+        hipLaunchKernelGGL(k_e5_order_tail, dim3(std::min(1024u, B / 64)), dim3(64), 0, st, B, w, nullptr, models);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (staged) {  // the slice's [9][B] into its columns of the round's [9][A R]
+            e = hipMemcpy2DAsync(r.models + g0, sizeof(float) * G, stage, sizeof(float) * B, sizeof(float) * B, 9,
+                                 hipMemcpyDeviceToDevice, st);
+            if (e != hipSuccess) return e;
+        }
     }
     return hipSuccess;
 }

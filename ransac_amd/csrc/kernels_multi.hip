@@ -11,9 +11,10 @@
 //   grid     : NAPSAC only, the problems' grid neighbours (MultiGrid, kernels_multi_grid.hip);
 //   models   : per-launch SoA slab over the A * R hypotheses of the launch, hypothesis h of
 //              active entry a at g = a * R + h -- H: [18][A R] (H then H^-1), F: [9][3 A R] with
-//              slot 3 g + j = the j-th valid model of the sample (seven_points.cpp root order);
-//   counts / sums : per slot, count -1 on an empty F slot;
-//   list / list_n : F only, per active entry the occupied slots (3 R entries each, any order).
+//              slot 3 g + j = the j-th valid model of the sample (seven_points.cpp root order),
+//              E: [9][A R], slot g = the sample's model (launch_multi_solve_e5, kernels_ess.hip);
+//   counts / sums : per slot, count -1 on an empty F / E slot;
+//   list / list_n : F and E, per active entry the occupied slots (spk R entries each, any order).
 //
 // Every per-hypothesis step is the single-problem path's device math (usac_device.hpp), so a
 // problem's models, counts and sums equal those of a usac_ctx over its points bit for bit: the
@@ -28,97 +29,14 @@
 #include <hip/hip_runtime.h>
 
 #include "usac_device.hpp"
+#include "usac_device_e5.hpp"
 #include "usac_kernels.h"
+#include "usac_multi_sampler.hpp"
 #include "usac_prosac.hpp"
 
 namespace usac {
 
 namespace {
-
-__device__ __forceinline__ DevSampler uniform_sampler(uint64_t seed) {
-    DevSampler ds{};
-    ds.seed = seed;
-    return ds;
-}
-
-// The sampler of an instantiation and the kernels' last argument under it: the growth functions
-// (PROSAC; unused by the uniform sampler) or the problems' grids (NAPSAC, kernels_multi_grid.hip).
-enum : int { kUniform = 0, kProsac = 1, kNapsac = 2 };
-template <int SAMPLER>
-struct SamplerArg {
-    using type = const uint32_t *__restrict__;
-};
-template <>
-struct SamplerArg<kNapsac> {
-    using type = MultiGrid;
-};
-
-// Lane h's sample of a round.  Uniform: draw_sample over n_p.  PROSAC (usac_prosac.hpp's closed form
-// over the problem's growth function g, the item's clock T and termination length L): t = T + h,
-//   t > T_N        : M distinct indices of [0, n)        (the reference past its growth table)
-//   s(t - 1) > L   : M distinct indices of [0, L]        (closed range, L < n; the subset is tested
-//                                                          before this call's increment)
-//   otherwise      : M - 1 distinct indices of [0, s(t) - 2] and point s(t) - 1
-// from the (seed, global hypothesis index) stream either way: the first M - 1 draws are
-// draw_unique's over the branch's range, the last one is its M-th step or the fixed point.
-// NAPSAC: draw_sample's NAPSAC branch over the problem's slices of the grid CSR (block-uniform bases):
-// the initial point uniform over the eligible points, M - 1 consecutive neighbours from a random
-// phase, uniform samples for a problem without an eligible point -- what a usac_ctx over the
-// problem's points draws after usac_set_cell_size and usac_set_device_sampler(NAPSAC).
-template <int M, bool PROSAC>
-__device__ __forceinline__ void stream_sample(const MultiItem &it, const uint32_t *__restrict__ g, uint32_t n,
-                                              uint64_t hyp, uint32_t h, int32_t (&s)[M]) {
-    if constexpr (!PROSAC) {
-        draw_sample<M>(uniform_sampler(it.seed), hyp, n, s);
-    } else {
-        uint64_t st = it.seed ^ (hyp * 0xD1B54A32D192ED03ull);
-        const uint32_t t = it.clock + h;
-        uint32_t range = n, last = 0;  // last != 0: the fixed point + 1
-        if (t <= kProsacGrowthMax) {
-            uint32_t s_prev, s_now;
-            prosac_subset_pair(g, n, (uint32_t)M, t, s_prev, s_now);
-            if (s_prev > it.term_len) {
-                range = it.term_len + 1;
-            } else {
-                range = s_now - 1;
-                last = s_now;
-            }
-        }
-        draw_unique<M - 1>(st, range, s);
-        if (last) {
-            s[M - 1] = (int32_t)last - 1;
-        } else {  // draw_unique<M>'s last step
-            int32_t v;
-            bool dup;
-            do {
-                const uint64_t r = splitmix64(st);
-                v = (int32_t)(((r >> 32) * (uint64_t)range) >> 32);
-                dup = false;
-#pragma unroll
-                for (int j = 0; j < M - 1; j++) dup |= (s[j] == v);
-            } while (dup);
-            s[M - 1] = v;
-        }
-    }
-}
-
-template <int M, int SAMPLER>
-__device__ __forceinline__ void multi_sample(const MultiItem &it, const typename SamplerArg<SAMPLER>::type &aux,
-                                             uint32_t base, uint32_t n, uint64_t hyp, uint32_t h, int32_t (&s)[M]) {
-    if constexpr (SAMPLER == kNapsac) {
-        DevSampler ds{};
-        ds.seed = it.seed;
-        ds.nap_n_eligible = aux.n_eligible[it.problem];
-        ds.nap_cell = aux.cell + base;
-        ds.nap_rank = aux.rank + base;
-        ds.nap_start = aux.start + base + it.problem;
-        ds.nap_members = aux.members + base;
-        ds.nap_eligible = aux.eligible + base;
-        draw_sample<M>(ds, hyp, n, s);
-    } else {
-        stream_sample<M, SAMPLER == kProsac>(it, aux + base, n, hyp, h, s);
-    }
-}
 
 // as kernels.hip store_h: H = v / v[8] in fp64, one cast, H^-1 by inv3x3
 __device__ __forceinline__ void multi_store_h(float *__restrict__ models, size_t stride, size_t g, const double *v) {
@@ -299,8 +217,15 @@ __global__ __launch_bounds__(64) void k_multi_score_h(const float4 *__restrict__
     sums[g] = sum;
 }
 
-// grid (3 R / 64, A): lanes walk the active entry's occupied-slot list (as k_score_f<1,
-// USAC_FUNDAMENTAL>); tiles past the list's end leave at once
+template <int EST>
+__device__ __forceinline__ float multi_epipolar_error(const float *f, const float4 &p) {
+    if constexpr (EST == USAC_ESSENTIAL) return essential_error(f, p.x, p.y, p.z, p.w);
+    else return fundamental_error(f, p.x, p.y, p.z, p.w);
+}
+
+// grid (SPK R / 64, A), SPK = 3 (F) or 1 (E) slots per sample: lanes walk the active entry's
+// occupied-slot list (as k_score_f<1, EST>); tiles past the list's end leave at once
+template <int EST>
 __global__ __launch_bounds__(64) void k_multi_score_f(const float4 *__restrict__ pts_all,
                                                       const uint32_t *__restrict__ offsets,
                                                       const MultiItem *__restrict__ items,
@@ -308,6 +233,7 @@ __global__ __launch_bounds__(64) void k_multi_score_f(const float4 *__restrict__
                                                       const uint32_t *__restrict__ list,
                                                       const uint32_t *__restrict__ list_n, float thr,
                                                       int32_t *__restrict__ counts, float *__restrict__ sums) {
+    constexpr uint32_t SPK = EST == USAC_FUNDAMENTAL ? 3 : 1;
     const uint32_t a = blockIdx.y;
     const uint32_t K = __builtin_amdgcn_readfirstlane(list_n[a]);
     const uint32_t i0 = blockIdx.x * 64;
@@ -315,9 +241,9 @@ __global__ __launch_bounds__(64) void k_multi_score_f(const float4 *__restrict__
     const uint32_t prob = items[a].problem;
     const uint32_t base = offsets[prob], n = offsets[prob + 1] - base;
     const float4 *__restrict__ pts = pts_all + base;
-    const size_t stride = 3 * (size_t)gridDim.y * R;
+    const size_t stride = SPK * (size_t)gridDim.y * R;
     const uint32_t i = i0 + threadIdx.x;
-    const uint32_t slot = list[3 * (size_t)a * R + (i < K ? i : K - 1)];
+    const uint32_t slot = list[SPK * (size_t)a * R + (i < K ? i : K - 1)];
     float f[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) f[k] = models[(size_t)k * stride + slot];
@@ -326,18 +252,17 @@ __global__ __launch_bounds__(64) void k_multi_score_f(const float4 *__restrict__
     uint32_t p = 0;
     for (; p + 4 <= n; p += 4) {
         const float4 a0 = pts[p], a1 = pts[p + 1], a2 = pts[p + 2], a3 = pts[p + 3];
-        const float e0 = fundamental_error(f, a0.x, a0.y, a0.z, a0.w);
-        const float e1 = fundamental_error(f, a1.x, a1.y, a1.z, a1.w);
-        const float e2 = fundamental_error(f, a2.x, a2.y, a2.z, a2.w);
-        const float e3 = fundamental_error(f, a3.x, a3.y, a3.z, a3.w);
+        const float e0 = multi_epipolar_error<EST>(f, a0);
+        const float e1 = multi_epipolar_error<EST>(f, a1);
+        const float e2 = multi_epipolar_error<EST>(f, a2);
+        const float e3 = multi_epipolar_error<EST>(f, a3);
         if (e0 < thr) { cnt++; sum += e0; }
         if (e1 < thr) { cnt++; sum += e1; }
         if (e2 < thr) { cnt++; sum += e2; }
         if (e3 < thr) { cnt++; sum += e3; }
     }
     for (; p < n; p++) {
-        const float4 q = pts[p];
-        const float e = fundamental_error(f, q.x, q.y, q.z, q.w);
+        const float e = multi_epipolar_error<EST>(f, pts[p]);
         if (e < thr) { cnt++; sum += e; }
     }
     if (i < K) {
@@ -427,10 +352,10 @@ __global__ __launch_bounds__(256) void k_multi_mask_prep(const float *__restrict
 }
 
 // one thread per point of the concatenated array: its problem by bisection of offsets, the
-// residual of usac_get_inliers under that problem's model, mask = err < thr
+// residual of usac_get_inliers under that problem's model (H, F or E), mask = err < thr
 __global__ __launch_bounds__(256) void k_multi_mask(const float4 *__restrict__ pts_all,
                                                     const uint32_t *__restrict__ offsets, uint32_t P,
-                                                    uint32_t n_total, const float *__restrict__ m18, int is_h,
+                                                    uint32_t n_total, const float *__restrict__ m18, int est,
                                                     float thr, uint8_t *__restrict__ mask) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_total) return;
@@ -444,7 +369,9 @@ __global__ __launch_bounds__(256) void k_multi_mask(const float4 *__restrict__ p
 #pragma unroll
     for (int k = 0; k < 18; k++) m[k] = m18[18 * (size_t)lo + k];
     const float4 p = pts_all[i];
-    const float err = is_h ? homography_error(m, m + 9, p.x, p.y, p.z, p.w) : fundamental_error(m, p.x, p.y, p.z, p.w);
+    const float err = est == USAC_HOMOGRAPHY    ? homography_error(m, m + 9, p.x, p.y, p.z, p.w)
+                      : est == USAC_FUNDAMENTAL ? fundamental_error(m, p.x, p.y, p.z, p.w)
+                                                : essential_error(m, p.x, p.y, p.z, p.w);
     mask[i] = err < thr ? 1 : 0;
 }
 
@@ -487,11 +414,19 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
             e = launch_multi_sprt_score(st, r);
             if (e != hipSuccess) return e;
         } else {
-            hipLaunchKernelGGL(k_multi_score_f, dim3(3 * r.R / 64, r.A), dim3(64), 0, st, r.pts, r.offsets, r.items,
+            hipLaunchKernelGGL(k_multi_score_f<USAC_FUNDAMENTAL>, dim3(3 * r.R / 64, r.A), dim3(64), 0, st, r.pts, r.offsets, r.items,
                                r.models, r.R, r.list, r.list_n, r.thr, r.counts, r.sums);
         }
         hipLaunchKernelGGL(k_multi_argmax, dim3(r.A), dim3(256), 0, st, r.items, r.counts, r.sums, r.models, 3 * r.R,
                            9, r.first_hyp, 3u, r.running, r.out);
+    } else if (r.estimator == USAC_ESSENTIAL) {  // one slot per sample; no SPRT, no NAPSAC
+        if (r.sprt || r.grid) return hipErrorInvalidValue;
+        const hipError_t e = launch_multi_solve_e5(st, r);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_multi_score_f<USAC_ESSENTIAL>, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.models,
+                           r.R, r.list, r.list_n, r.thr, r.counts, r.sums);
+        hipLaunchKernelGGL(k_multi_argmax, dim3(r.A), dim3(256), 0, st, r.items, r.counts, r.sums, r.models, r.R, 9,
+                           r.first_hyp, 1u, r.running, r.out);
     } else {
         return hipErrorInvalidValue;
     }
@@ -519,16 +454,19 @@ hipError_t launch_multi_draw(hipStream_t st, int estimator, const uint32_t *offs
                              uint32_t R, uint64_t first_hyp, const uint32_t *growth, const MultiGrid *mg, int32_t *out) {
     if (A == 0 || R == 0 || R % 64 || (growth && mg)) return hipErrorInvalidValue;
     const dim3 grid(R / 64, A);
-    if (estimator != USAC_HOMOGRAPHY && estimator != USAC_FUNDAMENTAL) return hipErrorInvalidValue;
+    if (estimator != USAC_HOMOGRAPHY && estimator != USAC_FUNDAMENTAL && estimator != USAC_ESSENTIAL)
+        return hipErrorInvalidValue;
     if (mg) {
+        if (estimator == USAC_ESSENTIAL) return hipErrorInvalidValue;
         auto *draw = estimator == USAC_HOMOGRAPHY ? k_multi_draw<4, kNapsac> : k_multi_draw<7, kNapsac>;
         hipLaunchKernelGGL(draw, grid, dim3(64), 0, st, offsets, items, R, first_hyp, *mg, out);
         return hipGetLastError();
     }
     auto *draw4 = growth ? k_multi_draw<4, kProsac> : k_multi_draw<4, kUniform>;
+    auto *draw5 = growth ? k_multi_draw<5, kProsac> : k_multi_draw<5, kUniform>;
     auto *draw7 = growth ? k_multi_draw<7, kProsac> : k_multi_draw<7, kUniform>;
-    hipLaunchKernelGGL(estimator == USAC_HOMOGRAPHY ? draw4 : draw7, grid, dim3(64), 0, st, offsets, items, R,
-                       first_hyp, growth, out);
+    hipLaunchKernelGGL(estimator == USAC_HOMOGRAPHY ? draw4 : estimator == USAC_ESSENTIAL ? draw5 : draw7, grid, dim3(64),
+                       0, st, offsets, items, R, first_hyp, growth, out);
     return hipGetLastError();
 }
 
@@ -537,7 +475,7 @@ hipError_t launch_multi_mask(hipStream_t st, int estimator, const float4 *pts, c
     const int is_h = estimator == USAC_HOMOGRAPHY;
     hipLaunchKernelGGL(k_multi_mask_prep, dim3((P + 255) / 256), dim3(256), 0, st, models, P, is_h, m18);
     hipLaunchKernelGGL(k_multi_mask, dim3((n_total + 255) / 256), dim3(256), 0, st, pts, offsets, P, n_total, m18,
-                       is_h, thr, mask);
+                       estimator, thr, mask);
     return hipGetLastError();
 }
 

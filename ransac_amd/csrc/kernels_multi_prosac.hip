@@ -12,8 +12,8 @@
 // One workgroup of 256 threads per active entry, launched after the round's argmax.  A workgroup
 // whose problem did not improve in this round leaves at once.  Otherwise it walks the problem's
 // points in tiles of 256, point i = tile + thread:
-//   flag_i    = residual(point i) < thr, the residual of usac_get_inliers / k_multi_mask (H^-1 by
-//               inv3x3 of the running model);
+//   flag_i    = residual(point i) < thr, the residual of usac_get_inliers / k_multi_mask (H, F or E; H^-1
+//               by inv3x3 of the running model);
 //   count_i   = inliers among points 0 .. i: the tiles before (a register every thread carries), the
 //               waves before in this tile (their ballots' popcounts through LDS), the lanes up to
 //               this one (the wave's ballot under the lane mask);
@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "usac_device.hpp"
+#include "usac_device_e5.hpp"
 #include "usac_kernels.h"
 
 namespace usac {
@@ -33,18 +34,21 @@ namespace {
 constexpr uint32_t kScanWaves = kMultiScanTile / 64;
 constexpr uint32_t kProsacMinLength = 20;  // min_termination_length (prosac_termination_criteria.hpp)
 
-template <bool IS_H>
+template <int EST>
 __device__ __forceinline__ bool scan_flag(const float4 *__restrict__ pts, uint32_t i, uint32_t n, const float *m,
                                           const float *mi, float thr) {
     if (i >= n) return false;
     const float4 p = pts[i];
-    const float err = IS_H ? homography_error(m, mi, p.x, p.y, p.z, p.w) : fundamental_error(m, p.x, p.y, p.z, p.w);
+    float err;
+    if constexpr (EST == USAC_HOMOGRAPHY) err = homography_error(m, mi, p.x, p.y, p.z, p.w);
+    else if constexpr (EST == USAC_FUNDAMENTAL) err = fundamental_error(m, p.x, p.y, p.z, p.w);
+    else err = essential_error(m, p.x, p.y, p.z, p.w);
     return err < thr;
 }
 
 }  // namespace
 
-template <bool IS_H>
+template <int EST>
 __global__ __launch_bounds__(kMultiScanTile) void k_multi_prosac_scan(
     const float4 *__restrict__ pts_all, const uint32_t *__restrict__ offsets, const MultiItem *__restrict__ items,
     const usac_record *__restrict__ running, uint64_t first_hyp, float thr, uint32_t *__restrict__ non_random,
@@ -67,12 +71,12 @@ __global__ __launch_bounds__(kMultiScanTile) void k_multi_prosac_scan(
     float m[9], mi[9] = {};
 #pragma unroll
     for (int k = 0; k < 9; k++) m[k] = rec->model[k];
-    if (IS_H) inv3x3(m, mi);
+    if (EST == USAC_HOMOGRAPHY) inv3x3(m, mi);
     uint32_t count0 = 0, ncand = 0;  // inliers / candidates of the tiles before (block-uniform)
     for (uint32_t tile = 0; tile < n; tile += kMultiScanTile) {
         const uint32_t i = tile + t;
-        const bool flag = scan_flag<IS_H>(pts, i, n, m, mi, thr);
-        const bool next = scan_flag<IS_H>(pts, i + 1, n, m, mi, thr);
+        const bool flag = scan_flag<EST>(pts, i, n, m, mi, thr);
+        const bool next = scan_flag<EST>(pts, i + 1, n, m, mi, thr);
         const unsigned long long bal = __ballot(flag);
         const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
         if (lane == 0) sh_inl[wave] = (uint32_t)__popcll(bal);
@@ -119,10 +123,13 @@ hipError_t launch_multi_prosac_scan(hipStream_t st, int estimator, const float4 
                                     uint32_t *cand_n) {
     if (A == 0) return hipErrorInvalidValue;
     if (estimator == USAC_HOMOGRAPHY)
-        hipLaunchKernelGGL(k_multi_prosac_scan<true>, dim3(A), dim3(kMultiScanTile), 0, st, pts, offsets, items, running,
+        hipLaunchKernelGGL(k_multi_prosac_scan<USAC_HOMOGRAPHY>, dim3(A), dim3(kMultiScanTile), 0, st, pts, offsets, items, running,
                            first_hyp, thr, non_random, cand, cand_n);
     else if (estimator == USAC_FUNDAMENTAL)
-        hipLaunchKernelGGL(k_multi_prosac_scan<false>, dim3(A), dim3(kMultiScanTile), 0, st, pts, offsets, items,
+        hipLaunchKernelGGL(k_multi_prosac_scan<USAC_FUNDAMENTAL>, dim3(A), dim3(kMultiScanTile), 0, st, pts, offsets, items,
+                           running, first_hyp, thr, non_random, cand, cand_n);
+    else if (estimator == USAC_ESSENTIAL)
+        hipLaunchKernelGGL(k_multi_prosac_scan<USAC_ESSENTIAL>, dim3(A), dim3(kMultiScanTile), 0, st, pts, offsets, items,
                            running, first_hyp, thr, non_random, cand, cand_n);
     else
         return hipErrorInvalidValue;

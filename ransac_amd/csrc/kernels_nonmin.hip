@@ -1396,6 +1396,9 @@ hipError_t launch_multi_polish(hipStream_t st, int estimator, const float4 *pts,
         case USAC_FUNDAMENTAL:
             hipLaunchKernelGGL(k_multi_polish<USAC_FUNDAMENTAL>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, lists, n_total, out, mask);
             break;
+        case USAC_ESSENTIAL:
+            hipLaunchKernelGGL(k_multi_polish<USAC_ESSENTIAL>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, lists, n_total, out, mask);
+            break;
         default:
             return hipErrorInvalidValue;
     }

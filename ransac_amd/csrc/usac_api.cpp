@@ -4047,6 +4047,10 @@ struct usac_multi {
     DevBuf grid;
     int grid_cs = 0;
     std::vector<uint32_t> grid_counts;  // 3 P
+    // Essential (ABI 21): the 5-point pipeline's workspace and the cap on a solve slice's samples
+    // (kMultiE5Slice, lowered by USAC_MULTI_E5_SLICE at creation)
+    DevBuf e5_ws;
+    uint32_t e5_slice = usac::kMultiE5Slice;
     std::string err;
 };
 
@@ -4069,6 +4073,15 @@ int pin_grow(usac_multi *mc, PinBlock &b, size_t need) {
 
 bool multi_round_ok(uint32_t R) { return R >= 64 && R <= 8192 && R % 64 == 0; }
 
+bool multi_is_e(const usac_multi *mc) { return mc->estimator == USAC_ESSENTIAL; }
+
+// what an essential context does not offer: refused before any device call
+int multi_no_essential(usac_multi *mc, const char *who) {
+    if (!multi_is_e(mc)) return USAC_OK;
+    return fail(mc, USAC_ERR_UNSUPPORTED, std::string(who) + ": not for the essential estimator (multi-problem batches "
+                                                              "of essential matrices have no LO, SPRT or NAPSAC)");
+}
+
 // device buffers and pinned staging for a round of A active problems x R hypotheses
 int multi_ensure(usac_multi *mc, uint32_t A, uint32_t R, bool host_samples) {
     const size_t G = (size_t)A * R, S = G * mc->spk;
@@ -4078,10 +4091,12 @@ int multi_ensure(usac_multi *mc, uint32_t A, uint32_t R, bool host_samples) {
     HIP_TRY(mc, mc->counts.reserve(sizeof(int32_t) * S));
     HIP_TRY(mc, mc->sums.reserve(sizeof(float) * S));
     HIP_TRY(mc, mc->out.reserve(sizeof(usac_record) * (size_t)A));
-    if (mc->estimator == USAC_FUNDAMENTAL) {
+    if (mc->estimator != USAC_HOMOGRAPHY) {
         HIP_TRY(mc, mc->list.reserve(sizeof(uint32_t) * S));
         HIP_TRY(mc, mc->list_n.reserve(sizeof(uint32_t) * (size_t)A));
     }
+    if (multi_is_e(mc))
+        HIP_TRY(mc, mc->e5_ws.reserve(usac::multi_e5_workspace_bytes(A, R, usac::multi_e5_slice_samples(mc->e5_slice, R))));
     return pin_grow(mc, mc->pin, (sizeof(usac::MultiItem) + sizeof(usac_record)) * (size_t)A);
 }
 
@@ -4107,6 +4122,8 @@ usac::MultiRound multi_round(usac_multi *mc, uint32_t A, uint32_t R, uint64_t fi
     r.list = mc->list.as<uint32_t>();
     r.list_n = mc->list_n.as<uint32_t>();
     r.out = mc->out.as<usac_record>();
+    r.e5_ws = mc->e5_ws.p;
+    r.e5_slice = usac::multi_e5_slice_samples(mc->e5_slice, R);
     return r;
 }
 
@@ -4489,7 +4506,8 @@ int multi_check_entries(usac_multi *mc, const uint32_t *problems, uint32_t A, co
 int multi_hook_args(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, const int32_t *samples, uint32_t R,
                     const uint64_t *seeds, int dlt_mode, uint32_t &A) {
     if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
-    if (dlt_mode != USAC_DLT_THIN && dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    if (!multi_is_e(mc) && dlt_mode != USAC_DLT_THIN && dlt_mode != USAC_DLT_NULLSPACE)
+        return fail(mc, USAC_ERR_ARG, "dlt_mode");
     const int rc = multi_listed(mc, problems, n_problems, A);
     if (rc) return rc;
     if (!samples && !seeds) return fail(mc, USAC_ERR_ARG, "seeds are required with the device sampler");
@@ -4571,7 +4589,10 @@ int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *see
     if (napsac && (sprt || prm->cell_size <= 0)) return fail(mc, USAC_ERR_ARG, "NAPSAC: cell_size > 0, no SPRT");
     const uint32_t R = prm->batch ? prm->batch : 256u;
     if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
-    if (prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE) return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    if (!multi_is_e(mc) && prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE)
+        return fail(mc, USAC_ERR_ARG, "dlt_mode");
+    if (multi_is_e(mc) && (lo || sprt || napsac))
+        return fail(mc, USAC_ERR_UNSUPPORTED, "the essential estimator: uniform or PROSAC sampler, no LO, no SPRT");
     const uint32_t P = mc->P, m = mc->m;
     if (prosac)
         for (uint32_t p = 0; p < P; p++)
@@ -4693,6 +4714,51 @@ int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *see
                                sizeof(usac_multi_output) / sizeof(float), prm->threshold, outs.pol, outs.mask);
 }
 
+// usac_multi_create / usac_multi_create_essential after their own checks (out is not NULL): the
+// arguments, before any device call, then the context
+int multi_create(usac_multi **out, int device, int estimator, const float *pts, const uint32_t *offsets, uint32_t P) {
+    const uint32_t m = estimator == USAC_FUNDAMENTAL ? 7 : estimator == USAC_ESSENTIAL ? 5 : 4;
+    if (P == 0 || P > usac::kMultiMaxActive || !pts || !offsets || offsets[0] != 0) return USAC_ERR_ARG;
+    for (uint32_t p = 0; p < P; p++)
+        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] < m) return USAC_ERR_ARG;
+    usac_multi *mc = new usac_multi();
+    mc->device = device;
+    mc->estimator = estimator;
+    mc->P = P;
+    mc->m = m;
+    mc->spk = estimator == USAC_FUNDAMENTAL ? 3 : 1;
+    mc->n_total = offsets[P];
+    if (const char *es = getenv("USAC_MULTI_E5_SLICE")) {  // tests: a lower cap on the 5-point solve's slices
+        const long v = atol(es);
+        if (v > 0 && v < (long)usac::kMultiE5Slice) mc->e5_slice = (uint32_t)v;
+    }
+    mc->offsets.assign(offsets, offsets + P + 1);
+    hipError_t e = hipSetDevice(device);
+    const char *what = "hipSetDevice";
+    if (e == hipSuccess) {
+        e = StreamPool::get().stream(&mc->stream);
+        what = "hipStreamCreate";
+    }
+    if (e == hipSuccess) {
+        e = mc->pts.reserve(sizeof(float) * 4 * (size_t)mc->n_total);
+        what = "hipMalloc points";
+    }
+    if (e == hipSuccess) e = mc->offs.reserve(sizeof(uint32_t) * ((size_t)P + 1));
+    if (e == hipSuccess) e = mc->running.reserve(sizeof(usac_record) * (size_t)P);
+    if (e == hipSuccess) {
+        e = hipMemcpy(mc->pts.p, pts, sizeof(float) * 4 * (size_t)mc->n_total, hipMemcpyHostToDevice);
+        what = "hipMemcpy";
+    }
+    if (e == hipSuccess) e = hipMemcpy(mc->offs.p, offsets, sizeof(uint32_t) * ((size_t)P + 1), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        fprintf(stderr, "usac_multi_create: %s: %s\n", what, hipGetErrorString(e));
+        usac_multi_destroy(mc);
+        return USAC_ERR_HIP;
+    }
+    *out = mc;
+    return USAC_OK;
+}
+
 // usac_multi_run with or without the polish (usac_multi_run_polished)
 int multi_run_uniform(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
                       usac_multi_polish_output *pol, uint8_t *mask) {
@@ -4733,42 +4799,13 @@ int usac_multi_create(usac_multi **out, int device, int estimator, const float *
     if (!out) return USAC_ERR_ARG;
     *out = nullptr;
     if (estimator != USAC_HOMOGRAPHY && estimator != USAC_FUNDAMENTAL) return USAC_ERR_UNSUPPORTED;
-    const uint32_t m = estimator == USAC_FUNDAMENTAL ? 7 : 4;
-    if (P == 0 || P > usac::kMultiMaxActive || !pts || !offsets || offsets[0] != 0) return USAC_ERR_ARG;
-    for (uint32_t p = 0; p < P; p++)
-        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] < m) return USAC_ERR_ARG;
-    usac_multi *mc = new usac_multi();
-    mc->device = device;
-    mc->estimator = estimator;
-    mc->P = P;
-    mc->m = m;
-    mc->spk = estimator == USAC_FUNDAMENTAL ? 3 : 1;
-    mc->n_total = offsets[P];
-    mc->offsets.assign(offsets, offsets + P + 1);
-    hipError_t e = hipSetDevice(device);
-    const char *what = "hipSetDevice";
-    if (e == hipSuccess) {
-        e = StreamPool::get().stream(&mc->stream);
-        what = "hipStreamCreate";
-    }
-    if (e == hipSuccess) {
-        e = mc->pts.reserve(sizeof(float) * 4 * (size_t)mc->n_total);
-        what = "hipMalloc points";
-    }
-    if (e == hipSuccess) e = mc->offs.reserve(sizeof(uint32_t) * ((size_t)P + 1));
-    if (e == hipSuccess) e = mc->running.reserve(sizeof(usac_record) * (size_t)P);
-    if (e == hipSuccess) {
-        e = hipMemcpy(mc->pts.p, pts, sizeof(float) * 4 * (size_t)mc->n_total, hipMemcpyHostToDevice);
-        what = "hipMemcpy";
-    }
-    if (e == hipSuccess) e = hipMemcpy(mc->offs.p, offsets, sizeof(uint32_t) * ((size_t)P + 1), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        fprintf(stderr, "usac_multi_create: %s: %s\n", what, hipGetErrorString(e));
-        usac_multi_destroy(mc);
-        return USAC_ERR_HIP;
-    }
-    *out = mc;
-    return USAC_OK;
+    return multi_create(out, device, estimator, pts, offsets, P);
+}
+
+int usac_multi_create_essential(usac_multi **out, int device, const float *pts, const uint32_t *offsets, uint32_t P) {
+    if (!out) return USAC_ERR_ARG;
+    *out = nullptr;
+    return multi_create(out, device, USAC_ESSENTIAL, pts, offsets, P);
 }
 
 void usac_multi_destroy(usac_multi *mc) {
@@ -4782,7 +4819,7 @@ void usac_multi_destroy(usac_multi *mc) {
         b->release();
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
                       &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
-                      &mc->pol_out, &mc->lo_state})
+                      &mc->pol_out, &mc->lo_state, &mc->e5_ws})
         b->release();
     if (mc->stream) StreamPool::get().give_back(mc->stream);
     delete mc;
@@ -4946,6 +4983,7 @@ int usac_lo_draw(uint64_t seed, uint64_t draw, uint32_t k, uint32_t max, int32_t
 int usac_multi_lo(usac_multi *mc, const usac_params *prm, int reset, const uint64_t *seeds, usac_record *recs,
                   usac_multi_lo_output *lo) {
     if (!mc || !prm || !recs) return USAC_ERR_ARG;
+    if (const int no = multi_no_essential(mc, "usac_multi_lo")) return no;
     int rc = multi_lo_check(mc, prm, "usac_multi_lo");
     if (rc) return rc;
     const uint32_t P = mc->P;
@@ -4966,6 +5004,7 @@ int usac_multi_run_lo(usac_multi *mc, const usac_params *prm, const uint64_t *se
                       usac_multi_lo_output *lo, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
                       uint8_t *mask) {
     if (!mc || !prm || !out) return USAC_ERR_ARG;
+    if (const int no = multi_no_essential(mc, "usac_multi_run_lo")) return no;
     int rc = multi_lo_check(mc, prm, "usac_multi_run_lo");
     if (rc) return rc;
     if (prm->sampler != USAC_SAMPLER_UNIFORM && prm->sampler != USAC_SAMPLER_PROSAC)
@@ -4994,6 +5033,7 @@ int usac_multi_sprt_update(int estimator, uint32_t n_points, uint32_t m, uint32_
 
 int usac_multi_sprt_setup(usac_multi *mc, const uint32_t *pool_seeds) {
     if (!mc) return USAC_ERR_ARG;
+    if (const int no = multi_no_essential(mc, "usac_multi_sprt_setup")) return no;
     HIP_TRY(mc, hipSetDevice(mc->device));
     return multi_sprt_setup(mc, pool_seeds);
 }
@@ -5003,6 +5043,7 @@ int usac_multi_hypothesize_score_sprt(usac_multi *mc, const uint32_t *problems, 
                                       float thr, int dlt_mode, const double *eps_delta, int32_t *counts, float *sums,
                                       usac_record *best, usac_multi_sprt_stats *stats, uint32_t *starts) {
     if (!mc) return USAC_ERR_ARG;
+    if (const int no = multi_no_essential(mc, "usac_multi_hypothesize_score_sprt")) return no;
     uint32_t A = 0;
     int rc = multi_hook_args(mc, problems, n_problems, samples, R, seeds, dlt_mode, A);
     if (rc) return rc;
@@ -5053,6 +5094,7 @@ int usac_multi_run_sprt(usac_multi *mc, const usac_params *prm, const uint64_t *
                         usac_multi_sprt_output *sprt, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
                         uint8_t *mask) {
     if (!mc || !prm || !out) return USAC_ERR_ARG;
+    if (const int no = multi_no_essential(mc, "usac_multi_run_sprt")) return no;
     if (prm->lo != USAC_LO_NONE)
         return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run_sprt: no LO with SPRT (LO: usac_multi_run_lo)");
     if (!prm->sprt) return fail(mc, USAC_ERR_ARG, "usac_multi_run_sprt: params->sprt must be set");
@@ -5065,6 +5107,7 @@ int usac_multi_run_sprt(usac_multi *mc, const usac_params *prm, const uint64_t *
 int usac_multi_grid(usac_multi *mc, int cell_size, uint32_t *n_cells, uint32_t *cell, uint32_t *rank, uint32_t *start,
                     int32_t *members, int32_t *eligible, uint32_t *n_eligible) {
     if (!mc) return USAC_ERR_ARG;
+    if (const int no = multi_no_essential(mc, "usac_multi_grid")) return no;
     const int rc = multi_grid_ensure(mc, cell_size);
     if (rc) return rc;
     const size_t N = mc->n_total, P = mc->P;
@@ -5083,6 +5126,7 @@ int usac_multi_grid(usac_multi *mc, int cell_size, uint32_t *n_cells, uint32_t *
 int usac_multi_draw_samples_napsac(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t R,
                                    const uint64_t *seeds, uint64_t first_hyp, int cell_size, int32_t *out) {
     if (!mc) return USAC_ERR_ARG;
+    if (const int no = multi_no_essential(mc, "usac_multi_draw_samples_napsac")) return no;
     if (!seeds || !out) return fail(mc, USAC_ERR_ARG, "seeds and out");
     if (cell_size <= 0) return fail(mc, USAC_ERR_ARG, "grid cell_size must be > 0");
     if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "R must be a multiple of 64 in 64..8192");
@@ -5108,6 +5152,7 @@ int usac_multi_hypothesize_score_napsac(usac_multi *mc, const uint32_t *problems
                                         const uint64_t *seeds, uint64_t first_hyp, float thr, int dlt_mode,
                                         int cell_size, int32_t *counts, float *sums, usac_record *best) {
     if (!mc) return USAC_ERR_ARG;
+    if (const int no = multi_no_essential(mc, "usac_multi_hypothesize_score_napsac")) return no;
     if (cell_size <= 0) return fail(mc, USAC_ERR_ARG, "grid cell_size must be > 0");
     uint32_t A = 0;
     int rc = multi_hook_args(mc, problems, n_problems, nullptr, R, seeds, dlt_mode, A);
@@ -5129,6 +5174,7 @@ int usac_multi_hypothesize_score_napsac(usac_multi *mc, const uint32_t *problems
 int usac_multi_run_napsac(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
                           usac_multi_lo_output *lo, usac_multi_polish_output *pol, uint8_t *mask) {
     if (!mc || !prm || !out) return USAC_ERR_ARG;
+    if (const int no = multi_no_essential(mc, "usac_multi_run_napsac")) return no;
     if (prm->sampler != USAC_SAMPLER_NAPSAC) return fail(mc, USAC_ERR_ARG, "usac_multi_run_napsac: the NAPSAC sampler");
     if (prm->neighbors != USAC_NEIGHBORS_GRID)
         return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run_napsac: grid neighbours only (no KNN NAPSAC)");

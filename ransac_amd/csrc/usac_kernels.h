@@ -343,7 +343,7 @@ struct MultiItem {
 };
 static_assert(sizeof(MultiItem) == 24, "MultiItem: a multiple of 8 bytes");
 struct MultiRound {
-    int estimator;  // USAC_HOMOGRAPHY | USAC_FUNDAMENTAL
+    int estimator;  // USAC_HOMOGRAPHY | USAC_FUNDAMENTAL | USAC_ESSENTIAL
     int nullspace;  // H: USAC_DLT_NULLSPACE
     const float4 *pts;
     const uint32_t *offsets;
@@ -352,17 +352,31 @@ struct MultiRound {
     const int32_t *samples_in;  // nullable: A x R x m indices local to each problem; else the device sampler
     uint64_t first_hyp;
     float thr;
-    float *models;              // SoA slab over the launch: H [18][A R], F [9][3 A R]
+    float *models;              // SoA slab over the launch: H [18][A R], F [9][3 A R], E [9][A R]
     int32_t *counts;            // A x R x spk
     float *sums;
-    uint32_t *list, *list_n;    // F: occupied slots, 3 R per entry, and their numbers [A]
+    uint32_t *list, *list_n;    // F, E: occupied slots, spk R per entry, and their numbers [A]
     usac_record *running;       // nullable, indexed by problem: the round's best is folded into it
     usac_record *out;           // [A]: the merged record (running given) or the round's record
     const uint32_t *growth;     // nullable: the PROSAC sampler (items' clock / term_len) over the growth
                                 // functions, n_total values, problem p's at growth + offsets[p]
     const struct MultiSprt *sprt;  // nullable: SPRT verification (kernels_multi_sprt.hip) in place of the score launch
     const struct MultiGrid *grid;  // nullable (not with growth): the NAPSAC sampler over the problems' grids
+    // E: the 5-point pipeline's workspace, multi_e5_workspace_bytes(A, R, e5_slice), and the samples per
+    // solve slice (a multiple of R; multi_e5_slice_samples)
+    void *e5_ws;
+    uint32_t e5_slice;
 };
+// The 5-point solve of an essential round (kernels_ess.hip): launch_solve_e5's staged pipeline over the
+// A R samples, sample g = a R + h, in slices of whole active entries of at most r.e5_slice samples (the
+// pair code r B + h is a uint32: 10 * slice < 2^32).  Models, counts (0 / -1), sums (0) and the entries'
+// occupied-slot lists go into the round's slabs; the results do not depend on the slice.  Everything on
+// the one stream.  kMultiE5Slice: the default cap, ~160 MB of workspace.
+constexpr uint32_t kMultiE5Slice = 131072;
+// the samples per slice for a cap: whole entries, at least one
+inline uint32_t multi_e5_slice_samples(uint32_t cap, uint32_t R) { return cap < R ? R : cap / R * R; }
+size_t multi_e5_workspace_bytes(uint32_t A, uint32_t R, uint32_t slice);
+hipError_t launch_multi_solve_e5(hipStream_t st, const MultiRound &r);
 // Grid neighbours of every problem (kernels_multi_grid.hip, one workgroup per problem): the CSR of
 // usac::GridNeighbors over each problem's points, problem-local at the points' offsets -- cell, rank,
 // members, eligible (points with >= m neighbours, ascending): n_total values each, problem p's at

@@ -3,6 +3,10 @@
 
   python tools/bench_multi.py --pairs 512 --points 1000 --round 256 --estimator homography
 
+--estimator essential takes calibrated pairs (synthetic.fundamental_points(normalized=True), threshold
+0.002) through MultiContext.essential; (b) is then the loop over Context(Essential) objects.  It offers
+the plain run, --polish and --sampler prosac.
+
 (a) MultiContext.run: batch-granular RANSAC over all pairs, one launch chain per round.
 (b) the same schedule -- per pair, rounds of R hypotheses until min(max_iterations, standard bound)
     is reached -- as a loop over one Context per pair with hypothesize_score(per_hypothesis=False),
@@ -67,6 +71,9 @@ from ransac_amd import synthetic  # noqa: E402
 
 
 def make_pairs(estimator, pairs, points, ratio, quality_sorted=False, cluster=None):
+    if estimator == "essential":  # calibrated coordinates (K^-1 x), cfg4's generator
+        return [synthetic.fundamental_points(n=points, inlier_ratio=ratio, seed=1000 + p, prosac_order=quality_sorted,
+                                             normalized=True)[0] for p in range(pairs)]
     if cluster is not None:
         return [synthetic.homography_points(n=points, inlier_ratio=ratio, seed=1000 + p, cluster=(500, 500, cluster))[0]
                 for p in range(pairs)]
@@ -450,7 +457,9 @@ def main():
     ap.add_argument("--pairs", type=int, default=512)
     ap.add_argument("--points", type=int, default=1000)
     ap.add_argument("--round", type=int, default=256, dest="R")
-    ap.add_argument("--estimator", choices=["homography", "fundamental"], default="homography")
+    ap.add_argument("--estimator", choices=["homography", "fundamental", "essential"], default="homography",
+                    help="essential: MultiContext.essential over calibrated pairs, threshold 0.002; the plain run, "
+                         "--polish and --sampler prosac")
     ap.add_argument("--inlier-ratio", type=float, default=0.3)
     ap.add_argument("--max-iterations", type=int, default=2048)
     ap.add_argument("--dlt", choices=["thin", "nullspace"], default="nullspace")
@@ -482,16 +491,21 @@ def main():
     if a.cluster is not None and a.estimator != "homography":
         ap.error("--cluster applies to homography pairs")
 
-    est = usac.ESTIMATOR.Homography if a.estimator == "homography" else usac.ESTIMATOR.Fundamental
-    thr, prob = 2.0, 0.95
+    essential = a.estimator == "essential"
+    if essential and (a.lo or a.sprt or a.sampler == "napsac"):
+        ap.error("--estimator essential: the plain run, --polish and --sampler prosac (no LO, SPRT or NAPSAC)")
+    est = {"homography": usac.ESTIMATOR.Homography, "fundamental": usac.ESTIMATOR.Fundamental,
+           "essential": usac.ESTIMATOR.Essential}[a.estimator]
+    thr, prob = (0.002 if essential else 2.0), 0.95
     sets = make_pairs(a.estimator, a.pairs, a.points, a.inlier_ratio, quality_sorted=a.sampler == "prosac",
                       cluster=a.cluster)
-    model = usac.Model(thr, 4 if a.estimator == "homography" else 7, prob, 5, est, usac.SAMPLER.Uniform)
+    model = usac.Model(thr, {"homography": 4, "fundamental": 7, "essential": 5}[a.estimator], prob, 5, est,
+                       usac.SAMPLER.Uniform)
     model.max_iterations, model.batch, model.seed = a.max_iterations, a.R, 1
     model.setDLTMode(usac.DLT.NULLSPACE if a.dlt == "nullspace" else usac.DLT.THIN)
     seeds = [model.seed + p for p in range(a.pairs)]
 
-    mc = usac.MultiContext(est, sets)
+    mc = usac.MultiContext.essential(sets) if essential else usac.MultiContext(est, sets)
     if a.sampler == "napsac":
         return main_napsac(a, mc, model, est)
     if a.sprt:
@@ -502,7 +516,8 @@ def main():
         return main_prosac(a, mc, model, est)
     ctxs = [usac.Context(est, p) for p in sets]
     for c in ctxs:
-        c.set_dlt_mode(model.dlt_mode)
+        if not essential:
+            c.set_dlt_mode(model.dlt_mode)
         c.set_timing(False)
 
     def run_a():
@@ -534,6 +549,7 @@ def main():
             "loop_spread_ms": round(sb, 3), "ratio_loop_over_multi": round(mb / ma, 2),
             "multi_faster_beyond_spread": bool(mb - ma > max(sa, sb)),
             "hypotheses": int(sum(x[1] for x in ra)) * a.R, "mean_rounds": round(float(np.mean([x[1] for x in ra])), 2),
+            "mean_best_inliers": round(float(np.mean([x[0] for x in ra])), 2),
             "best_inliers_agree": bool(agree)}
     text = json.dumps(line)
     print(text)
