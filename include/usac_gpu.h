@@ -68,7 +68,9 @@
  *                                  usac_multi_draw_samples_napsac / usac_multi_hypothesize_score_napsac
  *                                  exposing its parts;
  *                                  ABI 21: usac_multi_create_essential, multi contexts of essential-matrix
- *                                  problems (5-point solver): rounds, runs, masks, the polish and PROSAC
+ *                                  problems (5-point solver): rounds, runs, masks, the polish and PROSAC;
+ *                                  ABI 22: usac_multi_set_thresholds / usac_multi_get_thresholds, one inlier
+ *                                  threshold per problem of a multi context in place of the calls' scalar
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -83,7 +85,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 21
+#define USAC_ABI_VERSION 22
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -540,13 +542,29 @@ int usac_multi_create_essential(usac_multi **out, int device, const float *pts, 
 void usac_multi_destroy(usac_multi *mc);
 const char *usac_multi_last_error(const usac_multi *mc);
 uint32_t usac_multi_num_problems(const usac_multi *mc);
+/* Per-problem thresholds (ABI 22).  thr: P finite values > 0, problem p's inlier threshold in the units of
+ * its own coordinates (E: the squared Sampson distance in calibrated coordinates, so (t_px / f)^2 for a
+ * pixel tolerance t_px and focal length f); NULL clears them.  While they are set, every usac_multi_*
+ * call that reads a threshold -- the rounds, the runs, usac_multi_inliers, usac_multi_polish (its host
+ * path for a problem past the caps included), usac_multi_prosac_scan, usac_multi_lo -- uses thr[p] for
+ * problem p, whatever its place in an active list, and does not read its scalar (the thr argument or
+ * params->threshold); the LO threshold of problem p starts at thr[p], returns to thr[p] and steps by
+ * (thr[p] * lo_threshold_multiplier - thr[p]) / lo_iterative_iterations.  They are state of the context: they persist from call to call
+ * until cleared, and after a clear every call behaves as before ABI 22.  usac_multi_lo's persistent
+ * state is not touched: reset it after changing the thresholds.
+ * USAC_ERR_ARG for a NULL mc, or a value that is not finite and > 0 (the context and the thresholds set
+ * before stay as they were; usac_multi_last_error names the first bad problem). */
+int usac_multi_set_thresholds(usac_multi *mc, const float *thr);
+/* Returns 1 and fills out[P] if thresholds are set, 0 (out untouched) if not, USAC_ERR_ARG on a NULL mc. */
+int usac_multi_get_thresholds(const usac_multi *mc, float *out);
 /* One round.  problems: the active list, n_problems problem ids in any order (NULL: all P in order,
  * n_problems = P or 0).  samples: host n_problems x R x m indices local to each problem (out of
  * range: USAC_ERR_ARG), or NULL for the device sampler with seeds[i] for problems[i].  R: a multiple
  * of 64 in 64..8192 (a wave never spans two problems).  counts / sums (nullable): n_problems x R x S,
  * S = 3 for the fundamental solver, else 1 (essential: count -1 on a sample without a model).  best (nullable): n_problems records, each the round's
  * best of its problem under Score::bigger with the earliest (sample, slot) on exact ties,
- * hyp_index = first_hyp + sample. */
+ * hyp_index = first_hyp + sample.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and thr is not read. */
 int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint32_t n_problems,
                                  const int32_t *samples, uint32_t R, const uint64_t *seeds, uint64_t first_hyp,
                                  float thr, int dlt_mode, int32_t *counts, float *sums, usac_record *best);
@@ -562,10 +580,12 @@ int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint3
  * USAC_ERR_UNSUPPORTED here -- and it stops at the best minimal model; usac_multi_run_polished adds
  * the run's non-minimal polish.
  * Reads threshold, desired_prob, max_iterations, dlt_mode, seed and batch (= R, 0 = 256).
- * out: P results. */
+ * out: P results.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and params->threshold is not read. */
 int usac_multi_run(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out);
 /* Per-point inlier flags of each problem's model (models P x 9, mask N_total bytes of 0 / 1, counts
- * P, nullable) from the residual of usac_get_inliers; for H, H^-1 is the device inv3x3 of the given H. */
+ * P, nullable) from the residual of usac_get_inliers; for H, H^-1 is the device inv3x3 of the given H.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and thr is not read. */
 int usac_multi_inliers(usac_multi *mc, const float *models, float thr, uint8_t *mask, int32_t *counts);
 
 /* One problem's result of usac_multi_polish (ABI 16). */
@@ -588,7 +608,8 @@ typedef struct usac_multi_polish_output {
  * <= 4096 points; a problem past either cap is polished through a temporary single context over its
  * points (same result, a host loop for that problem only).
  * out: P results.  mask (nullable): N_total bytes of 0 / 1, the final getInliers of out[p].model.
- * NULL mc, models or out: USAC_ERR_ARG before any device call. */
+ * NULL mc, models or out: USAC_ERR_ARG before any device call.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and thr is not read. */
 int usac_multi_polish(usac_multi *mc, const float *models, float thr,
                       usac_multi_polish_output *out, uint8_t *mask);
 
@@ -597,7 +618,8 @@ int usac_multi_polish(usac_multi *mc, const float *models, float thr,
  * usac_multi_polish (a problem without a model: USAC_ERR_NO_MODEL in both).  The remaining deviations
  * from Ransac::run are usac_multi_run's: no NAPSAC (PROSAC: usac_multi_run_prosac, LO:
  * usac_multi_run_lo, SPRT: usac_multi_run_sprt), batch-granular termination.
- * NULL mc, params, out or pol: USAC_ERR_ARG before any device call. */
+ * NULL mc, params, out or pol: USAC_ERR_ARG before any device call.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and params->threshold is not read. */
 int usac_multi_run_polished(usac_multi *mc, const usac_params *params, const uint64_t *seeds,
                             usac_multi_output *out, usac_multi_polish_output *pol, uint8_t *mask);
 
@@ -657,7 +679,8 @@ typedef struct usac_multi_prosac_output {
  * params or out -- all before any device call.
  * out: P results as usac_multi_run's (bound: the last scan's, max_iterations if none ran).  pro
  * (nullable): P states.  pol (nullable): the polish of usac_multi_run_polished from the device's running
- * records, with mask (nullable, read only with pol). */
+ * records, with mask (nullable, read only with pol).
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and params->threshold is not read. */
 int usac_multi_run_prosac(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
                           usac_multi_prosac_output *pro, usac_multi_polish_output *pol, uint8_t *mask);
 /* For tests: one termination scan of every problem, models (P x 9) taken as new bests found at
@@ -665,7 +688,8 @@ int usac_multi_run_prosac(usac_multi *mc, const usac_params *params, const uint6
  * state persists in the context from call to call; reset != 0 (and any usac_multi_run_prosac) starts
  * it afresh from params->desired_prob and ->max_iterations.  bound / term_len: P values after the
  * scan.  n_cand (nullable): P candidate numbers; cand (nullable): N_total / 2 + P pairs (i, count),
- * problem p's from pair offsets[p] / 2 + p, ascending i.  Every n_p > 20. */
+ * problem p's from pair offsets[p] / 2 + p, ascending i.  Every n_p > 20.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and params->threshold is not read. */
 int usac_multi_prosac_scan(usac_multi *mc, const usac_params *params, int reset, const float *models,
                            const uint32_t *hyp_count, const uint32_t *largest, uint32_t *bound, uint32_t *term_len,
                            uint32_t *n_cand, uint32_t *cand);
@@ -708,7 +732,8 @@ typedef struct usac_multi_lo_output {
  * lo_iterative_iterations and lo_threshold_multiplier -- not sampler, batch, dlt_mode, desired_prob or
  * max_iterations.  USAC_ERR_UNSUPPORTED for USAC_LO_GC or params->sprt; USAC_ERR_ARG for USAC_LO_NONE,
  * lo_sample_size 0 or > 64, lo_iterative_iterations 0, NULL mc, params or recs -- all before any device
- * call. */
+ * call.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and params->threshold is not read. */
 int usac_multi_lo(usac_multi *mc, const usac_params *params, int reset, const uint64_t *seeds,
                   usac_record *recs, usac_multi_lo_output *lo);
 
@@ -725,7 +750,8 @@ int usac_multi_lo(usac_multi *mc, const usac_params *params, int reset, const ui
  * or > 64, lo_iterative_iterations 0, USAC_SAMPLER_NAPSAC, a bad batch or dlt_mode, NULL mc, params or
  * out, and with PROSAC any n_p <= 20 -- all before any device call.
  * out / pol / mask as usac_multi_run_prosac's; lo (nullable): P LO states; pro (nullable) is written
- * only with PROSAC. */
+ * only with PROSAC.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and params->threshold is not read. */
 int usac_multi_run_lo(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
                       usac_multi_lo_output *lo, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
                       uint8_t *mask);
@@ -779,7 +805,8 @@ int usac_multi_sprt_setup(usac_multi *mc, const uint32_t *pool_seeds);
  * starts (nullable): n_problems x R x S first pool positions, UINT32_MAX on an empty F slot.
  * USAC_ERR_ARG also for an epsilon or delta outside (0, 1) or delta >= epsilon -- before any device
  * call.  The certificate's margin and climb limit are usac_set_sprt's, its budget taken at each
- * problem's n_p, with the same USAC_SPRT_CERT_MARGIN / USAC_SPRT_CERT_CLIMB test overrides. */
+ * problem's n_p, with the same USAC_SPRT_CERT_MARGIN / USAC_SPRT_CERT_CLIMB test overrides.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and thr is not read. */
 int usac_multi_hypothesize_score_sprt(usac_multi *mc, const uint32_t *problems, uint32_t n_problems,
                                       const int32_t *samples, uint32_t R, const uint64_t *seeds, uint64_t first_hyp,
                                       float thr, int dlt_mode, const double *eps_delta, int32_t *counts, float *sums,
@@ -823,7 +850,8 @@ int usac_multi_sprt_update(int estimator, uint32_t n_points, uint32_t m, uint32_
  * out, and with PROSAC any n_p <= 20; USAC_ERR_UNSUPPORTED for params->lo != USAC_LO_NONE -- all before
  * any device call.
  * out / pro / pol / mask as usac_multi_run_prosac's (pro is written only with PROSAC; the polish reads
- * only the record's model); sprt (nullable): P states. */
+ * only the record's model); sprt (nullable): P states.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and params->threshold is not read. */
 int usac_multi_run_sprt(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
                         usac_multi_sprt_output *sprt, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
                         uint8_t *mask);
@@ -848,7 +876,8 @@ int usac_multi_grid(usac_multi *mc, int cell_size, uint32_t *n_cells, uint32_t *
 int usac_multi_draw_samples_napsac(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t R,
                                    const uint64_t *seeds, uint64_t first_hyp, int cell_size, int32_t *out);
 
-/* usac_multi_hypothesize_score with that sampler (seeds required; no host samples). */
+/* usac_multi_hypothesize_score with that sampler (seeds required; no host samples).
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and thr is not read. */
 int usac_multi_hypothesize_score_napsac(usac_multi *mc, const uint32_t *problems, uint32_t n_problems, uint32_t R,
                                         const uint64_t *seeds, uint64_t first_hyp, float thr, int dlt_mode,
                                         int cell_size, int32_t *counts, float *sums, usac_record *best);
@@ -863,7 +892,8 @@ int usac_multi_hypothesize_score_napsac(usac_multi *mc, const uint32_t *problems
  * usac_multi_run_lo refuses, NULL mc, params or out; USAC_ERR_UNSUPPORTED for ->neighbors other than
  * USAC_NEIGHBORS_GRID (KNN NAPSAC is not built), params->sprt, USAC_LO_GC -- all before any device call
  * (the grid build included).  out / pol / mask as usac_multi_run_prosac's; lo (nullable): P LO states,
- * written only with LO. */
+ * written only with LO.
+ * While usac_multi_set_thresholds is in effect (ABI 22) problem p uses its own threshold and params->threshold is not read. */
 int usac_multi_run_napsac(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
                           usac_multi_lo_output *lo, usac_multi_polish_output *pol, uint8_t *mask);
 

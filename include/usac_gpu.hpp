@@ -573,6 +573,24 @@ public:
         if (rc != USAC_OK) throw Error(rc, std::string(what) + ": " + usac_multi_last_error(mc_));
     }
 
+    // usac_multi_set_thresholds (ABI 22): one inlier threshold per problem, in the units of its own
+    // coordinates.  While set, every member below that takes a threshold (thr, or the model's) uses
+    // problem p's value and ignores its own; they persist until clear_thresholds().  Throws
+    // USAC_ERR_ARG (nothing changed) for a wrong length or a value that is not finite and > 0.
+    void set_thresholds(const std::vector<float> &thr) const {
+        if (thr.size() != problems()) throw Error(USAC_ERR_ARG, "set_thresholds: one threshold per problem");
+        check(usac_multi_set_thresholds(mc_, thr.data()), "MultiContext::set_thresholds");
+    }
+    void clear_thresholds() const { check(usac_multi_set_thresholds(mc_, nullptr), "MultiContext::clear_thresholds"); }
+    // the thresholds in effect; empty: none
+    std::vector<float> thresholds() const {
+        std::vector<float> out(problems());
+        const int rc = usac_multi_get_thresholds(mc_, out.data());
+        if (rc < 0) check(rc, "MultiContext::thresholds");
+        if (rc == 0) out.clear();
+        return out;
+    }
+
     // one round of R hypotheses (a multiple of 64 in 64..8192) for the listed problems (empty: all,
     // in order), device sampler keyed by seeds[i] for problems[i]; with per_hypothesis the counts
     // and sums of every slot come back too

@@ -202,6 +202,7 @@ ABI_SYMBOLS = [
     "usac_multi_sprt_setup", "usac_multi_hypothesize_score_sprt", "usac_multi_sprt_update", "usac_multi_run_sprt",
     "usac_multi_grid", "usac_multi_draw_samples_napsac", "usac_multi_hypothesize_score_napsac", "usac_multi_run_napsac",
     "usac_multi_create_essential",
+    "usac_multi_set_thresholds", "usac_multi_get_thresholds",
 ]
 
 
@@ -303,6 +304,8 @@ def lib():
         "usac_multi_destroy": (None, [_vp]),
         "usac_multi_last_error": (ctypes.c_char_p, [_vp]),
         "usac_multi_num_problems": (ctypes.c_uint32, [_vp]),
+        "usac_multi_set_thresholds": (ctypes.c_int, [_vp, f32p]),
+        "usac_multi_get_thresholds": (ctypes.c_int, [_vp, f32p]),
         "usac_multi_hypothesize_score": (ctypes.c_int, [_vp, u32p, ctypes.c_uint32, i32p, ctypes.c_uint32,
                                                         _P(ctypes.c_uint64), ctypes.c_uint64, ctypes.c_float,
                                                         ctypes.c_int, i32p, f32p, _P(Record)]),
@@ -841,6 +844,29 @@ class MultiContext:
 
     def set_dlt_mode(self, mode):
         self.dlt_mode = DLT(mode)
+
+    def set_thresholds(self, thr):
+        """usac_multi_set_thresholds: one inlier threshold per problem (P finite values > 0, in the
+        units of each problem's own coordinates), or None to clear them.  While set, every method
+        that takes a threshold -- thr, or the model's -- uses problem p's value for problem p (whatever
+        its place in `problems`) and ignores its own; they persist like set_dlt_mode.  UsacError(-1),
+        nothing changed, for a wrong length or a value that is not finite and > 0."""
+        if thr is None:
+            self._check(lib().usac_multi_set_thresholds(self._h, None), "multi_set_thresholds")
+            return
+        t = np.ascontiguousarray(thr, dtype=np.float32).ravel()
+        if t.size != self.P:
+            raise UsacError(-1, "set_thresholds: one threshold per problem (%d), got %d" % (self.P, t.size))
+        self._check(lib().usac_multi_set_thresholds(self._h, _ptr(t, ctypes.c_float)), "multi_set_thresholds")
+
+    @property
+    def thresholds(self):
+        """The per-problem thresholds in effect (a float32 array of P values), or None."""
+        out = np.zeros(self.P, dtype=np.float32)
+        rc = lib().usac_multi_get_thresholds(self._h, _ptr(out, ctypes.c_float))
+        if rc < 0:
+            self._check(rc, "multi_get_thresholds")
+        return out if rc == 1 else None
 
     def hypothesize_score(self, R, seeds=None, first_hyp=0, thr=2.0, problems=None, samples=None,
                           per_hypothesis=True):

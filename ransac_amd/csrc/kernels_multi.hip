@@ -190,10 +190,12 @@ __global__ __launch_bounds__(64) void k_multi_solve_f7(const float4 *__restrict_
 __global__ __launch_bounds__(64) void k_multi_score_h(const float4 *__restrict__ pts_all,
                                                       const uint32_t *__restrict__ offsets,
                                                       const MultiItem *__restrict__ items,
-                                                      const float *__restrict__ models, uint32_t R, float thr,
+                                                      const float *__restrict__ models, uint32_t R, float thr_s,
+                                                      const float *__restrict__ thrs,
                                                       int32_t *__restrict__ counts, float *__restrict__ sums) {
     const uint32_t a = blockIdx.y;
     const uint32_t prob = items[a].problem;
+    const float thr = thrs ? thrs[prob] : thr_s;  // per-problem thresholds: the workgroup's problem's
     const uint32_t base = offsets[prob], n = offsets[prob + 1] - base;
     const float4 *__restrict__ pts = pts_all + base;
     const size_t g = (size_t)a * R + blockIdx.x * 64 + threadIdx.x, stride = (size_t)gridDim.y * R;
@@ -231,7 +233,8 @@ __global__ __launch_bounds__(64) void k_multi_score_f(const float4 *__restrict__
                                                       const MultiItem *__restrict__ items,
                                                       const float *__restrict__ models, uint32_t R,
                                                       const uint32_t *__restrict__ list,
-                                                      const uint32_t *__restrict__ list_n, float thr,
+                                                      const uint32_t *__restrict__ list_n, float thr_s,
+                                                      const float *__restrict__ thrs,
                                                       int32_t *__restrict__ counts, float *__restrict__ sums) {
     constexpr uint32_t SPK = EST == USAC_FUNDAMENTAL ? 3 : 1;
     const uint32_t a = blockIdx.y;
@@ -239,6 +242,7 @@ __global__ __launch_bounds__(64) void k_multi_score_f(const float4 *__restrict__
     const uint32_t i0 = blockIdx.x * 64;
     if (i0 >= K) return;  // block-uniform
     const uint32_t prob = items[a].problem;
+    const float thr = thrs ? thrs[prob] : thr_s;  // per-problem thresholds: the workgroup's problem's
     const uint32_t base = offsets[prob], n = offsets[prob + 1] - base;
     const float4 *__restrict__ pts = pts_all + base;
     const size_t stride = SPK * (size_t)gridDim.y * R;
@@ -352,11 +356,15 @@ __global__ __launch_bounds__(256) void k_multi_mask_prep(const float *__restrict
 }
 
 // one thread per point of the concatenated array: its problem by bisection of offsets, the
-// residual of usac_get_inliers under that problem's model (H, F or E), mask = err < thr
+// residual of usac_get_inliers under that problem's model (H, F or E), mask = err < thr (thrs given:
+// that problem's, per thread -- the lanes of a wave may straddle a boundary).  PT: per-problem thresholds, a
+// template parameter so that the instantiation without them is the kernel it was before they existed
+template <bool PT>
 __global__ __launch_bounds__(256) void k_multi_mask(const float4 *__restrict__ pts_all,
                                                     const uint32_t *__restrict__ offsets, uint32_t P,
                                                     uint32_t n_total, const float *__restrict__ m18, int est,
-                                                    float thr, uint8_t *__restrict__ mask) {
+                                                    float thr_s, uint8_t *__restrict__ mask,
+                                                    const float *__restrict__ thrs) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_total) return;
     uint32_t lo = 0, hi = P;  // offsets[lo] <= i < offsets[hi]
@@ -372,6 +380,7 @@ __global__ __launch_bounds__(256) void k_multi_mask(const float4 *__restrict__ p
     const float err = est == USAC_HOMOGRAPHY    ? homography_error(m, m + 9, p.x, p.y, p.z, p.w)
                       : est == USAC_FUNDAMENTAL ? fundamental_error(m, p.x, p.y, p.z, p.w)
                                                 : essential_error(m, p.x, p.y, p.z, p.w);
+    const float thr = PT ? thrs[lo] : thr_s;
     mask[i] = err < thr ? 1 : 0;
 }
 
@@ -395,7 +404,7 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
             if (e != hipSuccess) return e;
         } else {
             hipLaunchKernelGGL(k_multi_score_h, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.models, r.R, r.thr,
-                               r.counts, r.sums);
+                               r.thrs, r.counts, r.sums);
         }
         hipLaunchKernelGGL(k_multi_argmax, dim3(r.A), dim3(256), 0, st, r.items, r.counts, r.sums, r.models, r.R, 9,
                            r.first_hyp, 1u, r.running, r.out);
@@ -415,7 +424,7 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
             if (e != hipSuccess) return e;
         } else {
             hipLaunchKernelGGL(k_multi_score_f<USAC_FUNDAMENTAL>, dim3(3 * r.R / 64, r.A), dim3(64), 0, st, r.pts, r.offsets, r.items,
-                               r.models, r.R, r.list, r.list_n, r.thr, r.counts, r.sums);
+                               r.models, r.R, r.list, r.list_n, r.thr, r.thrs, r.counts, r.sums);
         }
         hipLaunchKernelGGL(k_multi_argmax, dim3(r.A), dim3(256), 0, st, r.items, r.counts, r.sums, r.models, 3 * r.R,
                            9, r.first_hyp, 3u, r.running, r.out);
@@ -424,7 +433,7 @@ hipError_t launch_multi_round(hipStream_t st, const MultiRound &r) {
         const hipError_t e = launch_multi_solve_e5(st, r);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_multi_score_f<USAC_ESSENTIAL>, grid, dim3(64), 0, st, r.pts, r.offsets, r.items, r.models,
-                           r.R, r.list, r.list_n, r.thr, r.counts, r.sums);
+                           r.R, r.list, r.list_n, r.thr, r.thrs, r.counts, r.sums);
         hipLaunchKernelGGL(k_multi_argmax, dim3(r.A), dim3(256), 0, st, r.items, r.counts, r.sums, r.models, r.R, 9,
                            r.first_hyp, 1u, r.running, r.out);
     } else {
@@ -471,11 +480,12 @@ hipError_t launch_multi_draw(hipStream_t st, int estimator, const uint32_t *offs
 }
 
 hipError_t launch_multi_mask(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,
-                             uint32_t n_total, const float *models, float thr, float *m18, uint8_t *mask) {
+                             uint32_t n_total, const float *models, float thr, const float *thrs, float *m18,
+                             uint8_t *mask) {
     const int is_h = estimator == USAC_HOMOGRAPHY;
     hipLaunchKernelGGL(k_multi_mask_prep, dim3((P + 255) / 256), dim3(256), 0, st, models, P, is_h, m18);
-    hipLaunchKernelGGL(k_multi_mask, dim3((n_total + 255) / 256), dim3(256), 0, st, pts, offsets, P, n_total, m18,
-                       estimator, thr, mask);
+    hipLaunchKernelGGL(thrs ? k_multi_mask<true> : k_multi_mask<false>, dim3((n_total + 255) / 256), dim3(256), 0, st, pts,
+                       offsets, P, n_total, m18, estimator, thr, mask, thrs);
     return hipGetLastError();
 }
 

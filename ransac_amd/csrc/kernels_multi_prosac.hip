@@ -51,8 +51,8 @@ __device__ __forceinline__ bool scan_flag(const float4 *__restrict__ pts, uint32
 template <int EST>
 __global__ __launch_bounds__(kMultiScanTile) void k_multi_prosac_scan(
     const float4 *__restrict__ pts_all, const uint32_t *__restrict__ offsets, const MultiItem *__restrict__ items,
-    const usac_record *__restrict__ running, uint64_t first_hyp, float thr, uint32_t *__restrict__ non_random,
-    uint32_t *__restrict__ cand, uint32_t *__restrict__ cand_n) {
+    const usac_record *__restrict__ running, uint64_t first_hyp, float thr_s, const float *__restrict__ thrs,
+    uint32_t *__restrict__ non_random, uint32_t *__restrict__ cand, uint32_t *__restrict__ cand_n) {
     // the waves' inlier and candidate totals of the current tile: each is written before one of the
     // tile's two barriers and read after it, so the next tile's writes cannot overtake a read
     __shared__ uint32_t sh_inl[kScanWaves], sh_cand[kScanWaves];
@@ -63,6 +63,7 @@ __global__ __launch_bounds__(kMultiScanTile) void k_multi_prosac_scan(
         if (t == 0) cand_n[a] = 0;
         return;
     }
+    const float thr = thrs ? thrs[prob] : thr_s;  // per-problem thresholds: the workgroup's problem's
     const uint32_t base = offsets[prob], n = offsets[prob + 1] - base;
     const float4 *__restrict__ pts = pts_all + base;
     uint32_t *__restrict__ nr = non_random + base;
@@ -119,18 +120,18 @@ __global__ __launch_bounds__(kMultiScanTile) void k_multi_prosac_scan(
 
 hipError_t launch_multi_prosac_scan(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets,
                                     const MultiItem *items, uint32_t A, const usac_record *running,
-                                    uint64_t first_hyp, float thr, uint32_t *non_random, uint32_t *cand,
-                                    uint32_t *cand_n) {
+                                    uint64_t first_hyp, float thr, const float *thrs, uint32_t *non_random,
+                                    uint32_t *cand, uint32_t *cand_n) {
     if (A == 0) return hipErrorInvalidValue;
     if (estimator == USAC_HOMOGRAPHY)
         hipLaunchKernelGGL(k_multi_prosac_scan<USAC_HOMOGRAPHY>, dim3(A), dim3(kMultiScanTile), 0, st, pts, offsets, items, running,
-                           first_hyp, thr, non_random, cand, cand_n);
+                           first_hyp, thr, thrs, non_random, cand, cand_n);
     else if (estimator == USAC_FUNDAMENTAL)
         hipLaunchKernelGGL(k_multi_prosac_scan<USAC_FUNDAMENTAL>, dim3(A), dim3(kMultiScanTile), 0, st, pts, offsets, items,
-                           running, first_hyp, thr, non_random, cand, cand_n);
+                           running, first_hyp, thr, thrs, non_random, cand, cand_n);
     else if (estimator == USAC_ESSENTIAL)
         hipLaunchKernelGGL(k_multi_prosac_scan<USAC_ESSENTIAL>, dim3(A), dim3(kMultiScanTile), 0, st, pts, offsets, items,
-                           running, first_hyp, thr, non_random, cand, cand_n);
+                           running, first_hyp, thr, thrs, non_random, cand, cand_n);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();

@@ -83,7 +83,8 @@ __global__ __launch_bounds__(64) void k_multi_sprt_head(const float4 *__restrict
                                                         const uint32_t *__restrict__ offsets,
                                                         const MultiItem *__restrict__ items,
                                                         const SprtConsts *__restrict__ consts,
-                                                        const float *__restrict__ models, uint32_t S, float thr,
+                                                        const float *__restrict__ models, uint32_t S, float thr_s,
+                                                        const float *__restrict__ thrs,
                                                         int32_t *__restrict__ counts, float *__restrict__ sums,
                                                         usac_multi_sprt_stats *__restrict__ stats,
                                                         MultiSurvivor *__restrict__ surv,
@@ -91,6 +92,7 @@ __global__ __launch_bounds__(64) void k_multi_sprt_head(const float4 *__restrict
     constexpr int NC = EST == 2 ? 18 : 9;
     const uint32_t a = blockIdx.y;
     const uint32_t prob = items[a].problem;
+    const float thr = thrs ? thrs[prob] : thr_s;  // per-problem thresholds: the workgroup's problem's
     const uint32_t base = offsets[prob], n = offsets[prob + 1] - base;
     const float4 *__restrict__ pts = pool_all + base;
     const SprtConsts kc = consts[a];
@@ -191,7 +193,8 @@ __global__ __launch_bounds__(256) void k_multi_sprt_tail(const float4 *__restric
                                                          const MultiItem *__restrict__ items,
                                                          const SprtConsts *__restrict__ consts,
                                                          const float *__restrict__ models, uint32_t S, size_t stride,
-                                                         float thr, const MultiSurvivor *__restrict__ surv,
+                                                         float thr_s, const float *__restrict__ thrs,
+                                                         const MultiSurvivor *__restrict__ surv,
                                                          const uint32_t *__restrict__ surv_n,
                                                          int32_t *__restrict__ counts, float *__restrict__ sums,
                                                          usac_multi_sprt_stats *__restrict__ stats) {
@@ -203,6 +206,7 @@ __global__ __launch_bounds__(256) void k_multi_sprt_tail(const float4 *__restric
     for (uint32_t k = blockIdx.x; k < ns; k += gridDim.x) {
         const MultiSurvivor sv = surv[k];
         const uint32_t prob = items[sv.entry].problem;
+        const float thr = thrs ? thrs[prob] : thr_s;  // per-problem thresholds: the survivor's problem's
         const uint32_t base = offsets[prob], n = offsets[prob + 1] - base;  // n > kMsHead: the head appended it
         const float4 *__restrict__ pts = pool_all + base;
         const SprtConsts kc = consts[sv.entry];
@@ -364,10 +368,10 @@ hipError_t launch_multi_sprt_score(hipStream_t st, const MultiRound &r) {
 #define MS(E)                                                                                                        \
     do {                                                                                                             \
         hipLaunchKernelGGL(k_multi_sprt_head<E>, grid, dim3(64), 0, st, s.pool_pts, r.offsets, r.items, s.consts,    \
-                           r.models, S, r.thr, r.counts, r.sums, s.stats, sv, s.surv_n, s.starts);                   \
+                           r.models, S, r.thr, r.thrs, r.counts, r.sums, s.stats, sv, s.surv_n, s.starts);                   \
         if (s.tail)                                                                                                  \
             hipLaunchKernelGGL(k_multi_sprt_tail<E>, tgrid, dim3(256), 0, st, s.pool_pts, r.offsets, r.items,        \
-                               s.consts, r.models, S, total, r.thr, sv, s.surv_n, r.counts, r.sums, s.stats);        \
+                               s.consts, r.models, S, total, r.thr, r.thrs, sv, s.surv_n, r.counts, r.sums, s.stats);        \
     } while (0)
     if (r.estimator == USAC_HOMOGRAPHY) MS(2);
     else if (r.estimator == USAC_FUNDAMENTAL) MS(3);

@@ -1300,7 +1300,8 @@ template <int EST>
 __global__ __launch_bounds__(kPolT) void k_multi_polish(const float4 *__restrict__ pts_all,
                                                         const uint32_t *__restrict__ offsets,
                                                         const float *__restrict__ models, uint32_t model_stride,
-                                                        float thr, int32_t *__restrict__ lists, uint32_t n_total,
+                                                        float thr_s, const float *__restrict__ thrs,
+                                                        int32_t *__restrict__ lists, uint32_t n_total,
                                                         usac_multi_polish_output *__restrict__ out,
                                                         uint8_t *__restrict__ mask) {
     constexpr bool FUND = EST != USAC_HOMOGRAPHY;
@@ -1322,6 +1323,7 @@ __global__ __launch_bounds__(kPolT) void k_multi_polish(const float4 *__restrict
     sh.wc = s_wc;
     sh.dbg = nullptr;
     const uint32_t t = threadIdx.x, p = blockIdx.x;
+    const float thr = thrs ? thrs[p] : thr_s;  // per-problem thresholds: the workgroup's problem's
     const uint32_t base = offsets[p], N = offsets[p + 1] - base;
     usac_multi_polish_output *o = out + p;
     if (N > kPolPtsMax) {  // workgroup-uniform
@@ -1386,18 +1388,18 @@ __global__ __launch_bounds__(kPolT) void k_multi_polish(const float4 *__restrict
 }
 
 hipError_t launch_multi_polish(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,
-                               uint32_t n_total, const float *models, uint32_t model_stride, float thr, int32_t *lists,
-                               usac_multi_polish_output *out, uint8_t *mask) {
+                               uint32_t n_total, const float *models, uint32_t model_stride, float thr,
+                               const float *thrs, int32_t *lists, usac_multi_polish_output *out, uint8_t *mask) {
     if (P == 0) return hipErrorInvalidValue;
     switch (estimator) {
         case USAC_HOMOGRAPHY:
-            hipLaunchKernelGGL(k_multi_polish<USAC_HOMOGRAPHY>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, lists, n_total, out, mask);
+            hipLaunchKernelGGL(k_multi_polish<USAC_HOMOGRAPHY>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, thrs, lists, n_total, out, mask);
             break;
         case USAC_FUNDAMENTAL:
-            hipLaunchKernelGGL(k_multi_polish<USAC_FUNDAMENTAL>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, lists, n_total, out, mask);
+            hipLaunchKernelGGL(k_multi_polish<USAC_FUNDAMENTAL>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, thrs, lists, n_total, out, mask);
             break;
         case USAC_ESSENTIAL:
-            hipLaunchKernelGGL(k_multi_polish<USAC_ESSENTIAL>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, lists, n_total, out, mask);
+            hipLaunchKernelGGL(k_multi_polish<USAC_ESSENTIAL>, dim3(P), dim3(kPolT), 0, st, pts, offsets, models, model_stride, thr, thrs, lists, n_total, out, mask);
             break;
         default:
             return hipErrorInvalidValue;
@@ -1428,7 +1430,9 @@ hipError_t launch_multi_polish(hipStream_t st, int estimator, const float4 *pts,
 // lo_inliers: the iterative stage scores into the list it was just fitted from (pol_fit has the
 // points in LDS by then), and an improvement swaps the two pointers.  The length of max_inliers
 // stands for best_score->inlier_number wherever the reference sizes a list by it.
-template <int EST>
+// PT: per-problem thresholds (g.thrs / g.steps in place of g.thr / g.step).  A template parameter and not a
+// null test: at 256 VGPRs with scratch the run-time form cost the scalar path 2 %.
+template <int EST, bool PT>
 __global__ __launch_bounds__(kPolT) void k_multi_lo(const float4 *__restrict__ pts_all,
                                                     const uint32_t *__restrict__ offsets, MultiLo g) {
     constexpr bool FUND = EST != USAC_HOMOGRAPHY;
@@ -1457,6 +1461,8 @@ __global__ __launch_bounds__(kPolT) void k_multi_lo(const float4 *__restrict__ p
     if (!rec.valid || !(g.force || rec.hyp_index >= g.first_hyp)) return;  // workgroup-uniform
     usac_multi_lo_output st = g.state[p];
     st.lo_calls++;
+    // per-problem thresholds: θ_p and its iterative step (both workgroup-uniform)
+    const float theta = PT ? g.thrs[p] : g.thr, step = PT ? g.steps[p] : g.step;
     const uint32_t base = offsets[p], N = offsets[p + 1] - base;
     const float4 *__restrict__ pts = pts_all + base;
     int32_t *lmax = g.lists + base, *llo = g.lists + (size_t)g.n_total + base;
@@ -1468,13 +1474,13 @@ __global__ __launch_bounds__(kPolT) void k_multi_lo(const float4 *__restrict__ p
     int stage = best_cnt < 12 ? kEnd : kInit;
     if (stage == kInit && N > kPolPtsMax) {  // the caps rule
         st.capped++;
-        thr = g.thr;
+        thr = theta;
         stage = kEnd;
     }
     // the end of the iterative stage: the fail test, the best's update, the reference's counter
     auto finish = [&]() {
-        const bool fail = (double)fabsf(thr - g.thr) > 0.00001;
-        if (fail) thr = g.thr;
+        const bool fail = (double)fabsf(thr - theta) > 0.00001;
+        if (fail) thr = theta;
         if (!fail && (lo_cnt > best_cnt || (lo_cnt == best_cnt && lo_sum > best_sum))) {
             best_cnt = lo_cnt;
             best_sum = lo_sum;
@@ -1518,7 +1524,7 @@ __global__ __launch_bounds__(kPolT) void k_multi_lo(const float4 *__restrict__ p
         } else {  // the iterative stage's loop head
             bool fin = k >= g.iters;
             if (!fin) {
-                thr -= g.step;
+                thr -= step;
                 fin = lo_cnt <= kM;
             }
             if (fin) {
@@ -1528,7 +1534,7 @@ __global__ __launch_bounds__(kPolT) void k_multi_lo(const float4 *__restrict__ p
             sampled = g.limited && (uint32_t)lo_cnt > g.limit;
             if (!sampled && (uint32_t)lo_cnt > kPolFitMax) {  // the caps rule
                 st.capped++;
-                thr = g.thr;
+                thr = theta;
                 break;
             }
             fl = sampled ? s_samp : llo;
@@ -1562,7 +1568,7 @@ __global__ __launch_bounds__(kPolT) void k_multi_lo(const float4 *__restrict__ p
         __syncthreads();
         if (stage == kInner) thr = g.mult * thr;
         const uint32_t cnt = __builtin_amdgcn_readfirstlane(
-            pol_score<EST>(pts, N, s_model, stage == kInit ? g.thr : thr, stage == kInit ? lmax : llo, sh));
+            pol_score<EST>(pts, N, s_model, stage == kInit ? theta : thr, stage == kInit ? lmax : llo, sh));
         pol_seq<1, false>(sh.E, 0, cnt, sh, s_sum);
         if (stage == kInit) {
             n_max = cnt;
@@ -1602,13 +1608,16 @@ __global__ __launch_bounds__(kPolT) void k_multi_lo(const float4 *__restrict__ p
 
 hipError_t launch_multi_lo(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t A,
                            const MultiLo &lo) {
+    if (!lo.thrs != !lo.steps) return hipErrorInvalidValue;
     if (A == 0 || lo.limit == 0 || lo.limit > kLoDrawMax || lo.iters == 0) return hipErrorInvalidValue;
     switch (estimator) {
         case USAC_HOMOGRAPHY:
-            hipLaunchKernelGGL(k_multi_lo<USAC_HOMOGRAPHY>, dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
+            if (lo.thrs) hipLaunchKernelGGL((k_multi_lo<USAC_HOMOGRAPHY, true>), dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
+            else hipLaunchKernelGGL((k_multi_lo<USAC_HOMOGRAPHY, false>), dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
             break;
         case USAC_FUNDAMENTAL:
-            hipLaunchKernelGGL(k_multi_lo<USAC_FUNDAMENTAL>, dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
+            if (lo.thrs) hipLaunchKernelGGL((k_multi_lo<USAC_FUNDAMENTAL, true>), dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
+            else hipLaunchKernelGGL((k_multi_lo<USAC_FUNDAMENTAL, false>), dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
             break;
         default:
             return hipErrorInvalidValue;

@@ -4051,6 +4051,11 @@ struct usac_multi {
     // (kMultiE5Slice, lowered by USAC_MULTI_E5_SLICE at creation)
     DevBuf e5_ws;
     uint32_t e5_slice = usac::kMultiE5Slice;
+    // Per-problem thresholds (ABI 22): empty = none, every call uses its scalar; else P values, their
+    // device copy, and per LO call the iterative steps (θ_p mult - θ_p) / iterations of the call's params
+    std::vector<float> thr_host;
+    DevBuf thrs, lo_steps;
+    uint32_t lo_steps_mult = 0, lo_steps_iters = 0;  // what lo_steps was computed for (iters 0: nothing)
     std::string err;
 };
 
@@ -4105,6 +4110,10 @@ usac_record *multi_records_pin(usac_multi *mc, uint32_t A_cap) {
     return reinterpret_cast<usac_record *>(multi_items_pin(mc) + A_cap);
 }
 
+// the device thresholds of a context that has them set (else null: the call's scalar), and problem p's on the host
+const float *multi_thrs(const usac_multi *mc) { return mc->thr_host.empty() ? nullptr : mc->thrs.as<float>(); }
+float multi_thr_of(const usac_multi *mc, uint32_t p, float scalar) { return mc->thr_host.empty() ? scalar : mc->thr_host[p]; }
+
 usac::MultiRound multi_round(usac_multi *mc, uint32_t A, uint32_t R, uint64_t first_hyp, float thr, int dlt_mode) {
     usac::MultiRound r{};
     r.estimator = mc->estimator;
@@ -4116,6 +4125,7 @@ usac::MultiRound multi_round(usac_multi *mc, uint32_t A, uint32_t R, uint64_t fi
     r.R = R;
     r.first_hyp = first_hyp;
     r.thr = thr;
+    r.thrs = multi_thrs(mc);
     r.models = mc->models.as<float>();
     r.counts = mc->counts.as<int32_t>();
     r.sums = mc->sums.as<float>();
@@ -4184,7 +4194,7 @@ int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, c
     HIP_TRY(mc, mc->pol_out.reserve(sizeof(usac_multi_polish_output) * (size_t)P));
     if (mask) HIP_TRY(mc, mc->mask.reserve(mc->n_total));
     HIP_TRY(mc, usac::launch_multi_polish(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), P,
-                                          mc->n_total, dmodels, stride, thr, mc->pol_lists.as<int32_t>(),
+                                          mc->n_total, dmodels, stride, thr, multi_thrs(mc), mc->pol_lists.as<int32_t>(),
                                           mc->pol_out.as<usac_multi_polish_output>(),
                                           mask ? mc->mask.as<uint8_t>() : nullptr));
     // results and mask come down through pinned staging, then into the caller's (pageable) buffers
@@ -4199,7 +4209,8 @@ int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, c
     if (mask) memcpy(mask, stage + out_bytes, mc->n_total);
     for (uint32_t p = 0; p < P; p++) {
         if (out[p].status != usac::kMultiPolishDefer) continue;
-        rc = multi_polish_single(mc, p, hstart + (size_t)p * hstride, thr, out + p, mask ? mask + mc->offsets[p] : nullptr);
+        rc = multi_polish_single(mc, p, hstart + (size_t)p * hstride, multi_thr_of(mc, p, thr), out + p,
+                                 mask ? mask + mc->offsets[p] : nullptr);
         if (rc) return rc;
     }
     return USAC_OK;
@@ -4251,7 +4262,7 @@ int multi_prosac_reset(usac_multi *mc, const usac_params *prm) {
 hipError_t multi_launch_scan(usac_multi *mc, uint32_t A, uint64_t first_hyp, float thr) {
     return usac::launch_multi_prosac_scan(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(),
                                           mc->items.as<usac::MultiItem>(), A, mc->running.as<usac_record>(),
-                                          first_hyp, thr, mc->non_random.as<uint32_t>(), multi_cand_pin(mc),
+                                          first_hyp, thr, multi_thrs(mc), mc->non_random.as<uint32_t>(), multi_cand_pin(mc),
                                           multi_cand_n_pin(mc));
 }
 
@@ -4280,11 +4291,24 @@ int multi_lo_ensure(usac_multi *mc, const usac_params *prm, bool reset) {
     HIP_TRY(mc, mc->pol_lists.reserve(sizeof(int32_t) * 2 * (size_t)mc->n_total));
     HIP_TRY(mc, mc->lo_state.reserve(sizeof(usac_multi_lo_output) * (size_t)P));
     if (reset || !mc->lo_state_set) {
-        usac_multi_lo_output fresh{};
-        fresh.threshold = prm->threshold;
-        const std::vector<usac_multi_lo_output> init(P, fresh);
+        std::vector<usac_multi_lo_output> init(P, usac_multi_lo_output{});
+        for (uint32_t p = 0; p < P; p++) init[p].threshold = multi_thr_of(mc, p, prm->threshold);
         HIP_TRY(mc, hipMemcpy(mc->lo_state.p, init.data(), sizeof(usac_multi_lo_output) * (size_t)P, hipMemcpyHostToDevice));
         mc->lo_state_set = true;
+    }
+    // the call's iterative steps: multi_lo_args' expression with θ_p for θ; uploaded when the thresholds or
+    // the two parameters they depend on changed
+    if (!mc->thr_host.empty() && (mc->lo_steps_mult != prm->lo_threshold_multiplier ||
+                                  mc->lo_steps_iters != prm->lo_iterative_iterations)) {
+        std::vector<float> steps(P);
+        for (uint32_t p = 0; p < P; p++) {
+            const float t = mc->thr_host[p];
+            steps[p] = (t * prm->lo_threshold_multiplier - t) / prm->lo_iterative_iterations;
+        }
+        HIP_TRY(mc, mc->lo_steps.reserve(sizeof(float) * (size_t)P));
+        HIP_TRY(mc, hipMemcpy(mc->lo_steps.p, steps.data(), sizeof(float) * (size_t)P, hipMemcpyHostToDevice));
+        mc->lo_steps_mult = prm->lo_threshold_multiplier;
+        mc->lo_steps_iters = prm->lo_iterative_iterations;
     }
     return USAC_OK;
 }
@@ -4301,6 +4325,8 @@ usac::MultiLo multi_lo_args(usac_multi *mc, const usac_params *prm, uint64_t fir
     lo.thr = prm->threshold;
     lo.mult = (float)prm->lo_threshold_multiplier;
     lo.step = (prm->threshold * prm->lo_threshold_multiplier - prm->threshold) / prm->lo_iterative_iterations;
+    lo.thrs = multi_thrs(mc);
+    lo.steps = lo.thrs ? mc->lo_steps.as<float>() : nullptr;  // uploaded by multi_lo_ensure
     lo.inner = prm->lo_inner_iterations;
     lo.iters = prm->lo_iterative_iterations;
     lo.limit = prm->lo_sample_size;
@@ -4819,7 +4845,7 @@ void usac_multi_destroy(usac_multi *mc) {
         b->release();
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
                       &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
-                      &mc->pol_out, &mc->lo_state, &mc->e5_ws})
+                      &mc->pol_out, &mc->lo_state, &mc->e5_ws, &mc->thrs, &mc->lo_steps})
         b->release();
     if (mc->stream) StreamPool::get().give_back(mc->stream);
     delete mc;
@@ -4827,6 +4853,34 @@ void usac_multi_destroy(usac_multi *mc) {
 
 const char *usac_multi_last_error(const usac_multi *mc) { return mc ? mc->err.c_str() : "null context"; }
 uint32_t usac_multi_num_problems(const usac_multi *mc) { return mc ? mc->P : 0; }
+
+// ---- per-problem thresholds (ABI 22)
+int usac_multi_set_thresholds(usac_multi *mc, const float *thr) {
+    if (!mc) return USAC_ERR_ARG;
+    if (!thr) {
+        mc->thr_host.clear();
+        mc->lo_steps_iters = 0;
+        return USAC_OK;
+    }
+    for (uint32_t p = 0; p < mc->P; p++)
+        if (!(thr[p] > 0.f) || !std::isfinite(thr[p]))
+            return fail(mc, USAC_ERR_ARG, "usac_multi_set_thresholds: problem " + std::to_string(p) +
+                                              ": the threshold must be finite and > 0");
+    // every call waits for its stream before it returns: no launch of this context reads the old values now
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    HIP_TRY(mc, mc->thrs.reserve(sizeof(float) * (size_t)mc->P));
+    HIP_TRY(mc, hipMemcpy(mc->thrs.p, thr, sizeof(float) * (size_t)mc->P, hipMemcpyHostToDevice));
+    mc->thr_host.assign(thr, thr + mc->P);
+    mc->lo_steps_iters = 0;  // the LO steps follow the thresholds
+    return USAC_OK;
+}
+
+int usac_multi_get_thresholds(const usac_multi *mc, float *out) {
+    if (!mc) return USAC_ERR_ARG;
+    if (mc->thr_host.empty()) return 0;
+    if (out) std::copy(mc->thr_host.begin(), mc->thr_host.end(), out);
+    return 1;
+}
 
 int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint32_t n_problems,
                                  const int32_t *samples, uint32_t R, const uint64_t *seeds, uint64_t first_hyp,
@@ -4861,7 +4915,7 @@ int usac_multi_inliers(usac_multi *mc, const float *models, float thr, uint8_t *
     HIP_TRY(mc, hipMemcpyAsync(mc->mmodels.p, models, sizeof(float) * 9 * (size_t)mc->P, hipMemcpyHostToDevice,
                                mc->stream));
     HIP_TRY(mc, usac::launch_multi_mask(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), mc->P,
-                                        mc->n_total, mc->mmodels.as<float>(), thr, mc->m18.as<float>(),
+                                        mc->n_total, mc->mmodels.as<float>(), thr, multi_thrs(mc), mc->m18.as<float>(),
                                         mc->mask.as<uint8_t>()));
     std::vector<uint8_t> tmp;
     if (!mask) {

@@ -352,6 +352,7 @@ struct MultiRound {
     const int32_t *samples_in;  // nullable: A x R x m indices local to each problem; else the device sampler
     uint64_t first_hyp;
     float thr;
+    const float *thrs;          // nullable, indexed by problem: problem p scores under thrs[p] and thr is unread
     float *models;              // SoA slab over the launch: H [18][A R], F [9][3 A R], E [9][A R]
     int32_t *counts;            // A x R x spk
     float *sums;
@@ -427,12 +428,13 @@ __host__ __device__ inline size_t multi_cand_offset(uint32_t point_offset, uint3
 inline size_t multi_cand_capacity(uint32_t n_total, uint32_t P) { return (size_t)(n_total >> 1) + P; }
 hipError_t launch_multi_prosac_scan(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets,
                                     const MultiItem *items, uint32_t A, const usac_record *running,
-                                    uint64_t first_hyp, float thr, uint32_t *non_random, uint32_t *cand,
-                                    uint32_t *cand_n);
+                                    uint64_t first_hyp, float thr, const float *thrs, uint32_t *non_random,
+                                    uint32_t *cand, uint32_t *cand_n);
 // per-point inlier flags of each problem's model (models P x 9 row-major, device; m18 = P x 18
 // floats of scratch): the residual of launch_inliers, H^-1 by inv3x3
 hipError_t launch_multi_mask(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,
-                             uint32_t n_total, const float *models, float thr, float *m18, uint8_t *mask);
+                             uint32_t n_total, const float *models, float thr, const float *thrs, float *m18,
+                             uint8_t *mask);
 // the non-minimal polish and final getInliers of every problem (kernels_nonmin.hip k_multi_polish:
 // k_polish_fused's workgroup, one per problem).  models: problem p's start model at models + p *
 // model_stride floats (device); lists: 2 x n_total int32 of scratch; out: P results (device); mask
@@ -440,8 +442,8 @@ hipError_t launch_multi_mask(hipStream_t st, int estimator, const float4 *pts, c
 // fit > kPolFitMax) gets out[p].status = kMultiPolishDefer and no other output.
 constexpr int32_t kMultiPolishDefer = 1;
 hipError_t launch_multi_polish(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t P,
-                               uint32_t n_total, const float *models, uint32_t model_stride, float thr, int32_t *lists,
-                               usac_multi_polish_output *out, uint8_t *mask);
+                               uint32_t n_total, const float *models, uint32_t model_stride, float thr,
+                               const float *thrs, int32_t *lists, usac_multi_polish_output *out, uint8_t *mask);
 // LO-RANSAC of every active problem whose running record improved in the round (kernels_nonmin.hip
 // k_multi_lo: k_multi_polish's workgroup under InnerLocalOptimization::GetModelScore's control flow).
 // lists: launch_multi_polish's 2 x n_total int32; state: per problem, the LO threshold, the draw
@@ -458,6 +460,10 @@ struct MultiLo {
     int32_t *lists;
     uint32_t n_total;
     usac_multi_lo_output *state;
+    // nullable (both or neither), indexed by problem: θ_p and the step (θ_p mult - θ_p) / iters, in place of thr /
+    // step.  Last, and read by an instantiation of their own (k_multi_lo<EST, true>): without them the kernel
+    // is the one it was before they existed, argument offsets included
+    const float *thrs, *steps;
 };
 hipError_t launch_multi_lo(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t A,
                            const MultiLo &lo);

@@ -51,6 +51,13 @@ hypotheses, mean best inliers; for the NAPSAC run also the share of pairs withou
 (they draw uniform samples) and the mean eligible share; and, apart from the runs, the grid build of all
 pairs (usac_multi_grid with no output, after a build for another size), which a run pays once per cell
 size.  No loop over single contexts in this mode.
+
+--per-problem-thr compares the run with per-problem thresholds (MultiContext.set_thresholds, all P of them
+equal to the scalar) with the same run without them: the plain run, or with --lo / --sprt / --sampler
+prosac|napsac / --polish the run those flags select, alternated on the same context (the thresholds are
+set and cleared outside the timed window).  The two results must be equal bit for bit (exit status 1
+otherwise); the difference of the two medians is the cost of the indexed path.  No loop over single
+contexts in this mode.
 """
 import argparse
 import ctypes
@@ -452,6 +459,80 @@ def main_napsac(a, mc, model, est):
     return 0
 
 
+def same_bits(x, y):
+    """equal without tolerance: floats and float arrays by bit pattern"""
+    if isinstance(x, dict):
+        return list(x) == list(y) and all(same_bits(x[k], y[k]) for k in x)
+    if isinstance(x, (list, tuple)):
+        return len(x) == len(y) and all(same_bits(u, v) for u, v in zip(x, y))
+    if isinstance(x, np.ndarray):
+        return x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes()
+    if isinstance(x, float):
+        return np.float64(x).tobytes() == np.float64(y).tobytes()
+    return x == y
+
+
+def main_thresholds(a, mc, model, est):
+    """--per-problem-thr: the selected run with P thresholds equal to the scalar against the same run
+    without them, alternated, host-timed, medians and spreads as in main()"""
+    S = usac.SAMPLER
+    sampler = {"uniform": S.Uniform, "prosac": S.Prosac, "napsac": S.Napsac}[a.sampler]
+    rmodel = usac.Model(model.threshold, mc.m, model.desired_prob, 5, est, sampler)
+    rmodel.max_iterations, rmodel.batch, rmodel.seed = model.max_iterations, model.batch, model.seed
+    rmodel.setDLTMode(model.dlt_mode)
+    if a.sampler == "napsac":
+        rmodel.setNeighborsType(usac.NeighborsSearch.Grid)
+        rmodel.setCellSize(a.cell_size)
+    if a.lo:
+        rmodel.lo = usac.LocOpt.InItLORsc if a.lo == "lorsc" else usac.LocOpt.InItFLORsc
+    rmodel.setSprt(a.sprt)
+    if a.sprt:
+        mc.set_sprt_pool()
+    call = (mc.run_napsac if a.sampler == "napsac" else mc.run_sprt if a.sprt else mc.run_lo if a.lo
+            else mc.run_prosac if a.sampler == "prosac" else mc.run)
+    thrs = [model.threshold] * mc.P
+
+    def run(per_problem):
+        mc.set_thresholds(thrs if per_problem else None)
+        t0 = time.perf_counter()
+        res = call(rmodel, polish=a.polish)
+        return res, (time.perf_counter() - t0) * 1e3
+
+    for _ in range(a.warmup):
+        run(True), run(False)
+    tp, ts, equal = [], [], True
+    for _ in range(a.reps):
+        rp, ms_p = run(True)
+        rs, ms_s = run(False)
+        tp.append(ms_p)
+        ts.append(ms_s)
+        equal = equal and same_bits(rp, rs)
+
+    def summary(ms):
+        return {"ms": round(statistics.median(ms), 3), "spread_ms": round(max(ms) - min(ms), 3),
+                "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
+
+    line = {"bench": "multi_thresholds", "run": call.__name__, "estimator": a.estimator, "pairs": a.pairs,
+            "points": a.points, "round": a.R, "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio,
+            "dlt": a.dlt, "reps": a.reps, "polish": bool(a.polish), "lo": a.lo, "sprt": bool(a.sprt),
+            "sampler": a.sampler, "per_problem": summary(tp), "scalar": summary(ts),
+            "launch_rounds": int(max(r["rounds"] for r in rs)),
+            "hypotheses": int(sum(r["hypotheses"] for r in rs)),
+            "mean_best_inliers": round(float(np.mean([r["best"]["inliers"] for r in rs])), 2),
+            "results_bit_equal": bool(equal)}
+    line["indexed_path_ms"] = round(line["per_problem"]["ms"] - line["scalar"]["ms"], 3)
+    line["differs_beyond_spread"] = bool(abs(line["indexed_path_ms"]) >
+                                         max(line["per_problem"]["spread_ms"], line["scalar"]["spread_ms"]))
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    mc.close()
+    return 0 if equal else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=512)
@@ -481,6 +562,10 @@ def main():
     ap.add_argument("--sprt", action="store_true",
                     help="MultiContext.run_sprt (SPRT verification of every slot, one test per pair and round) against "
                          "the same run without SPRT; with --sampler prosac both use the PROSAC sampler")
+    ap.add_argument("--per-problem-thr", action="store_true",
+                    help="the selected multi run with P per-problem thresholds equal to the scalar "
+                         "(MultiContext.set_thresholds) against the same run without them: bit-equal results, and the "
+                         "cost of the indexed path")
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("--reps must be at least 5")
@@ -506,6 +591,8 @@ def main():
     seeds = [model.seed + p for p in range(a.pairs)]
 
     mc = usac.MultiContext.essential(sets) if essential else usac.MultiContext(est, sets)
+    if a.per_problem_thr:
+        return main_thresholds(a, mc, model, est)
     if a.sampler == "napsac":
         return main_napsac(a, mc, model, est)
     if a.sprt:
