@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from ransac_amd import synthetic
+from tests.helpers import record_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +33,13 @@ def test_h16_counts_equal_exact_full_size(usac, dlt):
         ctx.hypothesize_async(B, 99, 0, thr)
         rec = ctx.fetch_best()
         cf, sf = ctx.last_counts(B)
+        models, _ = ctx.estimate_models(ctx.draw_samples(B, 99, 0))
     np.testing.assert_array_equal(cf, ce)
     err = np.abs(sf.astype(np.float64) - se.astype(np.float64))
     assert (err <= _bound(se, ce, pts, thr)).all()
     assert rec.inliers == be["inliers"]
+    # the whole record: the argmax of the path's own counts and Σ (tests/helpers/record_ref.py)
+    record_ref.assert_record(rec, record_ref.record(cf, sf, models, 1, 0), "h16, dlt %d" % dlt)
 
 
 def test_h16_loop_batch_clustered_100k(usac):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from ransac_amd import synthetic
+from tests.helpers import record_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -214,11 +215,15 @@ def test_fast_kernel_equals_exact_kernel_full_size(usac):
             np.testing.assert_array_equal(cf, ce)
             np.testing.assert_array_equal(sf.view(np.int32), se.view(np.int32))
             assert bf["hyp_index"] == be["hyp_index"]
+            models, _ = ctx.estimate_models(ctx.draw_samples(65536, 99, 0))
             for chunks in (2, 4, 8):
                 ctx.set_score_chunks(chunks)
                 ctx.hypothesize_async(65536, 99, 0, 2.0)
                 rec = ctx.fetch_best()
                 assert rec.inliers == be["inliers"]
+                # the whole record: the argmax of the path's own counts and Σ (tests/helpers/record_ref.py)
+                cc, sc = ctx.last_counts(65536)
+                record_ref.assert_record(rec, record_ref.record(cc, sc, models, 1, 0), "dlt %d, %d chunks" % (mode, chunks))
 
 
 def test_fast_kernel_adversarial_models(usac, oracle):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from ransac_amd import synthetic
+from tests.helpers import record_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -81,6 +82,11 @@ def test_fast_twoview_full_batch_equals_exact(usac, kind):
         ctx.hypothesize_async(65536, 7, 0, thr)
         rec = ctx.fetch_best()
         assert rec.inliers == be["inliers"]
+        # the whole record: the argmax of the path's own counts and Σ (tests/helpers/record_ref.py)
+        S = 65536 * ctx.spk
+        cc, sc = ctx.last_counts(S)
+        models, _ = ctx.estimate_models(ctx.draw_samples(65536, 7, 0))
+        record_ref.assert_record(rec, record_ref.record(cc, sc, models.reshape(S, 9), ctx.spk, 0), kind)
 
 
 def test_essential_guarded_drain(usac, oracle):
