@@ -70,7 +70,9 @@
  *                                  ABI 21: usac_multi_create_essential, multi contexts of essential-matrix
  *                                  problems (5-point solver): rounds, runs, masks, the polish and PROSAC;
  *                                  ABI 22: usac_multi_set_thresholds / usac_multi_get_thresholds, one inlier
- *                                  threshold per problem of a multi context in place of the calls' scalar
+ *                                  threshold per problem of a multi context in place of the calls' scalar;
+ *                                  ABI 23: usac_multi_lo_essential / usac_multi_run_lo_essential, LO-RANSAC
+ *                                  on multi contexts of essential-matrix problems (8-point non-minimal fit)
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -85,7 +87,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 22
+#define USAC_ABI_VERSION 23
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -535,6 +537,8 @@ int usac_multi_create(usac_multi **out, int device, int estimator, const float *
  * USAC_ERR_UNSUPPORTED, before any device call: usac_multi_lo, usac_multi_run_lo, usac_multi_sprt_setup,
  * usac_multi_hypothesize_score_sprt, usac_multi_run_sprt, usac_multi_grid,
  * usac_multi_draw_samples_napsac, usac_multi_hypothesize_score_napsac and usac_multi_run_napsac.
+ * LO-RANSAC on such a context has entries of its own (ABI 23): usac_multi_lo_essential and
+ * usac_multi_run_lo_essential.
  * The solve's workspace is ~1.2 KB per sample; a round of more than 131 072 samples is solved in slices
  * of whole problems (USAC_MULTI_E5_SLICE in the environment at creation lowers the cap, for tests);
  * the results do not depend on the slice. */
@@ -755,6 +759,24 @@ int usac_multi_lo(usac_multi *mc, const usac_params *params, int reset, const ui
 int usac_multi_run_lo(usac_multi *mc, const usac_params *params, const uint64_t *seeds, usac_multi_output *out,
                       usac_multi_lo_output *lo, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
                       uint8_t *mask);
+
+/* LO-RANSAC on a multi context of essential-matrix problems (usac_multi_create_essential; ABI 23).
+ * usac_multi_lo_essential is usac_multi_lo and usac_multi_run_lo_essential is usac_multi_run_lo, each with
+ * its contract word for word -- the params read, the error codes before any device call, the uniform or
+ * the PROSAC sampler (PROSAC: every n_p > 20), the per-problem state, the caps rule, out / lo / pro / pol /
+ * mask, per-problem thresholds -- on an essential context: the sample size every `<= m` test of the
+ * reference reads is 5, a non-minimal sample is fitted by the 8-point algorithm
+ * (essential_estimator.hpp:64-74: usac_nonminimal's fit on a usac_ctx of USAC_ESSENTIAL) and scored by the
+ * squared Sampson distance in calibrated coordinates.  dlt_mode is ignored.  The 5-point solve of a round
+ * is sliced as without LO (usac_multi_create_essential); the results do not depend on the slice.
+ * They are entries of their own because usac_multi_lo / usac_multi_run_lo keep returning
+ * USAC_ERR_UNSUPPORTED on an essential context.  On a homography or fundamental context these two return
+ * USAC_ERR_UNSUPPORTED and name usac_multi_lo / usac_multi_run_lo.  No SPRT, no NAPSAC. */
+int usac_multi_lo_essential(usac_multi *mc, const usac_params *params, int reset, const uint64_t *seeds,
+                            usac_record *recs, usac_multi_lo_output *lo);
+int usac_multi_run_lo_essential(usac_multi *mc, const usac_params *params, const uint64_t *seeds,
+                                usac_multi_output *out, usac_multi_lo_output *lo, usac_multi_prosac_output *pro,
+                                usac_multi_polish_output *pol, uint8_t *mask);
 
 /* ---- multi-problem batches: SPRT verification (ABI 19) ----------------------------------------------
  * A batch-granular SPRT: every problem has its own test (epsilon, delta, A), fixed for a round of R

@@ -737,6 +737,38 @@ public:
         return out;
     }
 
+    // usac_multi_lo_essential / usac_multi_run_lo_essential (ABI 23): lo() and runLo() on a context from
+    // essential(), where those two keep refusing; sample size 5, the 8-point non-minimal fit
+    std::vector<usac_multi_lo_output> loEssential(const Model &model, std::vector<usac_record> &records,
+                                                  const std::vector<uint64_t> &seeds = std::vector<uint64_t>(),
+                                                  bool reset = true) const {
+        usac_params p = model.params();
+        p.seed = model.seed;
+        const unsigned int P = problems();
+        if (records.size() != P) throw Error(USAC_ERR_ARG, "loEssential: one record per problem");
+        if (!seeds.empty() && seeds.size() != P) throw Error(USAC_ERR_ARG, "loEssential: one seed per problem");
+        std::vector<usac_multi_lo_output> out(P);
+        check(usac_multi_lo_essential(mc_, &p, reset ? 1 : 0, seeds.empty() ? nullptr : seeds.data(), records.data(),
+                                      out.data()),
+              "MultiContext::loEssential");
+        return out;
+    }
+
+    Lo runLoEssential(const Model &model, const std::vector<uint64_t> &seeds = std::vector<uint64_t>()) const {
+        usac_params p = model.params();
+        p.seed = model.seed;
+        const unsigned int P = problems();
+        if (!seeds.empty() && seeds.size() != P) throw Error(USAC_ERR_ARG, "runLoEssential: one seed per problem");
+        Lo out;
+        out.run.resize(P);
+        out.lo.resize(P);
+        if (p.sampler == USAC_SAMPLER_PROSAC) out.prosac.resize(P);
+        check(usac_multi_run_lo_essential(mc_, &p, seeds.empty() ? nullptr : seeds.data(), out.run.data(), out.lo.data(),
+                                          out.prosac.empty() ? nullptr : out.prosac.data(), nullptr, nullptr),
+              "MultiContext::runLoEssential");
+        return out;
+    }
+
     // usac_multi_sprt_setup: the problems' SPRT pools (the reference's shuffle after srandom(seeds[p]),
     // default p + 1) and the pool-ordered copy of the points on the device; once per context
     void setSprtPool(const std::vector<uint32_t> &seeds = std::vector<uint32_t>()) const {

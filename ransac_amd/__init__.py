@@ -203,6 +203,7 @@ ABI_SYMBOLS = [
     "usac_multi_grid", "usac_multi_draw_samples_napsac", "usac_multi_hypothesize_score_napsac", "usac_multi_run_napsac",
     "usac_multi_create_essential",
     "usac_multi_set_thresholds", "usac_multi_get_thresholds",
+    "usac_multi_lo_essential", "usac_multi_run_lo_essential",
 ]
 
 
@@ -326,6 +327,11 @@ def lib():
                                          _P(_MultiLoOutput)]),
         "usac_multi_run_lo": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
                                              _P(_MultiLoOutput), _P(_MultiProsacOutput), _P(_MultiPolishOutput), u8p]),
+        "usac_multi_lo_essential": (ctypes.c_int, [_vp, _P(_Params), ctypes.c_int, _P(ctypes.c_uint64), _P(Record),
+                                                   _P(_MultiLoOutput)]),
+        "usac_multi_run_lo_essential": (ctypes.c_int, [_vp, _P(_Params), _P(ctypes.c_uint64), _P(_MultiOutput),
+                                                       _P(_MultiLoOutput), _P(_MultiProsacOutput),
+                                                       _P(_MultiPolishOutput), u8p]),
         "usac_multi_sprt_setup": (ctypes.c_int, [_vp, u32p]),
         "usac_multi_hypothesize_score_sprt": (ctypes.c_int, [_vp, u32p, ctypes.c_uint32, i32p, ctypes.c_uint32,
                                                              _P(ctypes.c_uint64), ctypes.c_uint64, ctypes.c_float,
@@ -1020,7 +1026,7 @@ class MultiContext:
         segs = [cand[int(o) // 2 + q:int(o) // 2 + q + int(nc[q])].copy() for q, o in enumerate(self.offsets[:-1])]
         return bound, tl, segs
 
-    def lo(self, model_or_params, records, seeds=None, reset=True):
+    def lo(self, model_or_params, records, seeds=None, reset=True, _entry="multi_lo"):
         """usac_multi_lo: one LO call (inner + iterative LO-RANSAC, model.lo = InItLORsc / InItFLORsc) for
         every problem, records[p] (a Record or a record dict) taken as a new best.  The LO threshold, the
         draw counter and the counters persist between calls unless reset.  Returns (list of P record
@@ -1041,9 +1047,15 @@ class MultiContext:
         if sd is not None and sd.size != self.P:
             raise ValueError("seeds: one per problem (%d), got %d" % (self.P, sd.size))
         lo = (_MultiLoOutput * self.P)()
-        self._check(lib().usac_multi_lo(self._h, ctypes.byref(p), 1 if reset else 0, _ptr(sd, ctypes.c_uint64), recs,
-                                        lo), "multi_lo")
+        self._check(getattr(lib(), "usac_" + _entry)(self._h, ctypes.byref(p), 1 if reset else 0, _ptr(sd, ctypes.c_uint64),
+                                                     recs, lo), _entry)
         return [r.as_dict() for r in recs], [q.as_dict() for q in lo]
+
+    def lo_essential(self, model_or_params, records, seeds=None, reset=True):
+        """usac_multi_lo_essential: lo() on a context of essential-matrix problems (MultiContext.essential),
+        where lo() itself keeps refusing: sample size 5, the 8-point non-minimal fit, the squared Sampson
+        distance in calibrated coordinates.  Returns what lo() returns."""
+        return self.lo(model_or_params, records, seeds, reset, _entry="multi_lo_essential")
 
     def run_lo(self, model_or_params, seeds=None, polish=False):
         """usac_multi_run_lo: run() (model.sampler Uniform) or run_prosac() (Prosac) with LO-RANSAC of every
@@ -1051,6 +1063,11 @@ class MultiContext:
         "lo" (the problem's LO counters and threshold); with PROSAC also run_prosac()'s keys; polish=True
         adds "polished" and "inliers" as run() does."""
         return self._run("run_lo", model_or_params, seeds, polish, own=("lo", _MultiLoOutput), prosac="sampler")
+
+    def run_lo_essential(self, model_or_params, seeds=None, polish=False):
+        """usac_multi_run_lo_essential: run_lo() on a context of essential-matrix problems
+        (MultiContext.essential), where run_lo() itself keeps refusing.  Returns what run_lo() returns."""
+        return self._run("run_lo_essential", model_or_params, seeds, polish, own=("lo", _MultiLoOutput), prosac="sampler")
 
     def set_sprt_pool(self, seeds=None):
         """usac_multi_sprt_setup: the problems' SPRT pools (the reference's shuffle after srandom(seeds[p]),

@@ -1430,13 +1430,16 @@ hipError_t launch_multi_polish(hipStream_t st, int estimator, const float4 *pts,
 // lo_inliers: the iterative stage scores into the list it was just fitted from (pol_fit has the
 // points in LDS by then), and an improvement swaps the two pointers.  The length of max_inliers
 // stands for best_score->inlier_number wherever the reference sizes a list by it.
+// EST: H, F or E.  The essential estimator fits non-minimal samples with the 8-point algorithm
+// (essential_estimator.hpp:64-74: pol_fit<true>, as F) and differs from F in its residual and in the
+// sample size the `<= m` tests read (5).
 // PT: per-problem thresholds (g.thrs / g.steps in place of g.thr / g.step).  A template parameter and not a
 // null test: at 256 VGPRs with scratch the run-time form cost the scalar path 2 %.
 template <int EST, bool PT>
 __global__ __launch_bounds__(kPolT) void k_multi_lo(const float4 *__restrict__ pts_all,
                                                     const uint32_t *__restrict__ offsets, MultiLo g) {
-    constexpr bool FUND = EST != USAC_HOMOGRAPHY;
-    constexpr int32_t kM = FUND ? 7 : 4;
+    constexpr bool FUND = EST != USAC_HOMOGRAPHY;  // the fit: the 8-point algorithm for F and E
+    constexpr int32_t kM = EST == USAC_FUNDAMENTAL ? 7 : EST == USAC_ESSENTIAL ? 5 : 4;  // the estimator's sample size
     __shared__ __attribute__((aligned(16))) float4 s_q[kPolFitMax];
     __shared__ __attribute__((aligned(16))) double s_d[kPolSbWin * 64 * 45 > 2 * kPolFitMax ? kPolSbWin * 64 * 45
                                                                                             : 2 * kPolFitMax];
@@ -1618,6 +1621,10 @@ hipError_t launch_multi_lo(hipStream_t st, int estimator, const float4 *pts, con
         case USAC_FUNDAMENTAL:
             if (lo.thrs) hipLaunchKernelGGL((k_multi_lo<USAC_FUNDAMENTAL, true>), dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
             else hipLaunchKernelGGL((k_multi_lo<USAC_FUNDAMENTAL, false>), dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
+            break;
+        case USAC_ESSENTIAL:
+            if (lo.thrs) hipLaunchKernelGGL((k_multi_lo<USAC_ESSENTIAL, true>), dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
+            else hipLaunchKernelGGL((k_multi_lo<USAC_ESSENTIAL, false>), dim3(A), dim3(kPolT), 0, st, pts, offsets, lo);
             break;
         default:
             return hipErrorInvalidValue;

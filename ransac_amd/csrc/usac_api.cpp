@@ -4003,6 +4003,7 @@ void usac_lo_destroy(usac_lo *h) {
 //     split between k_multi_prosac_scan, which stores its candidates into pinned host memory, and
 //     ProsacTerminationCriteria::applyCandidates;
 //   LO (ABI 18): k_multi_lo (kernels_nonmin.hip) between the round's merge and the scan / the record copy;
+//     on an essential context through usac_multi_run_lo_essential alone (ABI 23);
 //   SPRT (ABI 19): the round's score launch replaced by SPRT verification (kernels_multi_sprt.hip), one
 //     test per problem and round, re-designed on the host between rounds (usac::SprtRounds) from the
 //     statistics that come down with the records.  LO and SPRT do not combine;
@@ -4084,7 +4085,15 @@ bool multi_is_e(const usac_multi *mc) { return mc->estimator == USAC_ESSENTIAL; 
 int multi_no_essential(usac_multi *mc, const char *who) {
     if (!multi_is_e(mc)) return USAC_OK;
     return fail(mc, USAC_ERR_UNSUPPORTED, std::string(who) + ": not for the essential estimator (multi-problem batches "
-                                                              "of essential matrices have no LO, SPRT or NAPSAC)");
+                                                              "of essential matrices have no SPRT or NAPSAC, and LO through "
+                                                              "usac_multi_lo_essential / usac_multi_run_lo_essential)");
+}
+
+// the entries of an essential context alone (ABI 23): `other` is the H / F entry with the same contract
+int multi_only_essential(usac_multi *mc, const char *who, const char *other) {
+    if (multi_is_e(mc)) return USAC_OK;
+    return fail(mc, USAC_ERR_UNSUPPORTED, std::string(who) + ": for the essential estimator only (homography and "
+                                                              "fundamental contexts: " + other + ")");
 }
 
 // device buffers and pinned staging for a round of A active problems x R hypotheses
@@ -4339,6 +4348,25 @@ usac::MultiLo multi_lo_args(usac_multi *mc, const usac_params *prm, uint64_t fir
 int multi_lo_fetch(usac_multi *mc, usac_multi_lo_output *lo) {
     if (lo) HIP_TRY(mc, hipMemcpy(lo, mc->lo_state.p, sizeof(usac_multi_lo_output) * (size_t)mc->P, hipMemcpyDeviceToHost));
     return USAC_OK;
+}
+
+// usac_multi_lo / usac_multi_lo_essential after their own checks: one LO call on recs, every record a new best
+int multi_lo_hook(usac_multi *mc, const usac_params *prm, int reset, const uint64_t *seeds, usac_record *recs,
+                  usac_multi_lo_output *lo, const char *who) {
+    int rc = multi_lo_check(mc, prm, who);
+    if (rc) return rc;
+    const uint32_t P = mc->P;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    if ((rc = multi_ensure(mc, P, 64, false)) || (rc = multi_lo_ensure(mc, prm, reset != 0))) return rc;
+    usac::MultiItem *items = multi_items_pin(mc);
+    for (uint32_t p = 0; p < P; p++) items[p] = usac::MultiItem{p, 0u, seeds ? seeds[p] : (uint64_t)prm->seed + p, 0u, 0u};
+    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)P, hipMemcpyHostToDevice, mc->stream));
+    HIP_TRY(mc, hipMemcpyAsync(mc->running.p, recs, sizeof(usac_record) * (size_t)P, hipMemcpyHostToDevice, mc->stream));
+    HIP_TRY(mc, usac::launch_multi_lo(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), P,
+                                      multi_lo_args(mc, prm, 0, true)));
+    HIP_TRY(mc, hipMemcpyAsync(recs, mc->running.p, sizeof(usac_record) * (size_t)P, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return multi_lo_fetch(mc, lo);
 }
 
 // ---- SPRT for multi-problem batches (ABI 19)
@@ -4606,8 +4634,9 @@ ProsacNext multi_prosac_round_end(usac_multi *mc, uint32_t a, const usac::MultiI
 // the active list (with sprt: and the entries' tests) up, the round, LO, the PROSAC scan, one copy of
 // the records (with sprt: and the statistics behind them) down, one wait; then per entry the bound, and
 // the entry is finished or kept.  Every check comes before the first change of the context's state.
+// lo_essential: the caller is usac_multi_run_lo_essential, the one entry that runs LO on an essential context.
 int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
-                     const MultiRunOutputs &outs) {
+                     const MultiRunOutputs &outs, bool lo_essential = false) {
     const bool prosac = prm->sampler == USAC_SAMPLER_PROSAC, sprt = prm->sprt != 0;
     const bool napsac = prm->sampler == USAC_SAMPLER_NAPSAC;
     const bool lo = prm->lo == USAC_LO_INITLORSC || prm->lo == USAC_LO_INITFLORSC;
@@ -4617,8 +4646,9 @@ int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *see
     if (!multi_round_ok(R)) return fail(mc, USAC_ERR_ARG, "batch must be a multiple of 64 in 64..8192");
     if (!multi_is_e(mc) && prm->dlt_mode != USAC_DLT_THIN && prm->dlt_mode != USAC_DLT_NULLSPACE)
         return fail(mc, USAC_ERR_ARG, "dlt_mode");
-    if (multi_is_e(mc) && (lo || sprt || napsac))
-        return fail(mc, USAC_ERR_UNSUPPORTED, "the essential estimator: uniform or PROSAC sampler, no LO, no SPRT");
+    if (multi_is_e(mc) && ((lo && !lo_essential) || sprt || napsac))
+        return fail(mc, USAC_ERR_UNSUPPORTED, "the essential estimator: uniform or PROSAC sampler, no SPRT, LO through "
+                                              "usac_multi_run_lo_essential");
     const uint32_t P = mc->P, m = mc->m;
     if (prosac)
         for (uint32_t p = 0; p < P; p++)
@@ -5038,20 +5068,14 @@ int usac_multi_lo(usac_multi *mc, const usac_params *prm, int reset, const uint6
                   usac_multi_lo_output *lo) {
     if (!mc || !prm || !recs) return USAC_ERR_ARG;
     if (const int no = multi_no_essential(mc, "usac_multi_lo")) return no;
-    int rc = multi_lo_check(mc, prm, "usac_multi_lo");
-    if (rc) return rc;
-    const uint32_t P = mc->P;
-    HIP_TRY(mc, hipSetDevice(mc->device));
-    if ((rc = multi_ensure(mc, P, 64, false)) || (rc = multi_lo_ensure(mc, prm, reset != 0))) return rc;
-    usac::MultiItem *items = multi_items_pin(mc);
-    for (uint32_t p = 0; p < P; p++) items[p] = usac::MultiItem{p, 0u, seeds ? seeds[p] : (uint64_t)prm->seed + p, 0u, 0u};
-    HIP_TRY(mc, hipMemcpyAsync(mc->items.p, items, sizeof(usac::MultiItem) * (size_t)P, hipMemcpyHostToDevice, mc->stream));
-    HIP_TRY(mc, hipMemcpyAsync(mc->running.p, recs, sizeof(usac_record) * (size_t)P, hipMemcpyHostToDevice, mc->stream));
-    HIP_TRY(mc, usac::launch_multi_lo(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), P,
-                                      multi_lo_args(mc, prm, 0, true)));
-    HIP_TRY(mc, hipMemcpyAsync(recs, mc->running.p, sizeof(usac_record) * (size_t)P, hipMemcpyDeviceToHost, mc->stream));
-    HIP_TRY(mc, stream_wait(mc->stream));
-    return multi_lo_fetch(mc, lo);
+    return multi_lo_hook(mc, prm, reset, seeds, recs, lo, "usac_multi_lo");
+}
+
+int usac_multi_lo_essential(usac_multi *mc, const usac_params *prm, int reset, const uint64_t *seeds, usac_record *recs,
+                            usac_multi_lo_output *lo) {
+    if (!mc || !prm || !recs) return USAC_ERR_ARG;
+    if (const int no = multi_only_essential(mc, "usac_multi_lo_essential", "usac_multi_lo")) return no;
+    return multi_lo_hook(mc, prm, reset, seeds, recs, lo, "usac_multi_lo_essential");
 }
 
 int usac_multi_run_lo(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
@@ -5064,6 +5088,18 @@ int usac_multi_run_lo(usac_multi *mc, const usac_params *prm, const uint64_t *se
     if (prm->sampler != USAC_SAMPLER_UNIFORM && prm->sampler != USAC_SAMPLER_PROSAC)
         return fail(mc, USAC_ERR_ARG, "usac_multi_run_lo: the uniform or the PROSAC sampler");
     return multi_run_driver(mc, prm, seeds, out, MultiRunOutputs{lo, pro, nullptr, pol, mask});
+}
+
+int usac_multi_run_lo_essential(usac_multi *mc, const usac_params *prm, const uint64_t *seeds, usac_multi_output *out,
+                                usac_multi_lo_output *lo, usac_multi_prosac_output *pro, usac_multi_polish_output *pol,
+                                uint8_t *mask) {
+    if (!mc || !prm || !out) return USAC_ERR_ARG;
+    if (const int no = multi_only_essential(mc, "usac_multi_run_lo_essential", "usac_multi_run_lo")) return no;
+    int rc = multi_lo_check(mc, prm, "usac_multi_run_lo_essential");
+    if (rc) return rc;
+    if (prm->sampler != USAC_SAMPLER_UNIFORM && prm->sampler != USAC_SAMPLER_PROSAC)
+        return fail(mc, USAC_ERR_ARG, "usac_multi_run_lo_essential: the uniform or the PROSAC sampler");
+    return multi_run_driver(mc, prm, seeds, out, MultiRunOutputs{lo, pro, nullptr, pol, mask}, true);
 }
 
 // ---- SPRT (ABI 19)

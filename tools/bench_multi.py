@@ -5,7 +5,8 @@
 
 --estimator essential takes calibrated pairs (synthetic.fundamental_points(normalized=True), threshold
 0.002) through MultiContext.essential; (b) is then the loop over Context(Essential) objects.  It offers
-the plain run, --polish and --sampler prosac.
+the plain run, --polish, --sampler prosac and --lo (through MultiContext.run_lo_essential); no --sprt and
+no --sampler napsac.
 
 (a) MultiContext.run: batch-granular RANSAC over all pairs, one launch chain per round.
 (b) the same schedule -- per pair, rounds of R hypotheses until min(max_iterations, standard bound)
@@ -274,7 +275,7 @@ def main_prosac(a, mc, model, est):
 
 
 def main_lo(a, mc, model, est):
-    """--lo: MultiContext.run_lo against the same run without LO (run, or run_prosac with --sampler
+    """--lo: MultiContext.run_lo (--estimator essential: run_lo_essential) against the same run without LO (run, or run_prosac with --sampler
     prosac) on the same inputs, alternated, host-timed, medians and spreads as in main()"""
     prosac = a.sampler == "prosac"
     base = usac.Model(model.threshold, mc.m, model.desired_prob, 5, est,
@@ -286,6 +287,7 @@ def main_lo(a, mc, model, est):
     lmodel.setDLTMode(model.dlt_mode)
     lmodel.lo = usac.LocOpt.InItLORsc if a.lo == "lorsc" else usac.LocOpt.InItFLORsc
     run_base = mc.run_prosac if prosac else mc.run
+    run_lo = mc.run_lo_essential if a.estimator == "essential" else mc.run_lo
 
     def summary(res, ms):
         rounds = [r["rounds"] for r in res]
@@ -299,11 +301,11 @@ def main_lo(a, mc, model, est):
         return d
 
     for _ in range(a.warmup):
-        rl, rb = mc.run_lo(lmodel, polish=a.polish), run_base(base, polish=a.polish)
+        rl, rb = run_lo(lmodel, polish=a.polish), run_base(base, polish=a.polish)
     tl, tb = [], []
     for _ in range(a.reps):
         t0 = time.perf_counter()
-        rl = mc.run_lo(lmodel, polish=a.polish)
+        rl = run_lo(lmodel, polish=a.polish)
         t1 = time.perf_counter()
         rb = run_base(base, polish=a.polish)
         t2 = time.perf_counter()
@@ -488,7 +490,8 @@ def main_thresholds(a, mc, model, est):
     rmodel.setSprt(a.sprt)
     if a.sprt:
         mc.set_sprt_pool()
-    call = (mc.run_napsac if a.sampler == "napsac" else mc.run_sprt if a.sprt else mc.run_lo if a.lo
+    run_lo = mc.run_lo_essential if a.estimator == "essential" else mc.run_lo
+    call = (mc.run_napsac if a.sampler == "napsac" else mc.run_sprt if a.sprt else run_lo if a.lo
             else mc.run_prosac if a.sampler == "prosac" else mc.run)
     thrs = [model.threshold] * mc.P
 
@@ -540,7 +543,7 @@ def main():
     ap.add_argument("--round", type=int, default=256, dest="R")
     ap.add_argument("--estimator", choices=["homography", "fundamental", "essential"], default="homography",
                     help="essential: MultiContext.essential over calibrated pairs, threshold 0.002; the plain run, "
-                         "--polish and --sampler prosac")
+                         "--polish, --sampler prosac and --lo (MultiContext.run_lo_essential)")
     ap.add_argument("--inlier-ratio", type=float, default=0.3)
     ap.add_argument("--max-iterations", type=int, default=2048)
     ap.add_argument("--dlt", choices=["thin", "nullspace"], default="nullspace")
@@ -577,8 +580,8 @@ def main():
         ap.error("--cluster applies to homography pairs")
 
     essential = a.estimator == "essential"
-    if essential and (a.lo or a.sprt or a.sampler == "napsac"):
-        ap.error("--estimator essential: the plain run, --polish and --sampler prosac (no LO, SPRT or NAPSAC)")
+    if essential and (a.sprt or a.sampler == "napsac"):
+        ap.error("--estimator essential: the plain run, --polish, --sampler prosac and --lo (no SPRT or NAPSAC)")
     est = {"homography": usac.ESTIMATOR.Homography, "fundamental": usac.ESTIMATOR.Fundamental,
            "essential": usac.ESTIMATOR.Essential}[a.estimator]
     thr, prob = (0.002 if essential else 2.0), 0.95
