@@ -72,7 +72,11 @@
  *                                  ABI 22: usac_multi_set_thresholds / usac_multi_get_thresholds, one inlier
  *                                  threshold per problem of a multi context in place of the calls' scalar;
  *                                  ABI 23: usac_multi_lo_essential / usac_multi_run_lo_essential, LO-RANSAC
- *                                  on multi contexts of essential-matrix problems (8-point non-minimal fit)
+ *                                  on multi contexts of essential-matrix problems (8-point non-minimal fit);
+ *                                  ABI 24: usac_multi_create_essential_pixels, an essential multi context from
+ *                                  pixel coordinates and per-pair intrinsics (converted on the device), with
+ *                                  usac_multi_set_pixel_thresholds, usac_multi_pixel_models and
+ *                                  usac_multi_get_points
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -87,7 +91,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 23
+#define USAC_ABI_VERSION 24
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -541,8 +545,42 @@ int usac_multi_create(usac_multi **out, int device, int estimator, const float *
  * usac_multi_run_lo_essential.
  * The solve's workspace is ~1.2 KB per sample; a round of more than 131 072 samples is solved in slices
  * of whole problems (USAC_MULTI_E5_SLICE in the environment at creation lowers the cap, for tests);
- * the results do not depend on the slice. */
+ * the results do not depend on the slice.
+ * A caller with pixel coordinates and intrinsics uses usac_multi_create_essential_pixels (ABI 24). */
 int usac_multi_create_essential(usac_multi **out, int device, const float *pts, const uint32_t *offsets, uint32_t P);
+/* usac_multi_create_essential from pixel coordinates (ABI 24).  pts_px: N_total rows (u1, v1, u2, v2) in
+ * pixels; K1, K2: P x 9 fp32, problem p's intrinsics of view 1 and view 2, row-major
+ * k[0..8] = fx, s, cx, 0, fy, cy, 0, 0, 1; K2 == NULL: both views use K1.  The rows are converted on the
+ * device, in place, in fp32 in this order (no contraction, correctly rounded division):
+ *   y = (v - cy) / fy,  x = ((u - cx) - s * y) / fx      view 1 under K1_p, view 2 under K2_p
+ * and the context keeps (x1, y1, x2, y2) alone, not the pixels.  The result is an essential multi context
+ * over those rows: every call behaves as on usac_multi_create_essential over them, bit for bit.
+ * USAC_ERR_ARG, before any device call: everything usac_multi_create_essential refuses, a NULL K1, and any
+ * K with a non-finite entry, fx <= 0, fy <= 0, k[3], k[6] or k[7] != 0, or k[8] != 1. */
+int usac_multi_create_essential_pixels(usac_multi **out, int device, const float *pts_px, const uint32_t *offsets,
+                                       uint32_t P, const float *K1, const float *K2);
+/* Per-problem thresholds from pixel tolerances, on a context from usac_multi_create_essential_pixels (ABI 24).
+ * t_px: n tolerances in pixels, n == 1 (one for all problems) or n == P.  Problem p's threshold is, in fp32,
+ *   f_p = ((fx1 + fy1) + (fx2 + fy2)) * 0.25f,  r = t / f_p,  thr_p = r * r
+ * computed on the host and installed as by usac_multi_set_thresholds: usac_multi_get_thresholds returns the
+ * values, usac_multi_set_thresholds(mc, NULL) clears them, and every contract of ABI 22 holds.
+ * The value is compared with the essential residual as it is, the mean of the two point-to-epipolar-line
+ * distances in calibrated units (EssentialEstimator::GetError, not squared): thr_p admits t^2 / f_p pixels of
+ * it, so t = 45 at f = 1000 gives the 0.002 that 2 pixels of distance are (Pixel coordinates).
+ * USAC_ERR_ARG, with nothing changed: a NULL mc or t_px, n other than 1 or P, a tolerance that is not finite
+ * and > 0, or a thr_p that is not finite and > 0.  USAC_ERR_UNSUPPORTED on a context not created from pixels. */
+int usac_multi_set_pixel_thresholds(usac_multi *mc, const float *t_px, uint32_t n);
+/* The pixel-space models of a context from usac_multi_create_essential_pixels (ABI 24): E, F: P x 9,
+ * F_p = K2_p^-T E_p K1_p^-1 in fp64 on the host (P x 9 values earn no launch).  The inverse of K is the closed
+ * form 1/fx, -s/(fx fy), (s cy - cx fy)/(fx fy); 0, 1/fy, -cy/fy; 0, 0, 1 from the fp32 entries widened to
+ * fp64; G = E K1^-1, then F = K2^-T G, every entry a three-term sum taken left to right; no normalisation,
+ * one cast to fp32 at the end.  E and F may be the same array.
+ * USAC_ERR_ARG for a NULL argument, USAC_ERR_UNSUPPORTED on a context not created from pixels. */
+int usac_multi_pixel_models(usac_multi *mc, const float *E, float *F);
+/* The context's resident points (ABI 24): out holds N_total x 4 floats, the rows every kernel of the context
+ * reads, by a device-to-host copy -- on a context from usac_multi_create_essential_pixels the calibrated rows
+ * the conversion wrote.  Any multi context.  USAC_ERR_ARG for a NULL argument. */
+int usac_multi_get_points(usac_multi *mc, float *out);
 void usac_multi_destroy(usac_multi *mc);
 const char *usac_multi_last_error(const usac_multi *mc);
 uint32_t usac_multi_num_problems(const usac_multi *mc);

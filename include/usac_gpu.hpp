@@ -529,7 +529,7 @@ private:
 };
 
 // P independent two-view problems of one estimator (Homography / Fundamental, or Essential through
-// MultiContext::essential) run together (usac_multi_*, ABI 15): points concatenated, offsets[P + 1]; sample, hypothesis and inlier indices
+// MultiContext::essential, or MultiContext::essentialPixels from pixel coordinates) run together (usac_multi_*, ABI 15): points concatenated, offsets[P + 1]; sample, hypothesis and inlier indices
 // are local to each problem, and every per-problem result equals a Context over that problem's
 // points bit for bit.  Not copyable.
 class MultiContext {
@@ -555,6 +555,22 @@ public:
         const uint32_t P = offsets.empty() ? 0u : (uint32_t)(offsets.size() - 1);
         const int rc = usac_multi_create_essential(&mc.mc_, device, points, offsets.data(), P);
         if (rc != USAC_OK) throw Error(rc, "usac_multi_create_essential failed");
+        return mc;
+    }
+    // essential() from pixel coordinates (usac_multi_create_essential_pixels, ABI 24): rows (u1, v1, u2, v2) in
+    // pixels, K1 / K2: P x 9 row-major intrinsics fx s cx 0 fy cy 0 0 1 of view 1 / view 2 (K2 empty: K1 for
+    // both).  The device converts the rows in place -- y = (v - cy) / fy, x = ((u - cx) - s * y) / fx in fp32 --
+    // and every member then works as on essential() over those rows (points() returns them).
+    static MultiContext essentialPixels(const float *points_px, const std::vector<uint32_t> &offsets,
+                                        const std::vector<float> &K1, const std::vector<float> &K2 = std::vector<float>(),
+                                        int device = 0) {
+        MultiContext mc(offsets);
+        const uint32_t P = offsets.empty() ? 0u : (uint32_t)(offsets.size() - 1);
+        if (K1.size() != 9 * (size_t)P || (!K2.empty() && K2.size() != 9 * (size_t)P))
+            throw Error(USAC_ERR_ARG, "essentialPixels: P x 9 intrinsics per view");
+        const int rc = usac_multi_create_essential_pixels(&mc.mc_, device, points_px, offsets.data(), P, K1.data(),
+                                                          K2.empty() ? nullptr : K2.data());
+        if (rc != USAC_OK) throw Error(rc, "usac_multi_create_essential_pixels failed");
         return mc;
     }
     ~MultiContext() {
@@ -588,6 +604,29 @@ public:
         const int rc = usac_multi_get_thresholds(mc_, out.data());
         if (rc < 0) check(rc, "MultiContext::thresholds");
         if (rc == 0) out.clear();
+        return out;
+    }
+
+    // usac_multi_set_pixel_thresholds (ABI 24, a context from essentialPixels): one pixel tolerance for all
+    // problems or one each; problem p's threshold becomes (t / f_p)^2, f_p the mean of its four focal lengths,
+    // installed as by set_thresholds (thresholds() shows the values).  Throws USAC_ERR_ARG (nothing changed) for
+    // a wrong length or a tolerance that is not finite and > 0, USAC_ERR_UNSUPPORTED on any other context.
+    void setPixelThresholds(const std::vector<float> &t_px) const {
+        check(usac_multi_set_pixel_thresholds(mc_, t_px.data(), (uint32_t)t_px.size()), "MultiContext::setPixelThresholds");
+    }
+    void setPixelThresholds(float t_px) const { setPixelThresholds(std::vector<float>(1, t_px)); }
+    // usac_multi_pixel_models (ABI 24, a context from essentialPixels): E, P x 9 -> F_p = K2_p^-T E_p K1_p^-1,
+    // fp64 on the host, not normalised
+    std::vector<float> pixelModels(const std::vector<float> &E) const {
+        if (E.size() != 9 * (size_t)problems()) throw Error(USAC_ERR_ARG, "pixelModels: P x 9 values");
+        std::vector<float> F(E.size());
+        check(usac_multi_pixel_models(mc_, E.data(), F.data()), "MultiContext::pixelModels");
+        return F;
+    }
+    // usac_multi_get_points (ABI 24): the N_total x 4 rows resident on the device
+    std::vector<float> points() const {
+        std::vector<float> out(4 * (size_t)(offsets_.empty() ? 0u : offsets_.back()));
+        check(usac_multi_get_points(mc_, out.data()), "MultiContext::points");
         return out;
     }
 

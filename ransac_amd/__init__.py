@@ -204,6 +204,8 @@ ABI_SYMBOLS = [
     "usac_multi_create_essential",
     "usac_multi_set_thresholds", "usac_multi_get_thresholds",
     "usac_multi_lo_essential", "usac_multi_run_lo_essential",
+    "usac_multi_create_essential_pixels", "usac_multi_set_pixel_thresholds", "usac_multi_pixel_models",
+    "usac_multi_get_points",
 ]
 
 
@@ -302,6 +304,11 @@ def lib():
         "usac_lo_destroy": (None, [_vp]),
         "usac_multi_create": (ctypes.c_int, [_P(_vp), ctypes.c_int, ctypes.c_int, f32p, u32p, ctypes.c_uint32]),
         "usac_multi_create_essential": (ctypes.c_int, [_P(_vp), ctypes.c_int, f32p, u32p, ctypes.c_uint32]),
+        "usac_multi_create_essential_pixels": (ctypes.c_int, [_P(_vp), ctypes.c_int, f32p, u32p, ctypes.c_uint32, f32p,
+                                                              f32p]),
+        "usac_multi_set_pixel_thresholds": (ctypes.c_int, [_vp, f32p, ctypes.c_uint32]),
+        "usac_multi_pixel_models": (ctypes.c_int, [_vp, f32p, f32p]),
+        "usac_multi_get_points": (ctypes.c_int, [_vp, f32p]),
         "usac_multi_destroy": (None, [_vp]),
         "usac_multi_last_error": (ctypes.c_char_p, [_vp]),
         "usac_multi_num_problems": (ctypes.c_uint32, [_vp]),
@@ -782,7 +789,11 @@ class MultiContext:
     come from MultiContext.essential(point_sets): calibrated coordinates (K^-1 x), 5-point samples, one
     slot per sample (count -1 on a sample without a model).  On such a context hypothesize_score,
     run (with and without polish), inliers, polish, draw_samples, run_prosac and prosac_scan work as
-    for H / F; the LO, SPRT and NAPSAC methods raise UsacError(-3)."""
+    for H / F; the LO, SPRT and NAPSAC methods raise UsacError(-3).
+
+    MultiContext.essential_pixels(point_sets, K1, K2) is the same context from pixel coordinates and
+    per-pair intrinsics: the device converts the rows, `points` holds the calibrated rows it wrote, and
+    set_pixel_thresholds / pixel_models speak pixels on the way in and out."""
 
     def __init__(self, estimator, point_sets, device=0):
         self._create(ESTIMATOR(estimator), point_sets, device, False)
@@ -795,7 +806,32 @@ class MultiContext:
         self._create(ESTIMATOR.Essential, point_sets, device, True)
         return self
 
-    def _create(self, estimator, point_sets, device, essential):
+    @staticmethod
+    def _intrinsics(K, P, name):
+        """one 3 x 3 matrix (for all problems) or P of them -> P x 9 float32"""
+        K = np.asarray(K, dtype=np.float32)
+        if K.shape == (3, 3):
+            K = np.broadcast_to(K, (P, 3, 3))
+        if K.shape != (P, 3, 3):
+            raise ValueError("%s must be 3 x 3 or P x 3 x 3 (P = %d), got %s" % (name, P, K.shape))
+        return np.ascontiguousarray(K.reshape(P, 9))
+
+    @classmethod
+    def essential_pixels(cls, point_sets, K1, K2=None, device=0):
+        """usac_multi_create_essential_pixels: essential-matrix problems from pixel rows (u1, v1, u2, v2) and
+        intrinsics K = [[fx, s, cx], [0, fy, cy], [0, 0, 1]] -- K1 for view 1, K2 for view 2 (None: K1), each one
+        3 x 3 matrix for all problems or P x 3 x 3.  The device converts the rows in place in fp32,
+        y = (v - cy) / fy, x = ((u - cx) - s * y) / fx, and `points` is read back from it: the calibrated rows
+        every other method works on.  UsacError(-1) for a K that is not finite, upper triangular with
+        fx, fy > 0 and a last row of 0 0 1."""
+        self = cls.__new__(cls)
+        P = len(point_sets)
+        k1 = cls._intrinsics(K1, P, "K1")
+        k2 = None if K2 is None else cls._intrinsics(K2, P, "K2")
+        self._create(ESTIMATOR.Essential, point_sets, device, True, k1, k2)
+        return self
+
+    def _create(self, estimator, point_sets, device, essential, k1=None, k2=None):
         L = lib()
         self.estimator = estimator
         self._h = None
@@ -811,7 +847,13 @@ class MultiContext:
         self.points = np.ascontiguousarray(self.points, dtype=np.float32)
         self.dlt_mode = DLT.THIN
         h = _vp()
-        if essential:
+        if k1 is not None:
+            name = "usac_multi_create_essential_pixels"
+            rc = L.usac_multi_create_essential_pixels(ctypes.byref(h), device, _ptr(self.points, ctypes.c_float),
+                                                      _ptr(self.offsets, ctypes.c_uint32), self.P,
+                                                      _ptr(k1, ctypes.c_float),
+                                                      None if k2 is None else _ptr(k2, ctypes.c_float))
+        elif essential:
             name = "usac_multi_create_essential"
             rc = L.usac_multi_create_essential(ctypes.byref(h), device, _ptr(self.points, ctypes.c_float),
                                                _ptr(self.offsets, ctypes.c_uint32), self.P)
@@ -825,6 +867,37 @@ class MultiContext:
         self._h = h
         self.m = {ESTIMATOR.Fundamental: 7, ESTIMATOR.Essential: 5}.get(self.estimator, 4)
         self.spk = 3 if self.estimator == ESTIMATOR.Fundamental else 1
+        if k1 is not None:  # the rows the device wrote replace the pixels
+            self.points = self.resident_points()
+
+    def resident_points(self):
+        """usac_multi_get_points: the N_total x 4 rows resident on the device (a copy)."""
+        out = np.zeros((int(self.offsets[-1]), 4), dtype=np.float32)
+        self._check(lib().usac_multi_get_points(self._h, _ptr(out, ctypes.c_float)), "multi_get_points")
+        return out
+
+    def set_pixel_thresholds(self, t):
+        """usac_multi_set_pixel_thresholds (a context from essential_pixels): a pixel tolerance for all
+        problems, or P of them; problem p's threshold becomes (t / f_p)^2 with f_p the mean of its four focal
+        lengths, in fp32, installed as by set_thresholds (`thresholds` shows the values, set_thresholds(None)
+        clears them).  The essential residual it is compared with is a distance in calibrated units, not a
+        squared one, so (t / f)^2 admits t^2 / f pixels of it: 45 px at f = 1000 give 0.002.  UsacError(-1),
+        nothing changed, for a wrong length or a tolerance that is not finite and > 0; UsacError(-3) on a
+        context not created from pixels."""
+        t = np.ascontiguousarray(t, dtype=np.float32).ravel()
+        self._check(lib().usac_multi_set_pixel_thresholds(self._h, _ptr(t, ctypes.c_float), t.size),
+                    "multi_set_pixel_thresholds")
+
+    def pixel_models(self, E):
+        """usac_multi_pixel_models (a context from essential_pixels): E, P x 3 x 3 or P x 9 essential matrices ->
+        F_p = K2_p^-T E_p K1_p^-1 in the same shape, computed in fp64 on the host, not normalised."""
+        E = np.ascontiguousarray(E, dtype=np.float32)
+        if E.size != 9 * self.P:
+            raise ValueError("pixel_models: P x 9 values (P = %d), got %s" % (self.P, E.shape))
+        F = np.zeros_like(E)
+        self._check(lib().usac_multi_pixel_models(self._h, _ptr(E, ctypes.c_float), _ptr(F, ctypes.c_float)),
+                    "multi_pixel_models")
+        return F
 
     def close(self):
         if getattr(self, "_h", None):

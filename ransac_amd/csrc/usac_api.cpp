@@ -4057,6 +4057,9 @@ struct usac_multi {
     std::vector<float> thr_host;
     DevBuf thrs, lo_steps;
     uint32_t lo_steps_mult = 0, lo_steps_iters = 0;  // what lo_steps was computed for (iters 0: nothing)
+    // Pixel coordinates (ABI 24): a context created from pixels keeps its problems' intrinsics (P x 9 each; k2 =
+    // k1 where the caller gave one K) for the pixel thresholds and the pixel-space models; else both are empty
+    std::vector<float> k1, k2;
     std::string err;
 };
 
@@ -4864,6 +4867,46 @@ int usac_multi_create_essential(usac_multi **out, int device, const float *pts, 
     return multi_create(out, device, USAC_ESSENTIAL, pts, offsets, P);
 }
 
+int usac_multi_create_essential_pixels(usac_multi **out, int device, const float *pts_px, const uint32_t *offsets,
+                                       uint32_t P, const float *K1, const float *K2) {
+    if (!out) return USAC_ERR_ARG;
+    *out = nullptr;
+    if (!K1 || P == 0 || P > usac::kMultiMaxActive) return USAC_ERR_ARG;
+    if (!K2) K2 = K1;
+    for (uint32_t p = 0; p < P; p++)
+        if (!usac::pixel_k_ok(K1 + 9 * (size_t)p) || !usac::pixel_k_ok(K2 + 9 * (size_t)p)) return USAC_ERR_ARG;
+    usac_multi *mc = nullptr;
+    const int rc = multi_create(&mc, device, USAC_ESSENTIAL, pts_px, offsets, P);
+    if (rc) return rc;
+    mc->k1.assign(K1, K1 + 9 * (size_t)P);
+    mc->k2.assign(K2, K2 + 9 * (size_t)P);
+    // the rows in place: the problems' intrinsics up, one launch, and the call returns when it has finished
+    std::vector<float> calib(usac::kCalibFloats * (size_t)P);
+    for (uint32_t p = 0; p < P; p++)
+        usac::pixel_pack(K1 + 9 * (size_t)p, K2 + 9 * (size_t)p, calib.data() + usac::kCalibFloats * (size_t)p);
+    DevBuf dcal;
+    hipError_t e = dcal.reserve(sizeof(float) * calib.size());
+    const char *what = "hipMalloc intrinsics";
+    if (e == hipSuccess) {
+        e = hipMemcpy(dcal.p, calib.data(), sizeof(float) * calib.size(), hipMemcpyHostToDevice);
+        what = "hipMemcpy intrinsics";
+    }
+    if (e == hipSuccess) {
+        e = usac::launch_multi_calibrate(mc->stream, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), P, mc->n_total,
+                                         static_cast<const float *>(dcal.p));
+        what = "k_multi_calibrate";
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(mc->stream);
+    dcal.release();
+    if (e != hipSuccess) {
+        fprintf(stderr, "usac_multi_create_essential_pixels: %s: %s\n", what, hipGetErrorString(e));
+        usac_multi_destroy(mc);
+        return USAC_ERR_HIP;
+    }
+    *out = mc;
+    return USAC_OK;
+}
+
 void usac_multi_destroy(usac_multi *mc) {
     if (!mc) return;
     (void)hipSetDevice(mc->device);
@@ -4910,6 +4953,45 @@ int usac_multi_get_thresholds(const usac_multi *mc, float *out) {
     if (mc->thr_host.empty()) return 0;
     if (out) std::copy(mc->thr_host.begin(), mc->thr_host.end(), out);
     return 1;
+}
+
+// ---- pixel coordinates (ABI 24)
+int usac_multi_set_pixel_thresholds(usac_multi *mc, const float *t_px, uint32_t n) {
+    if (!mc) return USAC_ERR_ARG;
+    if (mc->k1.empty())
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_set_pixel_thresholds: the context was not created from pixel "
+                                              "coordinates (usac_multi_create_essential_pixels)");
+    if (!t_px || (n != 1 && n != mc->P))
+        return fail(mc, USAC_ERR_ARG, "usac_multi_set_pixel_thresholds: one tolerance, or one per problem");
+    std::vector<float> thr(mc->P);
+    for (uint32_t p = 0; p < mc->P; p++) {
+        const float t = t_px[n == 1 ? 0 : p];
+        if (!(t > 0.f) || !std::isfinite(t))
+            return fail(mc, USAC_ERR_ARG, "usac_multi_set_pixel_thresholds: problem " + std::to_string(p) +
+                                              ": the tolerance must be finite and > 0");
+        thr[p] = usac::pixel_threshold(mc->k1.data() + 9 * (size_t)p, mc->k2.data() + 9 * (size_t)p, t);
+    }
+    return usac_multi_set_thresholds(mc, thr.data());  // refuses a threshold that is not finite and > 0
+}
+
+int usac_multi_pixel_models(usac_multi *mc, const float *E, float *F) {
+    if (!mc) return USAC_ERR_ARG;
+    if (mc->k1.empty())
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_pixel_models: the context was not created from pixel "
+                                              "coordinates (usac_multi_create_essential_pixels)");
+    if (!E || !F) return fail(mc, USAC_ERR_ARG, "usac_multi_pixel_models: NULL argument");
+    for (uint32_t p = 0; p < mc->P; p++)
+        usac::pixel_model(mc->k1.data() + 9 * (size_t)p, mc->k2.data() + 9 * (size_t)p, E + 9 * (size_t)p, F + 9 * (size_t)p);
+    return USAC_OK;
+}
+
+int usac_multi_get_points(usac_multi *mc, float *out) {
+    if (!mc) return USAC_ERR_ARG;
+    if (!out) return fail(mc, USAC_ERR_ARG, "usac_multi_get_points: NULL argument");
+    // every call waits for its stream before it returns: nothing of this context is in flight
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    HIP_TRY(mc, hipMemcpy(out, mc->pts.p, sizeof(float) * 4 * (size_t)mc->n_total, hipMemcpyDeviceToHost));
+    return USAC_OK;
 }
 
 int usac_multi_hypothesize_score(usac_multi *mc, const uint32_t *problems, uint32_t n_problems,

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/usac_gpu.h"
+#include "usac_pixels.hpp"
 
 namespace usac {
 
@@ -467,6 +468,10 @@ struct MultiLo {
 };
 hipError_t launch_multi_lo(hipStream_t st, int estimator, const float4 *pts, const uint32_t *offsets, uint32_t A,
                            const MultiLo &lo);
+// pixel coordinates -> calibrated coordinates, in place over the concatenated rows (kernels_multi_calib.hip,
+// ABI 24): calib holds kCalibFloats floats per problem in pixel_pack's layout (usac_pixels.hpp), 16-byte aligned
+hipError_t launch_multi_calibrate(hipStream_t st, float4 *pts, const uint32_t *offsets, uint32_t P, uint32_t n_total,
+                                  const float *calib);
 
 // k nearest neighbours of every point (kernels_knn.hip, nearest_neighbors.cpp:69-128):
 // idx / d2 (nullable) n x k, self excluded, ascending distance, ties by index; 1 <= k <= 32

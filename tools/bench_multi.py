@@ -59,6 +59,16 @@ prosac|napsac / --polish the run those flags select, alternated on the same cont
 set and cleared outside the timed window).  The two results must be equal bit for bit (exit status 1
 otherwise); the difference of the two medians is the cost of the indexed path.  No loop over single
 contexts in this mode.
+
+--estimator essential --pixels times the creation of an essential multi context from pixel coordinates: the
+pairs are pixel correspondences under per-pair intrinsics whose focal lengths differ, and
+MultiContext.essential_pixels + set_pixel_thresholds (upload, the conversion kernel, the read-back of the rows
+into `points`) is alternated with the caller's path without them -- a float32 numpy conversion of every set
+by the same formulas, MultiContext.essential, set_thresholds with (t_px / f)^2 computed per pair.  Reported
+for both: min / median / max ms over the repetitions, the numpy conversion's share of the second, and the C
+entry alone (usac_multi_create_essential_pixels + usac_multi_destroy, no read-back).  The two contexts'
+run(polish=True) results must be equal bit for bit (exit status 1 otherwise).  The contexts are closed
+outside the timed windows.
 """
 import argparse
 import ctypes
@@ -536,6 +546,120 @@ def main_thresholds(a, mc, model, est):
     return 0 if equal else 1
 
 
+def pixel_pairs(pairs, points, ratio):
+    """(pixel sets, K P x 3 x 3): the calibrated pairs of make_pairs seen through cameras whose focal lengths run
+    from 800 to 1600 px over the pairs and whose principal points differ"""
+    cal = make_pairs("essential", pairs, points, ratio)
+    K = np.zeros((pairs, 3, 3), dtype=np.float32)
+    sets = []
+    for p, x in enumerate(cal):
+        f = np.float32(800.0 + 800.0 * p / max(pairs - 1, 1))
+        cx, cy = np.float32(640.0 + (p % 7)), np.float32(360.0 + (p % 5))
+        K[p] = [[f, 0, cx], [0, f, cy], [0, 0, 1]]
+        sets.append(np.ascontiguousarray(x * f + np.array([cx, cy, cx, cy], dtype=np.float32), dtype=np.float32))
+    return sets, K
+
+
+def numpy_calibrate(sets, K):
+    """what a caller does today: every set to calibrated coordinates in float32, by the library's formulas"""
+    out = []
+    for px, k in zip(sets, K):
+        fx, sk, cx, fy, cy = k[0, 0], k[0, 1], k[0, 2], k[1, 1], k[1, 2]
+        y1 = (px[:, 1] - cy) / fy
+        y2 = (px[:, 3] - cy) / fy
+        out.append(np.stack([((px[:, 0] - cx) - sk * y1) / fx, y1, ((px[:, 2] - cx) - sk * y2) / fx, y2], axis=1))
+    return out
+
+
+def main_pixels(a, model):
+    """--pixels: creation from pixel coordinates on the device against the numpy conversion + creation from
+    calibrated rows, alternated, host-timed"""
+    # (t / f)^2 against the mean epipolar distance in calibrated units: 45 px give 0.0032 .. 0.0008 over the focal
+    # lengths, around the 0.002 of the other essential modes
+    t_px = np.float32(45.0)
+    sets, K = pixel_pairs(a.pairs, a.points, a.inlier_ratio)
+    L = usac.lib()
+    f32p, u32p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
+
+    def create_pixels():
+        t0 = time.perf_counter()
+        mc = usac.MultiContext.essential_pixels(sets, K)
+        mc.set_pixel_thresholds(t_px)
+        return mc, (time.perf_counter() - t0) * 1e3
+
+    def create_numpy():
+        t0 = time.perf_counter()
+        rows = numpy_calibrate(sets, K)
+        t1 = time.perf_counter()
+        mc = usac.MultiContext.essential(rows)
+        f = ((K[:, 0, 0] + K[:, 1, 1]) + (K[:, 0, 0] + K[:, 1, 1])) * np.float32(0.25)
+        r = t_px / f
+        mc.set_thresholds(r * r)
+        t2 = time.perf_counter()
+        return mc, (t2 - t0) * 1e3, (t1 - t0) * 1e3
+
+    flat = np.ascontiguousarray(np.concatenate(sets, axis=0), dtype=np.float32)
+    offs = np.zeros(a.pairs + 1, dtype=np.uint32)
+    offs[1:] = np.cumsum([len(x) for x in sets])
+    k9 = np.ascontiguousarray(K.reshape(a.pairs, 9))
+
+    def create_c():
+        h = ctypes.c_void_p()
+        t0 = time.perf_counter()
+        rc = L.usac_multi_create_essential_pixels(ctypes.byref(h), 0, flat.ctypes.data_as(f32p), offs.ctypes.data_as(u32p),
+                                                  a.pairs, k9.ctypes.data_as(f32p), None)
+        ms = (time.perf_counter() - t0) * 1e3
+        if rc != 0:
+            raise usac.UsacError(rc, "usac_multi_create_essential_pixels")
+        L.usac_multi_destroy(h)
+        return ms
+
+    for _ in range(a.warmup):
+        create_pixels()[0].close()
+        create_numpy()[0].close()
+        create_c()
+    tp, tn, tconv, tc = [], [], [], []
+    for _ in range(a.reps):
+        mc, ms = create_pixels()
+        mc.close()
+        tp.append(ms)
+        mc, ms, conv = create_numpy()
+        mc.close()
+        tn.append(ms)
+        tconv.append(conv)
+        tc.append(create_c())
+
+    mp, _ = create_pixels()
+    mn, _, _ = create_numpy()
+    rows_equal = mp.points.tobytes() == mn.points.tobytes()
+    thr_equal = mp.thresholds.tobytes() == mn.thresholds.tobytes()
+    rp, rn = mp.run(model, polish=True), mn.run(model, polish=True)
+    equal = same_bits(rp, rn)
+    mp.close()
+    mn.close()
+
+    def summary(ms):
+        return {"min_ms": round(min(ms), 3), "median_ms": round(statistics.median(ms), 3), "max_ms": round(max(ms), 3)}
+
+    line = {"bench": "multi_pixels", "estimator": a.estimator, "pairs": a.pairs, "points": a.points, "round": a.R,
+            "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio, "reps": a.reps, "t_px": float(t_px),
+            "focal_lengths": [float(K[0, 0, 0]), float(K[-1, 0, 0])],
+            "from_pixels": summary(tp), "numpy_then_create": summary(tn), "numpy_conversion_alone": summary(tconv),
+            "c_entry_alone": summary(tc),
+            "ratio_numpy_path_over_pixels": round(statistics.median(tn) / statistics.median(tp), 2),
+            "rows_bit_equal": bool(rows_equal), "thresholds_bit_equal": bool(thr_equal),
+            "run_polished_bit_equal": bool(equal),
+            "mean_best_inliers": round(float(np.mean([r["best"]["inliers"] for r in rp])), 2),
+            "mean_polished_inliers": round(float(np.mean([r["polished"]["inliers"] for r in rp])), 2)}
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    return 0 if equal and rows_equal and thr_equal else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=512)
@@ -569,7 +693,13 @@ def main():
                     help="the selected multi run with P per-problem thresholds equal to the scalar "
                          "(MultiContext.set_thresholds) against the same run without them: bit-equal results, and the "
                          "cost of the indexed path")
+    ap.add_argument("--pixels", action="store_true",
+                    help="--estimator essential: creation from pixel coordinates (MultiContext.essential_pixels + "
+                         "set_pixel_thresholds) against the numpy conversion + MultiContext.essential + set_thresholds; "
+                         "the two contexts' polished runs must be bit-equal")
     a = ap.parse_args()
+    if a.pixels and (a.estimator != "essential" or a.sprt or a.lo or a.per_problem_thr or a.sampler != "uniform"):
+        ap.error("--pixels goes with --estimator essential alone")
     if a.reps < 5:
         ap.error("--reps must be at least 5")
     if a.sprt and a.lo:
@@ -592,6 +722,8 @@ def main():
     model.max_iterations, model.batch, model.seed = a.max_iterations, a.R, 1
     model.setDLTMode(usac.DLT.NULLSPACE if a.dlt == "nullspace" else usac.DLT.THIN)
     seeds = [model.seed + p for p in range(a.pairs)]
+    if a.pixels:
+        return main_pixels(a, model)
 
     mc = usac.MultiContext.essential(sets) if essential else usac.MultiContext(est, sets)
     if a.per_problem_thr:
