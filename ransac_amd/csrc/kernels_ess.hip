@@ -41,8 +41,6 @@
 #include "usac_kernels.h"
 #include "usac_multi_sampler.hpp"
 
-#include <stdlib.h>
-
 #include <algorithm>
 
 namespace usac {
@@ -286,13 +284,8 @@ __global__ __launch_bounds__(64) void k_e5_roots(uint32_t B, E5Work w) {
 
 // rpoly's work budget per listed sample in k_e5_order (usac_rpoly.hpp counts K-polynomial divisions:
 // 3 per fixed-shift step, 4 per quadratic and 2 per real variable-shift iteration; cfg4: median ~90,
-// p99 ~310, a 20-shift failure ~20 000); USAC_E5_BUDGET overrides (A/B)
+// p99 ~310, a 20-shift failure ~20 000)
 constexpr int kE5RootBudget = 320;
-
-int e5_budget() {
-    static const int b = getenv("USAC_E5_BUDGET") ? atoi(getenv("USAC_E5_BUDGET")) : kE5RootBudget;
-    return b;
-}
 
 // five_points.cpp:239-273 over rpoly's order (the oracle's essential_5pt_all): rpoly's real zeros in
 // the order found, each standing for the candidate value nearest to it (first on ties); the first whose
@@ -520,8 +513,7 @@ __global__ __launch_bounds__(64) void k_multi_e5_select(uint32_t R, E5Work w, fl
 
 hipError_t launch_solve_e5(hipStream_t st, const float4 *pts, uint32_t n, const int32_t *samples_in,
                            int32_t *samples_out, uint32_t B, DevSampler ds, uint64_t first_hyp, float *models,
-                           int32_t *counts, uint32_t *list, uint32_t *list_n, void *workspace, hipStream_t thin,
-                           hipEvent_t ev_in, hipEvent_t ev_out) {
+                           int32_t *counts, uint32_t *list, uint32_t *list_n, void *workspace) {
     const E5Work w = e5_carve(workspace, B);
     hipError_t e = hipMemsetAsync(list_n, 0, sizeof(uint32_t), st);
     if (e == hipSuccess) e = hipMemsetAsync(w.npairs, 0, sizeof(uint32_t), st);
@@ -535,22 +527,9 @@ hipError_t launch_solve_e5(hipStream_t st, const float4 *pts, uint32_t n, const 
     hipLaunchKernelGGL(k_e5_null, g10, dim3(64), 0, st, B, 10 * B, w);
     hipLaunchKernelGGL(k_e5_check, g10, dim3(64), 0, st, pts, B, 10 * B, w);
     hipLaunchKernelGGL(k_e5_select, g1, dim3(64), 0, st, B, w, models, counts, list, list_n);
-    // the order kernels hold one ~260-register wave per SIMD for hundreds of microseconds: on a CU-masked
-    // stream they keep off most of the chip, where the other batches' wide kernels run
-    hipStream_t os = st;
-    if (thin && ev_in && ev_out) {
-        if ((e = hipEventRecord(ev_in, st)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(thin, ev_in, 0)) != hipSuccess) return e;
-        os = thin;
-    }
-    hipLaunchKernelGGL(k_e5_order, g1, dim3(64), 0, os, B, w, nullptr, e5_budget(), models);
-    hipLaunchKernelGGL(k_e5_order_tail, dim3(std::min(1024u, (B + 63) / 64)), dim3(64), 0, os, B, w, nullptr, models);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (os != st) {
-        if ((e = hipEventRecord(ev_out, os)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(st, ev_out, 0)) != hipSuccess) return e;
-    }
-    return hipSuccess;
+    hipLaunchKernelGGL(k_e5_order, g1, dim3(64), 0, st, B, w, nullptr, kE5RootBudget, models);
+    hipLaunchKernelGGL(k_e5_order_tail, dim3(std::min(1024u, (B + 63) / 64)), dim3(64), 0, st, B, w, nullptr, models);
+    return hipGetLastError();
 }
 
 // multi-problem batches (usac_kernels.h launch_multi_solve_e5): the workspace of a slice, then, when the
@@ -590,7 +569,7 @@ hipError_t launch_multi_solve_e5(hipStream_t st, const MultiRound &r) {
         hipLaunchKernelGGL(k_multi_e5_select, ga, dim3(64), 0, st, r.R, w, models, g0, r.counts + g0, r.sums + g0,
                            r.list + g0, r.list_n + a0);
         // a multi context has one stream: the order kernels run on it (DESIGN.md §8b "Essential")
-        hipLaunchKernelGGL(k_e5_order, g1, dim3(64), 0, st, B, w, nullptr, e5_budget(), models);
+        hipLaunchKernelGGL(k_e5_order, g1, dim3(64), 0, st, B, w, nullptr, kE5RootBudget, models);
         hipLaunchKernelGGL(k_e5_order_tail, dim3(std::min(1024u, B / 64)), dim3(64), 0, st, B, w, nullptr, models);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (staged) {  // the slice's [9][B] into its columns of the round's [9][A R]
@@ -622,7 +601,7 @@ hipError_t launch_e5_roots_selftest(hipStream_t st, const double *coef, uint32_t
     if (e != hipSuccess) return e;
     const dim3 g1((B + 63) / 64);
     hipLaunchKernelGGL(k_e5_list_all, g1, dim3(64), 0, st, B, w);
-    hipLaunchKernelGGL(k_e5_order, g1, dim3(64), 0, st, B, w, coef, e5_budget(), nullptr);
+    hipLaunchKernelGGL(k_e5_order, g1, dim3(64), 0, st, B, w, coef, kE5RootBudget, nullptr);
     hipLaunchKernelGGL(k_e5_order_tail, dim3(std::min(1024u, (B + 63) / 64)), dim3(64), 0, st, B, w, coef, nullptr);
     hipLaunchKernelGGL(k_e5_njt_copy, g1, dim3(64), 0, st, B, w, nroots);
     e = hipGetLastError();

@@ -35,8 +35,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "usac_device.hpp"
@@ -269,8 +267,10 @@ __device__ __forceinline__ void h16_drain(uint32_t cnt, uint32_t head, const uin
 // (hypothesis t, component r) with i = (rho & 3) + 4 (rho >> 3), t = 5 ((rho >> 2) & 1) + i / 3, r = i % 3
 // (i < 15; row i = 15 of each lane half is spare), so that the D register q of lane half hf holds
 // (hypothesis 5 hf + q / 3, component q % 3): each lane owns whole (ex, ey, zr) triples of five
-// hypotheses of each tile for its point.  U = 1 always: the blocks of a trip run one after the other
-// (the parameter stays in the kernel's name, which the bench and the profile summaries match on).
+// hypotheses of each tile for its point.  U = 1 always: the blocks of a trip run one after the other.
+// Only <2, 1, 8> is built (four tiles per wave measured 440 M hyp/s on cfg2 and 7 waves per SIMD
+// 551-555 M against 559-570 M); the three parameters stay in the kernel's name, which
+// the bench and the profile summaries match on.
 template <int NA, int U, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_score_h16(const half8 *__restrict__ feat, const float4 *__restrict__ pts,
                                                    uint32_t n, const half8 *__restrict__ rows,
@@ -439,7 +439,6 @@ int h16_fixed_point(float thr) {
 hipError_t launch_score_h16(hipStream_t st, const void *feat, const float4 *pts, uint32_t n, const void *rows,
                             const float *fm, const float *models, uint32_t B, float thr, int chunks, void *part,
                             int32_t *counts, float *sums, bool finish) {
-    static const int na = getenv("USAC_H16_NA") ? atoi(getenv("USAC_H16_NA")) : 2;  // 10-hypothesis tiles per wave
     if (chunks < 1 || n == 0 || n > 0x2000000u) return hipErrorInvalidValue;  // 25-bit point indices in the queue
     // Σ in fixed point: a stage-B term is < 2 T (1 + 2^-15) (S ~ 2 err of an inlier, err < thr = T / 2), so
     // 2^fx with 2 T 2^fx <= 2^40 leaves 2^23 terms per hypothesis and chunk below 2^63: a chunk of more
@@ -450,19 +449,11 @@ hipError_t launch_score_h16(hipStream_t st, const void *feat, const float4 *pts,
     const double fxs = ldexp(1.0, fx);
     unsigned long long *sp = static_cast<unsigned long long *>(part);  // 8-byte words first (alignment)
     uint32_t *cp = reinterpret_cast<uint32_t *>(sp + (size_t)chunks * B);
-    // min waves per SIMD: 8 (64 VGPRs, no spills) -- same-box cfg2 559-570 vs 551-555 M hyp/s at 7
-    static const int wpe = getenv("USAC_H16_WPE") ? atoi(getenv("USAC_H16_WPE")) : 8;
-#define H16(NA_, U_, W_)                                                                                            \
-    hipLaunchKernelGGL((k_score_h16<NA_, U_, W_>), dim3((B + 40 * NA_ - 1) / (40 * NA_), chunks), dim3(256), 0, st,   \
-                       static_cast<const half8 *>(feat), pts, n, static_cast<const half8 *>(rows), fm, models, B, thr, \
-                       fxs, cp, sp)
-    if (na == 4)
-        H16(4, 1, 1);
-    else if (wpe == 8)
-        H16(2, 1, 8);
-    else
-        H16(2, 1, 1);
-#undef H16
+    // two 10-hypothesis tiles per wave; min waves per SIMD: 8 (64 VGPRs, no spills) -- same-box cfg2
+    // 559-570 vs 551-555 M hyp/s at 7
+    hipLaunchKernelGGL((k_score_h16<2, 1, 8>), dim3((B + 79) / 80, chunks), dim3(256), 0, st,
+                       static_cast<const half8 *>(feat), pts, n, static_cast<const half8 *>(rows), fm, models, B, thr,
+                       fxs, cp, sp);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !finish) return e;  // !finish: the caller's launch_argmax_h16 adds the chunks
     hipLaunchKernelGGL(k_h16_finish, dim3((B + 255) / 256), dim3(256), 0, st, cp, sp, B, (uint32_t)chunks,

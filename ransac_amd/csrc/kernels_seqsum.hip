@@ -22,7 +22,6 @@
 // Layout of one fit's scratch (seqsum_scratch_bytes(nch)): psum[kSegMax][nch] doubles (the
 // fp64 segment sums), then R[kSegMax][nch][kCand] floats (every candidate's segment end).
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include "usac_kernels.h"
 #include "usac_seqsum.hpp"
@@ -71,17 +70,19 @@ __global__ __launch_bounds__(256) void k_seq_psum(const typename Op<F64>::V *__r
     if (threadIdx.x < NCH) reinterpret_cast<double *>(scratch + w * sstride)[j * NCH + threadIdx.x] = red[threadIdx.x][0];
 }
 
-// every candidate's segment end: workgroup (segment j, fit b), lane = candidate, NCH
-// independent chains per lane.  The segment streams through LDS in chunks (every thread
-// loads a strided share of the next chunk into registers while the chains run over the
-// current one; one barrier per chunk), so each step reads its element by a broadcast
-// ds_read instead of waiting on a load.
-template <int NCH, bool F64>
+// every candidate's segment end of a one-chain sum: workgroup (segment j, fit b), lane =
+// candidate.  The segment streams through LDS in chunks (every thread loads a strided share of
+// the next chunk into registers while the chain runs over the current one; one barrier per
+// chunk), so each step reads its element by a broadcast ds_read instead of waiting on a load.
+// (The body is the former multi-chain kernel's with the chain count fixed at 1: a version
+// written over a scalar compiles to the same kernel with its adds' operands commuted.)
+template <bool F64>
 __global__ __launch_bounds__(kCand) void k_seq_seg(const typename Op<F64>::V *__restrict__ vals, size_t vstride,
                                                    const uint32_t *__restrict__ ns, uint32_t n1,
                                                    const uint32_t *__restrict__ slots, char *scratch, size_t sstride) {
     typedef typename Op<F64>::V V;
-    constexpr uint32_t kChunk = (NCH == 1 ? 8 : 4) * kCand;  // elements per LDS chunk (2048 / 1024 at 256 candidates)
+    constexpr int NCH = 1;                   // chains per lane
+    constexpr uint32_t kChunk = 8 * kCand;   // elements per LDS chunk (2048 at 256 candidates)
     constexpr uint32_t kPer = kChunk * NCH / kCand;      // values per thread per chunk
     __shared__ V sv[2][kChunk * NCH];
     __shared__ double sp[kSegMax * NCH];
@@ -277,76 +278,32 @@ __global__ __launch_bounds__(256) void k_seq_link(const typename Op<F64>::V *__r
 
 size_t seqsum_scratch_bytes(int nch) { return scratch_bytes(nch); }
 
-// multi-chain segment kernel: chains split over waves (default) or interleaved per lane
-// (USAC_SEQ_SPLIT=0, the round-3 kernel; kept for A/B)
-static bool seg_split() {
-    static const bool on = [] {
-        const char *e = getenv("USAC_SEQ_SPLIT");
-        return !e || atoi(e) != 0;
-    }();
-    return on;
-}
-// candidates per lane of the split kernel: 2 for the fp32 chains (the four coordinate means:
-// 15.9 -> 12.8 us per fit batch), 1 for the fp64-addend ones (21.3 / 21.2 us with 1 / 2, 27.8
-// with 4); USAC_SEQ_CPL = 1, 2 or 4 sets both, for A/B
-static int seg_cpl(bool f64) {
-    static const int cpl = [] {
-        const char *e = getenv("USAC_SEQ_CPL");
-        const int v = e ? atoi(e) : 0;
-        return v == 1 || v == 2 || v == 4 ? v : 0;
-    }();
-    return cpl ? cpl : f64 ? 1 : 2;
-}
-// one-chain sums (Σerr) through the split kernel with this many candidates per lane
-// (USAC_SEQ1_CPL = 1, 2 or 4; unset or 0: k_seq_seg).  One per lane runs as fast as k_seq_seg
-// (6.7 / 6.8 us) with half its LDS; the cfg5 / cfg3-exact lines split both ways over two boxes
-// (DESIGN §7 round 6), so k_seq_seg stays the default
-static int seg1_cpl() {
-    static const int cpl = [] {
-        const char *e = getenv("USAC_SEQ1_CPL");
-        const int v = e ? atoi(e) : 0;
-        return v == 1 || v == 2 || v == 4 ? v : 0;
-    }();
-    return cpl;
-}
-
+// The segment kernel of each chain shape, as measured per fit batch:
+//  - one fp32 chain (Σerr): k_seq_seg.  The split kernel with one candidate per lane runs as fast
+//    (6.7 / 6.8 us) with half its LDS, 2 / 4 per lane slower (8.8 / 10.4 us); the cfg5 / cfg3-exact
+//    lines split both ways over two boxes
+//  - four fp32 chains (the coordinate means): the chains split over the waves (15.9 against 17.3 us
+//    interleaved per lane), two candidates per lane (15.9 -> 12.8 us)
+//  - two fp64-addend chains (the distances): split (21.3 against 21.8 us), one candidate per lane
+//    (21.3 / 21.2 us with 1 / 2, 27.8 with 4)
 hipError_t launch_seqsum(hipStream_t st, int nch, bool f64, const void *vals, size_t vstride, const uint32_t *ns,
                          uint32_t n1, uint32_t W, const uint32_t *slots, void *scratch, size_t sstride,
                          bool have_psum, float *out) {
     if (W == 0) return hipSuccess;
     const dim3 gs(kSegMax, W), gl(nch, W);
     char *scr = static_cast<char *>(scratch);
-#define SEQ(N, D)                                                                                                   \
+#define SEQ(N, D, SEG, THREADS)                                                                                     \
     do {                                                                                                            \
         typedef typename Op<D>::V V_;                                                                               \
         const V_ *v_ = static_cast<const V_ *>(vals);                                                               \
         if (!have_psum)                                                                                             \
             hipLaunchKernelGGL((k_seq_psum<N, D>), gs, dim3(256), 0, st, v_, vstride, ns, n1, slots, scr, sstride); \
-        if (N == 1 && seg1_cpl() == 2)                                                                              \
-            hipLaunchKernelGGL((k_seq_seg_split<N, D, 2>), gs, dim3(kCand * N / 2), 0, st, v_, vstride, ns, n1, slots, \
-                               scr, sstride);                                                                       \
-        else if (N == 1 && seg1_cpl() == 4)                                                                         \
-            hipLaunchKernelGGL((k_seq_seg_split<N, D, 4>), gs, dim3(kCand * N / 4), 0, st, v_, vstride, ns, n1, slots, \
-                               scr, sstride);                                                                       \
-        else if (N == 1 && seg1_cpl() == 1)                                                                         \
-            hipLaunchKernelGGL((k_seq_seg_split<N, D, 1>), gs, dim3(kCand * N), 0, st, v_, vstride, ns, n1, slots,     \
-                               scr, sstride);                                                                       \
-        else if (N > 1 && seg_split() && seg_cpl(D) == 4)                                                                 \
-            hipLaunchKernelGGL((k_seq_seg_split<N, D, 4>), gs, dim3(kCand * N / 4), 0, st, v_, vstride, ns, n1, slots, \
-                               scr, sstride);                                                                       \
-        else if (N > 1 && seg_split() && seg_cpl(D) == 2)                                                            \
-            hipLaunchKernelGGL((k_seq_seg_split<N, D, 2>), gs, dim3(kCand * N / 2), 0, st, v_, vstride, ns, n1, slots, \
-                               scr, sstride);                                                                       \
-        else if (N > 1 && seg_split())                                                                              \
-            hipLaunchKernelGGL((k_seq_seg_split<N, D, 1>), gs, dim3(kCand * N), 0, st, v_, vstride, ns, n1, slots,     \
-                               scr, sstride);                                                                       \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_seq_seg<N, D>), gs, dim3(kCand), 0, st, v_, vstride, ns, n1, slots, scr, sstride);  \
+        hipLaunchKernelGGL(SEG, gs, dim3(THREADS), 0, st, v_, vstride, ns, n1, slots, scr, sstride);                \
         hipLaunchKernelGGL((k_seq_link<N, D>), gl, dim3(256), 0, st, v_, vstride, ns, n1, slots, scr, sstride, out); \
     } while (0)
-    if (nch == 1 && !f64) SEQ(1, false);
-    else if (nch == 4 && !f64) SEQ(4, false);
-    else if (nch == 2 && f64) SEQ(2, true);
+    if (nch == 1 && !f64) SEQ(1, false, (k_seq_seg<false>), kCand);
+    else if (nch == 4 && !f64) SEQ(4, false, (k_seq_seg_split<4, false, 2>), kCand * 4 / 2);
+    else if (nch == 2 && f64) SEQ(2, true, (k_seq_seg_split<2, true, 1>), kCand * 2);
     else return hipErrorInvalidValue;
 #undef SEQ
     return hipGetLastError();

@@ -156,39 +156,6 @@ struct StreamPool {
         std::lock_guard<std::mutex> g(mu);
         streams.emplace(dev, s);
     }
-    // streams restricted to a few CUs spread over the device (hipExtStreamCreateWithCUMask), pooled
-    // apart; cus <= 0 or >= the device's CU count: none (nullptr)
-    std::multimap<int, hipStream_t> masked;
-    hipError_t masked_stream(int cus, hipStream_t *s) {
-        *s = nullptr;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        {
-            std::lock_guard<std::mutex> g(mu);
-            auto it = masked.find(dev);
-            if (it != masked.end()) {
-                *s = it->second;
-                masked.erase(it);
-                return hipSuccess;
-            }
-        }
-        int ncu = 0;
-        hipError_t e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess) return e;
-        if (cus <= 0 || cus >= ncu) return hipSuccess;
-        std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-        for (int k = 0; k < cus; k++) {
-            const int cu = (int)((long long)k * ncu / cus);
-            mask[cu / 32] |= 1u << (cu % 32);
-        }
-        return hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data());
-    }
-    void give_back_masked(hipStream_t s) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> g(mu);
-        masked.emplace(dev, s);
-    }
     void give_back(hipEvent_t ev) {
         int dev = 0;
         (void)hipGetDevice(&dev);
@@ -225,33 +192,6 @@ struct PinnedPool {
     void give_back(void *p, size_t c) {
         std::lock_guard<std::mutex> g(mu);
         free.emplace(c, p);
-    }
-};
-
-// Captured LO stage graphs, process-wide: a context lives for one Ransac::run (as the reference
-// builds its Ransac per run), but its device blocks come from DevPool and recur from run to run,
-// so a graph keyed by the stage shape and every buffer address it touches is reused across runs
-// (a graph's kernels only reach what its key's shape implies; the key also holds every buffer's
-// reserved byte count, so a block handed out again at the same address with a smaller backing
-// never matches an old graph).  The cache only grows, up to kMax entries; past that, stages of new
-// shapes are launched kernel by kernel.  The execs are destroyed at process exit by an atexit
-// handler registered after the HIP runtime's own (so it runs before the runtime's teardown).
-struct GraphCache {
-    static constexpr size_t kMax = 256;
-    std::mutex mu;
-    std::map<std::vector<uintptr_t>, hipGraphExec_t> g;
-    static GraphCache &get() {
-        static GraphCache *c = [] {
-            GraphCache *gc = new GraphCache();
-            std::atexit([] {
-                GraphCache &cc = GraphCache::get();
-                std::lock_guard<std::mutex> lk(cc.mu);
-                for (auto &kv : cc.g) (void)hipGraphExecDestroy(kv.second);
-                cc.g.clear();
-            });
-            return gc;
-        }();
-        return *c;
     }
 };
 
@@ -388,19 +328,10 @@ struct usac_ctx {
     DevBuf lo_io;           // one LO stage's inputs (two blocks, alternating) and outputs
     // the LO stages' Σerr passes run on their own stream beside the next stage's fit
     hipStream_t lo_stream = nullptr;
-    // LO iterative stages replayed as HIP graphs (USAC_LO_GRAPH=1; one capture per stage shape and
-    // buffer set, process-wide).  Off by default: measured slower than the direct launches (same-
-    // process A/B over 60 cfg5 runs, tools/ab_lo_graph.py: 134 vs 127 us per LO stage)
-    bool lo_graph_on = false;
-    DevBuf lo_best;                  // the round's best count on the device (the graphs read it)
-    int32_t *lo_best_pin = nullptr;  // its pinned host word
-    size_t lo_best_pin_bytes = 0;
     void *rec_pin = nullptr;  // usac_fetch_best's pinned staging (a pageable D2H copy is staged by the runtime)
     size_t rec_pin_bytes = 0;
     // the loop's next batch drawn and run ahead of the current batch's replay (usac_ransac_run)
     hipStream_t spec_stream = nullptr;
-    hipStream_t thin_stream = nullptr;  // CU-masked: the essential solver's root-order kernels
-    hipEvent_t thin_ev[2] = {nullptr, nullptr};
     hipEvent_t spec_ev = nullptr;
     // per block parity: the stage's outputs in the host block (main), its Σ (side); round end
     hipEvent_t lo_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -659,18 +590,9 @@ hipError_t enqueue_solve(usac_ctx *c, const int32_t *samples_dev, uint32_t B, ui
     if (is_e(c)) {
         hipError_t e = c->e5_ws.reserve(usac::e5_workspace_bytes(B));
         if (e != hipSuccess) return e;
-        // USAC_E5_THIN_CUS = k > 0: the root-order kernels on a stream masked to k CUs (default 0: the
-        // context stream -- measured faster once every context has its own hardware queue)
-        static const int thin_cus = getenv("USAC_E5_THIN_CUS") ? atoi(getenv("USAC_E5_THIN_CUS")) : 0;
-        if (thin_cus > 0 && !c->thin_stream) {
-            if ((e = StreamPool::get().masked_stream(thin_cus, &c->thin_stream)) != hipSuccess) return e;
-            for (auto &ev : c->thin_ev)
-                if (!ev && (e = StreamPool::get().event(&ev)) != hipSuccess) return e;
-        }
         return usac::launch_solve_e5(c->stream, c->pts.as<float4>(), c->n, samples_dev, samples_out, B, ds,
                                      first_hyp, c->models.as<float>(), c->counts.as<int32_t>(),
-                                     c->list.as<uint32_t>(), c->list_n.as<uint32_t>(), c->e5_ws.p, c->thin_stream,
-                                     c->thin_ev[0], c->thin_ev[1]);
+                                     c->list.as<uint32_t>(), c->list_n.as<uint32_t>(), c->e5_ws.p);
     }
     if (is_f(c))
         return usac::launch_solve_f7(c->stream, c->pts.as<float4>(), c->n, samples_dev, samples_out, B, ds,
@@ -702,8 +624,7 @@ hipError_t enqueue_solve(usac_ctx *c, const int32_t *samples_dev, uint32_t B, ui
 // point chunks of the matrix-core scorer for a batch of B: ~16 waves per SIMD over the launch
 // (20 hypotheses per wave; USAC_H16_CHUNKS overrides), at most one 32-point block per chunk and 256
 uint32_t h16_chunks(const usac_ctx *c, uint32_t B) {
-    static const int na = getenv("USAC_H16_NA") && atoi(getenv("USAC_H16_NA")) == 4 ? 4 : 2;
-    const uint32_t waves = (B + 10 * na - 1) / (10 * na), nblk = (c->n + 31) / 32;
+    const uint32_t waves = (B + 19) / 20, nblk = (c->n + 31) / 32;
     static const int env_ch = getenv("USAC_H16_CHUNKS") ? atoi(getenv("USAC_H16_CHUNKS")) : 0;
     const uint32_t ch = env_ch > 0 ? (uint32_t)env_ch : (16384u + waves - 1) / waves;
     // at most 2^23 points per chunk: a hypothesis' fixed-point Σ partial of one chunk stays below 2^63
@@ -790,8 +711,7 @@ bool e16_scores(const usac_ctx *c, int chunks, float thr) {
 // 2^23 points (its fixed-point Σ bound)
 uint32_t e16_chunks(const usac_ctx *c, uint32_t kmax) {
     const uint32_t waves = (kmax + 63) / 64, nblk = (c->n + 31) / 32;
-    static const int env_ch = getenv("USAC_E16_CHUNKS") ? atoi(getenv("USAC_E16_CHUNKS")) : 0;
-    const uint32_t ch = env_ch > 0 ? (uint32_t)env_ch : (12288u + waves - 1) / waves;
+    const uint32_t ch = (12288u + waves - 1) / waves;
     const uint32_t min_ch = (nblk + (1u << 18) - 1) >> 18;
     return std::max(std::max(1u, min_ch), std::min(ch, std::min(nblk, 256u)));
 }
@@ -1041,7 +961,6 @@ struct LoRansac {
     uint32_t inner_count = 0, iterative_count = 0;
     uint32_t rounds = 0, stages = 0, fits = 0;  // speculation rounds, device stages, fits (statistics)
     double t_enqueue = 0.0, t_poll = 0.0;          // host ms spent enqueuing stages / waiting for them (USAC_PROFILE)
-    uint32_t graphs_built = 0;                      // iterative-stage graphs captured (USAC_PROFILE)
     int rc = USAC_OK;
     // entry best of the current call
     int best_cnt = 0;
@@ -1109,16 +1028,8 @@ struct LoRansac {
         HIP_TRY(c, c->lo_ws.reserve(sizeof(float) * 18 * W));
         scr_bytes = usac::inliers_scratch_bytes(n, wmax);
         HIP_TRY(c, c->lo_scr.reserve(2 * scr_bytes));
-        if (graphs()) {
-            HIP_TRY(c, c->lo_best.reserve(sizeof(int32_t)));
-            if (!c->lo_best_pin &&
-                !(c->lo_best_pin = static_cast<int32_t *>(PinnedPool::get().take(sizeof(int32_t), &c->lo_best_pin_bytes))))
-                return fail(c, USAC_ERR_HIP, "hipHostMalloc (LO best word) failed");
-        }
         return USAC_OK;
     }
-    // iterative stages as HIP graphs: the unlimited variant's pipelined stages, non-line fits
-    bool graphs() const { return c->lo_graph_on && !limited && c->estimator != USAC_LINE2D; }
 
     // the host and device blocks of parity b: inputs then outputs (layout of both)
     void set_block(int b) {
@@ -1368,16 +1279,10 @@ struct LoRansac {
                 nmax = std::max(nmax, hns[w]);
             }
             HIP_TRY(c, hipMemcpyAsync(dns, hns, in_bytes, hipMemcpyHostToDevice, st));
-            if (graphs()) {  // the round's best count, read by the captured iterative stages
-                *c->lo_best_pin = best_cnt;
-                HIP_TRY(c, hipMemcpyAsync(c->lo_best.p, c->lo_best_pin, sizeof(int32_t), hipMemcpyHostToDevice, st));
-            }
         }
         // iterative fits: counts and thresholds derived on the device from the previous stage
         // (by the fit's first kernel)
-        const bool graph = k > 0 && graphs();
-        const usac::LoPrep prep{pns,      pok, pcnt, pthr, dns, dthr, (int32_t)m, best_cnt, k > 1 ? 1 : 0, step,
-                                graph ? c->lo_best.as<int32_t>() : nullptr};
+        const usac::LoPrep prep{pns, pok, pcnt, pthr, dns, dthr, (int32_t)m, best_cnt, k > 1 ? 1 : 0, step};
         usac::NmBatch nb{};
         nb.base = k == 0 ? c->lo_max.as<int32_t>() : c->lo_lists.as<int32_t>();
         nb.base_stride = k == 0 ? 0 : n;
@@ -1396,71 +1301,9 @@ struct LoRansac {
         nb.model_out = dmod;
         nb.ok = dok;
         nb.seq = c->nm_seq.p;
-        auto launch = [&]() -> hipError_t {
-            hipError_t e = usac::launch_nonminimal_batch(st, c->estimator, c->pts.p, nb);
-            if (e == hipSuccess)
-                e = usac::launch_inliers_batch(st, c->estimator, c->pts.p, n, dmod, W, 0.f, dthr, nullptr,
-                                               c->lo_lists.as<int32_t>(), n, dcnt, nullptr, scr(b), dok);
-            return e;
-        };
-        if (graph) {  // the stage's ten kernels as one graph launch (captured once per shape)
-            float stepv = step;
-            uint32_t stepbits;
-            memcpy(&stepbits, &stepv, 4);
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            const std::vector<uintptr_t> key = {
-                (uintptr_t)dev, (uintptr_t)b, (uintptr_t)(k > 1), W, n, (uintptr_t)c->estimator, stepbits, m,
-                (uintptr_t)c->pts.p,
-                (uintptr_t)c->lo_io.p, (uintptr_t)c->lo_q.p, (uintptr_t)c->lo_part.p, (uintptr_t)c->lo_ws.p,
-                (uintptr_t)c->nm_seq.p, (uintptr_t)c->lo_lists.p, (uintptr_t)c->lo_max.p, (uintptr_t)c->lo_scr.p,
-                (uintptr_t)c->lo_best.p, scr_bytes, in_bytes, out_bytes,
-                // the blocks' reserved sizes (DevPool may hand an address out again with less behind it)
-                c->pts.bytes, c->lo_io.bytes, c->lo_q.bytes, c->lo_part.bytes, c->lo_ws.bytes, c->nm_seq.bytes,
-                c->lo_lists.bytes, c->lo_max.bytes, c->lo_scr.bytes, c->lo_best.bytes};
-            GraphCache &gc = GraphCache::get();
-            hipGraphExec_t ex = nullptr;
-            {
-                std::lock_guard<std::mutex> lk(gc.mu);
-                auto it = gc.g.find(key);
-                if (it != gc.g.end()) ex = it->second;
-            }
-            bool full = false;
-            if (!ex) {
-                std::lock_guard<std::mutex> lk(gc.mu);
-                full = gc.g.size() >= GraphCache::kMax;
-            }
-            if (!ex && full) {
-                HIP_TRY(c, launch());
-            } else if (!ex) {
-                HIP_TRY(c, hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-                const hipError_t le = launch();
-                hipGraph_t g = nullptr;
-                const hipError_t ce = hipStreamEndCapture(st, &g);
-                if (le != hipSuccess || ce != hipSuccess) {
-                    if (g) (void)hipGraphDestroy(g);
-                    return fail(c, USAC_ERR_HIP, std::string("LO stage capture: ") +
-                                                     hipGetErrorString(le != hipSuccess ? le : ce));
-                }
-                const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(g);
-                if (ie != hipSuccess) return fail(c, USAC_ERR_HIP, std::string("LO stage graph: ") + hipGetErrorString(ie));
-                {
-                    std::lock_guard<std::mutex> lk(gc.mu);
-                    auto ins = gc.g.emplace(key, ex);
-                    if (!ins.second) {  // another thread captured the same stage meanwhile
-                        (void)hipGraphExecDestroy(ex);
-                        ex = ins.first->second;
-                    }
-                }
-                graphs_built++;
-                HIP_TRY(c, hipGraphLaunch(ex, st));
-            } else {
-                HIP_TRY(c, hipGraphLaunch(ex, st));
-            }
-        } else {
-            HIP_TRY(c, launch());
-        }
+        HIP_TRY(c, usac::launch_nonminimal_batch(st, c->estimator, c->pts.p, nb));
+        HIP_TRY(c, usac::launch_inliers_batch(st, c->estimator, c->pts.p, n, dmod, W, 0.f, dthr, nullptr,
+                                              c->lo_lists.as<int32_t>(), n, dcnt, nullptr, scr(b), dok));
         // the side stream: Σ, then every output of the stage into the host block
         HIP_TRY(c, hipEventRecord(c->lo_ev[b], st));
         HIP_TRY(c, hipStreamWaitEvent(c->lo_stream, c->lo_ev[b], 0));
@@ -1910,7 +1753,6 @@ int usac_create(usac_ctx **out, int device, int estimator, const float *pts, uin
     // two-view scoring: a batch yields few models (about 0.4-1.3 per sample) and the few with
     // many inliers are much slower to score, so their point ranges are cut finer
     if (estimator == USAC_FUNDAMENTAL || estimator == USAC_ESSENTIAL) c->chunks = 96;
-    if (const char *g = getenv("USAC_LO_GRAPH")) c->lo_graph_on = atoi(g) != 0;
     int rc = USAC_OK;
     do {
         hipError_t e = hipSetDevice(device);
@@ -1972,7 +1814,6 @@ void usac_destroy(usac_ctx *c) {
     if (c->xstream) (void)hipStreamSynchronize(c->xstream);
     if (c->lo_stream) (void)hipStreamSynchronize(c->lo_stream);
     if (c->spec_stream) (void)hipStreamSynchronize(c->spec_stream);
-    if (c->thin_stream) (void)hipStreamSynchronize(c->thin_stream);
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->pol_pin) PinnedPool::get().give_back(c->pol_pin, c->pol_pin_bytes);
     if (c->x_pin) PinnedPool::get().give_back(c->x_pin, c->x_pin_bytes);
@@ -1986,13 +1827,9 @@ void usac_destroy(usac_ctx *c) {
     for (auto &ev : c->lo_ev)
         if (ev) StreamPool::get().give_back(ev);
     if (c->lo_stream) StreamPool::get().give_back(c->lo_stream);
-    if (c->lo_best_pin) PinnedPool::get().give_back(c->lo_best_pin, c->lo_best_pin_bytes);
     if (c->rec_pin) PinnedPool::get().give_back(c->rec_pin, c->rec_pin_bytes);
     if (c->spec_ev) StreamPool::get().give_back(c->spec_ev);
     if (c->spec_stream) StreamPool::get().give_back(c->spec_stream);
-    if (c->thin_stream) StreamPool::get().give_back_masked(c->thin_stream);
-    for (auto &ev : c->thin_ev)
-        if (ev) StreamPool::get().give_back(ev);
     if (c->grid_pin) PinnedPool::get().give_back(c->grid_pin, c->grid_pin_bytes);
     for (DevBuf *b : {&c->pts, &c->rec, &c->perm, &c->samples, &c->models, &c->counts, &c->sums, &c->best, &c->hostmodels,
                       &c->argmax_part, &c->list, &c->list_n, &c->h4_fb, &c->h4_fb_n, &c->pool_idx, &c->pool_pts, &c->masks, &c->sprt_pts,
@@ -2002,7 +1839,7 @@ void usac_destroy(usac_ctx *c) {
                       &c->rec_send, &c->rec_all, &c->tv_part, &c->hf_part, &c->prosac_tab, &c->lo_max, &c->lo_lists, &c->lo_pos,
                       &c->lo_ns, &c->lo_thrs, &c->lo_slots, &c->lo_models, &c->lo_ok, &c->lo_cnts, &c->lo_sums,
                       &c->lo_q, &c->lo_part, &c->lo_ws, &c->lo_scr, &c->knn_idx, &c->knn_d2, &c->gc_err, &c->grid_csr,
-                      &c->grid_elig, &c->grid_ws, &c->x_send, &c->lo_best,
+                      &c->grid_elig, &c->grid_ws, &c->x_send,
                       &c->x_recv, &c->xring})
         b->release();
     for (auto &ev : c->ev)
@@ -3360,9 +3197,7 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
         }
     };
     int k_first = 0;  // the first pass for the multi-launch path
-    // USAC_FINISH_SCORE=0: each pass's finish, scoring and acceptance as three launches
-    const char *fse = getenv("USAC_FINISH_SCORE");
-    const bool finish_score = !(fse && atoi(fse) == 0) && c->estimator != USAC_LINE2D && c->n <= usac::kPolPtsMax;
+    const bool finish_score = c->estimator != USAC_LINE2D && c->n <= usac::kPolPtsMax;
     if (fused) {
         HIP_TRY(c, hipMemcpyAsync(c->pol_pin, dres, sizeof(float) * usac::kPolWords, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, stream_wait(c->stream));
@@ -3425,11 +3260,11 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
     if (getenv("USAC_PROFILE"))
         fprintf(stderr,
                 "usac_ransac_run ms: setup %.3f draw %.3f device %.3f sums %.3f replay %.3f lo %.3f polish %.3f "
-                "(lo rounds %u stages %u enqueue %.3f poll %.3f graphs %u; setup: buffers %.3f neighbours %.3f "
+                "(lo rounds %u stages %u enqueue %.3f poll %.3f; setup: buffers %.3f neighbours %.3f "
                 "lo/gc %.3f; sprt walks %.3f, draws %.3f; iters %u batches %u)\n",
                 tsplit[T_SETUP], tsplit[T_DRAW], tsplit[T_DEVICE], tsplit[T_SUMS], tsplit[T_REPLAY], tsplit[T_LO],
                 tsplit[T_POLISH], lo ? lo->rounds : gc ? gc->labelings : 0u, lo ? lo->stages : gc ? gc->stages : 0u,
-                lo ? lo->t_enqueue : 0.0, lo ? lo->t_poll : 0.0, lo ? lo->graphs_built : 0u, tsub[0],
+                lo ? lo->t_enqueue : 0.0, lo ? lo->t_poll : 0.0, tsub[0],
                 tsub[1] - tsub[0], tsub[2] - tsub[1], t_verify, t_drawonly, iters, (uint32_t)out->batches);
     // ransac.cpp:214 getInliers(best_model): `cur` already is that list (see above)
     cnt = cur_cnt;
