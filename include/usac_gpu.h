@@ -76,7 +76,11 @@
  *                                  ABI 24: usac_multi_create_essential_pixels, an essential multi context from
  *                                  pixel coordinates and per-pair intrinsics (converted on the device), with
  *                                  usac_multi_set_pixel_thresholds, usac_multi_pixel_models and
- *                                  usac_multi_get_points
+ *                                  usac_multi_get_points;
+ *                                  ABI 25: usac_multi_create_device, a multi context from padded device memory
+ *                                  (rows with a validity mask or counts, or keypoints with a match index),
+ *                                  packed on the device, with usac_multi_get_offsets, usac_multi_get_source
+ *                                  and usac_multi_padded_mask, a host mask scattered into P x n_max device bytes
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -91,7 +95,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 24
+#define USAC_ABI_VERSION 25
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -581,7 +585,55 @@ int usac_multi_pixel_models(usac_multi *mc, const float *E, float *F);
  * reads, by a device-to-host copy -- on a context from usac_multi_create_essential_pixels the calibrated rows
  * the conversion wrote.  Any multi context.  USAC_ERR_ARG for a NULL argument. */
 int usac_multi_get_points(usac_multi *mc, float *out);
+/* Device input (ABI 25): P problems as padded device memory of `device`, n_max columns each, in one of two forms.
+ * Form a, rows: rows is P x n_max x 4 fp32, contiguous and 16-byte aligned, with valid (P x n_max bytes, nonzero
+ * keeps the row) or counts (P int32, the first counts[p] rows of problem p are kept) or neither (all rows are
+ * kept).  Form b, matches: kpts0 is P x n_max x 2 fp32, kpts1 P x n1 x 2 fp32, match P x n_max int32; column j is
+ * kept when match[p, j] >= 0 and its row is (kpts0[p, j], kpts1[p, match[p, j]]); two columns may share a target.
+ * The pointers of the form not used are NULL (and n1 is 0 in form a). */
+typedef struct usac_multi_device_input {
+    uint32_t P, n_max;
+    const float *rows; const uint8_t *valid; const int32_t *counts;      /* form a */
+    const float *kpts0, *kpts1; uint32_t n1; const int32_t *match;       /* form b */
+    const float *K1, *K2;  /* HOST, P x 9 each, essential only: pixels -> calibrated as ABI 24; NULL: rows are used as they are */
+    void *stream;          /* the hipStream_t that orders the producer's writes; NULL: the null stream */
+} usac_multi_device_input;
+/* A multi context of USAC_HOMOGRAPHY, USAC_FUNDAMENTAL or USAC_ESSENTIAL problems (line: USAC_ERR_UNSUPPORTED)
+ * from device input.  The device packs every problem's kept rows, in ascending column order, into the concatenated
+ * N_total x 4 rows and offsets[P + 1] all multi contexts hold, and keeps per packed row the column it came from.
+ * Rows are moved, not computed with: every bit arrives as it was.  With K1 (K2 == NULL: K1 for both views) the
+ * packed rows are then converted as by usac_multi_create_essential_pixels, and usac_multi_set_pixel_thresholds /
+ * usac_multi_pixel_models work.  The result is an ordinary multi context: every usac_multi_* call works on it,
+ * and per problem it equals, bit for bit, a context created from the host over the kept rows.
+ * Every kernel that reads the caller's memory is enqueued on in->stream, behind the work that produced it, and
+ * the call waits for that stream: when it returns the context holds its own copy.
+ * USAC_ERR_ARG before any device call: a NULL out or in, P == 0 or > 65535, n_max == 0, P * n_max >= 2^32, both
+ * forms or neither, valid together with counts, form b with n1 == 0 or a NULL among its three pointers, K1 or K2
+ * with an estimator other than USAC_ESSENTIAL, K2 without K1, a K usac_multi_create_essential_pixels refuses.
+ * USAC_ERR_ARG before any launch: a pointer that is not device memory of `device` (hipPointerGetAttributes), is
+ * misaligned, or whose allocation is too short.  USAC_ERR_ARG after the counting pass, with nothing kept: a
+ * problem with fewer kept rows than the sample size, counts[p] < 0 or > n_max, a match index >= n1 (it is never
+ * dereferenced).  *out is NULL after any failure; the reason, naming the argument or the first offending
+ * problem, goes to stderr and is what usac_multi_last_error(NULL) returns to the calling thread until its next
+ * usac_multi_create_device. */
+int usac_multi_create_device(usac_multi **out, int device, int estimator, const usac_multi_device_input *in);
+/* The context's offsets (ABI 25): offsets[P + 1], host.  Any multi context; what a caller of
+ * usac_multi_create_device sizes its arrays by (N_total = offsets[P]).  USAC_ERR_ARG for a NULL argument. */
+int usac_multi_get_offsets(const usac_multi *mc, uint32_t *offsets);
+/* The column of every packed row (ABI 25): src[N_total], host; row offsets[p] + i of the context is column
+ * src[offsets[p] + i] of problem p's padded input, ascending within a problem.  USAC_ERR_UNSUPPORTED on a context
+ * not created by usac_multi_create_device, USAC_ERR_ARG for a NULL argument. */
+int usac_multi_get_source(usac_multi *mc, uint32_t *src);
+/* A mask over the packed rows back in the padded layout (ABI 25).  mask: HOST, N_total bytes, what
+ * usac_multi_inliers, usac_multi_polish or a polished run wrote; d_out: P x n_max bytes of device memory of the
+ * context's device (checked as usac_multi_create_device's pointers).  out[p, src[i]] = mask[i], every other cell
+ * 0.  The upload, the memset and the scatter are enqueued on `stream` (a hipStream_t; NULL: the null stream) and
+ * the call waits for it.  Stateless: the host mask is the one source that is right for a problem the polish
+ * deferred to its host path.  USAC_ERR_UNSUPPORTED on a context not created by usac_multi_create_device,
+ * USAC_ERR_ARG for a NULL mc, mask or d_out. */
+int usac_multi_padded_mask(usac_multi *mc, const uint8_t *mask, uint8_t *d_out, void *stream);
 void usac_multi_destroy(usac_multi *mc);
+/* The message of the context's last failed call; mc == NULL: "null context", or see usac_multi_create_device. */
 const char *usac_multi_last_error(const usac_multi *mc);
 uint32_t usac_multi_num_problems(const usac_multi *mc);
 /* Per-problem thresholds (ABI 22).  thr: P finite values > 0, problem p's inlier threshold in the units of

@@ -573,12 +573,30 @@ public:
         if (rc != USAC_OK) throw Error(rc, "usac_multi_create_essential_pixels failed");
         return mc;
     }
+    // P problems from padded device memory (usac_multi_create_device, ABI 25): in holds device pointers of
+    // `device` in one of its two forms (rows with valid / counts, or kpts0 / kpts1 / match), K1 / K2 on the host
+    // (Essential only) and the stream (a hipStream_t as void *) that orders the producer's writes.  The device
+    // packs the kept rows in ascending column order; every member then works as on a context over them
+    // (offsets() and points() return what it holds).  Throws with the library's message, which names the
+    // argument or the first problem it refuses.
+    static MultiContext fromDevice(int estimator, const usac_multi_device_input &in, int device = 0) {
+        MultiContext mc((std::vector<uint32_t>()));
+        mc.est_ = (ESTIMATOR)estimator;
+        const int rc = usac_multi_create_device(&mc.mc_, device, estimator, &in);
+        if (rc != USAC_OK) throw Error(rc, usac_multi_last_error(nullptr));
+        mc.offsets_.resize((size_t)in.P + 1);
+        mc.n_max_ = in.n_max;
+        mc.check(usac_multi_get_offsets(mc.mc_, mc.offsets_.data()), "MultiContext::fromDevice");
+        return mc;
+    }
     ~MultiContext() {
         if (mc_) usac_multi_destroy(mc_);
     }
     MultiContext(const MultiContext &) = delete;
     MultiContext &operator=(const MultiContext &) = delete;
-    MultiContext(MultiContext &&o) : mc_(o.mc_), est_(o.est_), offsets_(std::move(o.offsets_)) { o.mc_ = nullptr; }
+    MultiContext(MultiContext &&o) : mc_(o.mc_), est_(o.est_), offsets_(std::move(o.offsets_)), n_max_(o.n_max_) {
+        o.mc_ = nullptr;
+    }
 
     usac_multi *get() const { return mc_; }
     unsigned int problems() const { return usac_multi_num_problems(mc_); }
@@ -628,6 +646,25 @@ public:
         std::vector<float> out(4 * (size_t)(offsets_.empty() ? 0u : offsets_.back()));
         check(usac_multi_get_points(mc_, out.data()), "MultiContext::points");
         return out;
+    }
+
+    // the context's offsets[P + 1], and the padded width of a context from fromDevice (else 0)
+    const std::vector<uint32_t> &offsets() const { return offsets_; }
+    unsigned int paddedWidth() const { return n_max_; }
+    // usac_multi_get_source (ABI 25, a context from fromDevice): per packed row the column of the padded input
+    // it came from, ascending within a problem.  Throws USAC_ERR_UNSUPPORTED on any other context.
+    std::vector<uint32_t> source() const {
+        std::vector<uint32_t> out(offsets_.empty() ? 0u : offsets_.back());
+        check(usac_multi_get_source(mc_, out.empty() ? nullptr : out.data()), "MultiContext::source");
+        return out;
+    }
+    // usac_multi_padded_mask (ABI 25, a context from fromDevice): mask, N_total bytes as inliers / polish / a
+    // polished run wrote them, scattered into d_out, P x paddedWidth() bytes of device memory, zero wherever no
+    // packed row came from; enqueued on stream (a hipStream_t as void *) and waited for
+    void paddedMask(const std::vector<uint8_t> &mask, uint8_t *d_out, void *stream = nullptr) const {
+        if (mask.size() != (offsets_.empty() ? 0u : offsets_.back()))
+            throw Error(USAC_ERR_ARG, "paddedMask: N_total mask bytes");
+        check(usac_multi_padded_mask(mc_, mask.data(), d_out, stream), "MultiContext::paddedMask");
     }
 
     // one round of R hypotheses (a multiple of 64 in 64..8192) for the listed problems (empty: all,
@@ -905,6 +942,7 @@ private:
     usac_multi *mc_ = nullptr;
     ESTIMATOR est_;
     std::vector<uint32_t> offsets_;
+    uint32_t n_max_ = 0;
 };
 
 }  // namespace usac_gpu

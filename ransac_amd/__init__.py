@@ -177,6 +177,15 @@ class _MultiSprtOutput(ctypes.Structure):
                 "accepted": int(self.accepted), "rejected": int(self.rejected), "points_tested": int(self.points_tested)}
 
 
+class _MultiDeviceInput(ctypes.Structure):
+    """usac_multi_device_input (ABI 25): the device pointers as integers, K1 / K2 on the host"""
+    _fields_ = [("P", ctypes.c_uint32), ("n_max", ctypes.c_uint32), ("rows", ctypes.c_void_p),
+                ("valid", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("kpts0", ctypes.c_void_p),
+                ("kpts1", ctypes.c_void_p), ("n1", ctypes.c_uint32), ("match", ctypes.c_void_p),
+                ("K1", ctypes.POINTER(ctypes.c_float)), ("K2", ctypes.POINTER(ctypes.c_float)),
+                ("stream", ctypes.c_void_p)]
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -206,6 +215,7 @@ ABI_SYMBOLS = [
     "usac_multi_lo_essential", "usac_multi_run_lo_essential",
     "usac_multi_create_essential_pixels", "usac_multi_set_pixel_thresholds", "usac_multi_pixel_models",
     "usac_multi_get_points",
+    "usac_multi_create_device", "usac_multi_get_offsets", "usac_multi_get_source", "usac_multi_padded_mask",
 ]
 
 
@@ -309,6 +319,10 @@ def lib():
         "usac_multi_set_pixel_thresholds": (ctypes.c_int, [_vp, f32p, ctypes.c_uint32]),
         "usac_multi_pixel_models": (ctypes.c_int, [_vp, f32p, f32p]),
         "usac_multi_get_points": (ctypes.c_int, [_vp, f32p]),
+        "usac_multi_create_device": (ctypes.c_int, [_P(_vp), ctypes.c_int, ctypes.c_int, _P(_MultiDeviceInput)]),
+        "usac_multi_get_offsets": (ctypes.c_int, [_vp, u32p]),
+        "usac_multi_get_source": (ctypes.c_int, [_vp, u32p]),
+        "usac_multi_padded_mask": (ctypes.c_int, [_vp, u8p, _vp, _vp]),
         "usac_multi_destroy": (None, [_vp]),
         "usac_multi_last_error": (ctypes.c_char_p, [_vp]),
         "usac_multi_num_problems": (ctypes.c_uint32, [_vp]),
@@ -368,6 +382,56 @@ def lib():
 
 def _ptr(a, t):
     return a.ctypes.data_as(_P(t)) if a is not None else None
+
+
+class _DevArray:
+    """A device array as the library takes it: the pointer, the shape, a dtype code (f4, i4, i8, u1, b1) and
+    the object that owns the memory.  A torch tensor (data_ptr()) or anything with __cuda_array_interface__;
+    TypeError for host memory, ValueError for a layout that is not C-contiguous."""
+
+    _TORCH = {"torch.float32": "f4", "torch.int32": "i4", "torch.int64": "i8", "torch.uint8": "u1", "torch.bool": "b1"}
+
+    def __init__(self, obj, name):
+        self.obj, self.name = obj, name
+        self.torch = False
+        self.device = None
+        if isinstance(obj, np.ndarray) or isinstance(obj, (list, tuple)):
+            raise TypeError("%s: a device array is needed, got host memory (%s)" % (name, type(obj).__name__))
+        if hasattr(obj, "data_ptr") and hasattr(obj, "is_contiguous"):
+            if not getattr(obj, "is_cuda", False):
+                raise TypeError("%s: a device tensor is needed, got one on %s" % (name, getattr(obj, "device", "the host")))
+            self.torch = True
+            self.device = obj.device.index
+            self.shape = tuple(int(d) for d in obj.shape)
+            self.kind = self._TORCH.get(str(obj.dtype), str(obj.dtype))
+            if not obj.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+            self.ptr = int(obj.data_ptr())
+        elif hasattr(obj, "__cuda_array_interface__"):
+            d = obj.__cuda_array_interface__
+            self.shape = tuple(int(v) for v in d["shape"])
+            self.kind = d["typestr"][1:]
+            if d.get("strides") is not None:
+                want, step = [], int(self.kind[1:])
+                for n in reversed(self.shape):
+                    want.insert(0, step)
+                    step *= n
+                if tuple(d["strides"]) != tuple(want):
+                    raise ValueError("%s must be contiguous" % name)
+            self.ptr = int(d["data"][0])
+        else:
+            raise TypeError("%s: a device array is needed (data_ptr() or __cuda_array_interface__), got %s"
+                            % (name, type(obj).__name__))
+
+    def need(self, shape, kinds):
+        """ValueError unless the shape (None: any extent) and one of the dtype codes fit"""
+        ok = len(self.shape) == len(shape) and all(w is None or w == h for w, h in zip(shape, self.shape))
+        if not ok:
+            raise ValueError("%s must be %s, got %s" % (self.name, " x ".join("*" if w is None else str(w) for w in shape),
+                                                        " x ".join(map(str, self.shape))))
+        if self.kind not in kinds:
+            raise ValueError("%s must be of dtype %s, got %s" % (self.name, " or ".join(kinds), self.kind))
+        return self
 
 
 def bk_label(unary, ei, ej, e00, e01, e10, e11):
@@ -793,7 +857,19 @@ class MultiContext:
 
     MultiContext.essential_pixels(point_sets, K1, K2) is the same context from pixel coordinates and
     per-pair intrinsics: the device converts the rows, `points` holds the calibrated rows it wrote, and
-    set_pixel_thresholds / pixel_models speak pixels on the way in and out."""
+    set_pixel_thresholds / pixel_models speak pixels on the way in and out.
+
+    MultiContext.from_padded(estimator, rows, valid / counts) and MultiContext.from_matches(estimator, kpts0,
+    kpts1, matches) take padded device tensors (usac_multi_create_device): the device packs the kept rows, nothing
+    comes down at creation (`points` is None, resident_points() fetches the rows), `n_max` is the padded width and
+    `source_index` the column of every packed row.  Such a context has inlier_lists = False: a polished run keeps
+    its host mask as `last_mask` and returns no index lists, and padded_mask() hands the mask back as a
+    (P, n_max) device tensor."""
+
+    inlier_lists = True  # False: polish(with_inliers=True) and the polished runs return no index lists
+    last_mask = None     # the N_total host mask bytes of the last call that computed inliers
+    n_max = None         # the padded width of a context from device input
+    device = 0
 
     def __init__(self, estimator, point_sets, device=0):
         self._create(ESTIMATOR(estimator), point_sets, device, False)
@@ -869,6 +945,132 @@ class MultiContext:
         self.spk = 3 if self.estimator == ESTIMATOR.Fundamental else 1
         if k1 is not None:  # the rows the device wrote replace the pixels
             self.points = self.resident_points()
+
+    @classmethod
+    def from_padded(cls, estimator, rows, valid=None, counts=None, K1=None, K2=None, stream=None, device=None):
+        """usac_multi_create_device, form a: rows is a (P, n_max, 4) float32 device tensor, with valid (P, n_max)
+        bool or uint8, nonzero keeps the row, or counts (P,) int32, the first counts[p] rows are kept, or neither
+        (all rows are kept).  estimator: Homography, Fundamental or Essential; K1 / K2 (Essential only, host, as
+        essential_pixels') convert the kept pixel rows on the device.  stream: the stream handle that orders the
+        writes of the tensors (default: torch's current stream for torch tensors, else 0); the call waits for it.
+        TypeError for host arrays, ValueError for a wrong shape, dtype or a non-contiguous layout, UsacError(-1)
+        naming the problem that keeps fewer rows than the sample size or has a count outside 0..n_max."""
+        r = _DevArray(rows, "rows").need((None, None, 4), ("f4",))
+        P, n_max = r.shape[0], r.shape[1]
+        v = None if valid is None else _DevArray(valid, "valid").need((P, n_max), ("b1", "u1"))
+        c = None if counts is None else _DevArray(counts, "counts").need((P,), ("i4",))
+        if v is not None and c is not None:
+            raise ValueError("valid and counts are alternatives")
+        inp = _MultiDeviceInput(P=P, n_max=n_max, rows=r.ptr, valid=v and v.ptr, counts=c and c.ptr)
+        return cls._from_device(estimator, inp, [r, v, c], K1, K2, stream, device)
+
+    @classmethod
+    def from_matches(cls, estimator, kpts0, kpts1, matches, K1=None, K2=None, stream=None, device=None):
+        """usac_multi_create_device, form b: kpts0 (P, n0, 2) and kpts1 (P, n1, 2) float32 device tensors and
+        matches (P, n0) int32 (int64 is cast on the device): keypoint j of view 1 is kept when matches[p, j] >= 0,
+        its row is (kpts0[p, j], kpts1[p, matches[p, j]]); n_max is n0.  Otherwise as from_padded; UsacError(-1)
+        also for a match index >= n1, which is never dereferenced."""
+        a = _DevArray(kpts0, "kpts0").need((None, None, 2), ("f4",))
+        P, n0 = a.shape[0], a.shape[1]
+        b = _DevArray(kpts1, "kpts1").need((P, None, 2), ("f4",))
+        m = _DevArray(matches, "matches").need((P, n0), ("i4", "i8"))
+        if m.kind == "i8":
+            if not m.torch:
+                raise ValueError("matches must be of dtype i4, got i8")
+            import torch
+
+            # the cast runs on torch's current stream; a caller's other stream waits for it through the host
+            m = _DevArray(matches.to(torch.int32), "matches")
+            cur = torch.cuda.current_stream(matches.device)
+            if stream is not None and int(stream) != cur.cuda_stream:
+                cur.synchronize()
+        inp = _MultiDeviceInput(P=P, n_max=n0, kpts0=a.ptr, kpts1=b.ptr, n1=b.shape[1], match=m.ptr)
+        return cls._from_device(estimator, inp, [a, b, m], K1, K2, stream, device)
+
+    @classmethod
+    def _from_device(cls, estimator, inp, arrays, K1, K2, stream, device):
+        arrays = [a for a in arrays if a is not None]
+        self = cls.__new__(cls)
+        self._h = None
+        self.estimator = ESTIMATOR(estimator)
+        if device is None:
+            device = next((a.device for a in arrays if a.device is not None), 0)
+        if stream is None:
+            stream = 0
+            if arrays[0].torch:
+                import torch
+
+                stream = torch.cuda.current_stream(arrays[0].obj.device).cuda_stream
+        P = int(inp.P)
+        if K2 is not None and K1 is None:
+            raise ValueError("K2 without K1")
+        k1 = None if K1 is None else cls._intrinsics(K1, P, "K1")
+        k2 = None if K2 is None else cls._intrinsics(K2, P, "K2")
+        inp.K1 = _ptr(k1, ctypes.c_float)
+        inp.K2 = _ptr(k2, ctypes.c_float)
+        inp.stream = int(stream) or None
+        L = lib()
+        h = _vp()
+        rc = L.usac_multi_create_device(ctypes.byref(h), int(device), int(self.estimator), ctypes.byref(inp))
+        if rc != 0:
+            msg = L.usac_multi_last_error(None)
+            raise UsacError(rc, msg.decode() if msg else "usac_multi_create_device failed")
+        self._h = h
+        self.device = int(device)
+        self.P, self.n_max = P, int(inp.n_max)
+        self.offsets = np.zeros(P + 1, dtype=np.uint32)
+        self._check(L.usac_multi_get_offsets(self._h, _ptr(self.offsets, ctypes.c_uint32)), "multi_get_offsets")
+        self.sizes = np.diff(self.offsets.astype(np.int64))
+        self.points = None  # nothing comes down at creation: resident_points()
+        self.dlt_mode = DLT.THIN
+        self.m = {ESTIMATOR.Fundamental: 7, ESTIMATOR.Essential: 5}.get(self.estimator, 4)
+        self.spk = 3 if self.estimator == ESTIMATOR.Fundamental else 1
+        self.inlier_lists = False
+        self._source = None
+        return self
+
+    @property
+    def source_index(self):
+        """usac_multi_get_source (a context from device input): per packed row the column of the padded input it
+        came from, a uint32 array of N_total values, ascending within a problem; fetched at first use."""
+        if getattr(self, "_source", None) is None:
+            src = np.zeros(int(self.offsets[-1]), dtype=np.uint32)
+            self._check(lib().usac_multi_get_source(self._h, _ptr(src, ctypes.c_uint32)), "multi_get_source")
+            self._source = src
+        return self._source
+
+    def padded_mask(self, mask=None, out=None, stream=None):
+        """usac_multi_padded_mask (a context from device input): the N_total mask bytes of a call that computed
+        inliers (None: last_mask, the last such call's) scattered into a (P, n_max) device array, zero wherever no
+        packed row came from.  out: a (P, n_max) uint8 device tensor to write (it is returned); None: a fresh
+        torch tensor, returned as a torch.bool view.  stream as from_padded's; the call waits for it."""
+        if self.n_max is None:
+            raise UsacError(-3, "padded_mask: the context was not created from device input")
+        mask = self.last_mask if mask is None else mask
+        if mask is None:
+            raise ValueError("padded_mask: no mask given and no call has computed one yet")
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).ravel()
+        if mask.size != int(self.offsets[-1]):
+            raise ValueError("padded_mask: N_total = %d mask bytes, got %d" % (int(self.offsets[-1]), mask.size))
+        fresh = out is None
+        if fresh:
+            import torch
+
+            out = torch.empty((self.P, self.n_max), dtype=torch.uint8, device="cuda:%d" % self.device)
+        o = _DevArray(out, "out").need((self.P, self.n_max), ("u1", "b1"))
+        if stream is None:
+            stream = 0
+            if o.torch:
+                import torch
+
+                stream = torch.cuda.current_stream(out.device).cuda_stream
+        self._check(lib().usac_multi_padded_mask(self._h, _ptr(mask, ctypes.c_uint8), o.ptr, int(stream) or None),
+                    "multi_padded_mask")
+        if fresh:
+            import torch
+
+            return out.view(torch.bool)
+        return out
 
     def resident_points(self):
         """usac_multi_get_points: the N_total x 4 rows resident on the device (a copy)."""
@@ -994,6 +1196,8 @@ class MultiContext:
                                             _ptr(mask, ctypes.c_uint8)), "multi_polish")
         res = _MultiPolishOutput.as_dicts(out)
         if with_inliers:
+            self.last_mask = mask
+        if with_inliers and self.inlier_lists:
             for r, idx in zip(res, self._split_mask(mask)):
                 r["inlier_idx"] = idx
         return res
@@ -1035,8 +1239,11 @@ class MultiContext:
                 r.update(termination_length=int(q.termination_length), largest_sample_size=int(q.largest_sample_size),
                          clock=int(q.clock), scans=int(q.scans))
         if polish:
-            for r, po, idx in zip(res, _MultiPolishOutput.as_dicts(pol), self._split_mask(mask)):
+            self.last_mask = mask
+            for r, po in zip(res, _MultiPolishOutput.as_dicts(pol)):
                 r["polished"] = po
+        if polish and self.inlier_lists:
+            for r, idx in zip(res, self._split_mask(mask)):
                 r["inliers"] = idx
         return res
 
@@ -1261,6 +1468,7 @@ class MultiContext:
         cnt = np.zeros(self.P, dtype=np.int32)
         self._check(lib().usac_multi_inliers(self._h, _ptr(m, ctypes.c_float), ctypes.c_float(thr),
                                              _ptr(mask, ctypes.c_uint8), _ptr(cnt, ctypes.c_int32)), "multi_inliers")
+        self.last_mask = mask
         return self._split_mask(mask)
 
 

@@ -3895,6 +3895,10 @@ struct usac_multi {
     // Pixel coordinates (ABI 24): a context created from pixels keeps its problems' intrinsics (P x 9 each; k2 =
     // k1 where the caller gave one K) for the pixel thresholds and the pixel-space models; else both are empty
     std::vector<float> k1, k2;
+    // Device input (ABI 25): a context from usac_multi_create_device keeps the padded width of its input and, per
+    // packed row, the column it came from (N_total values on the device); else n_max is 0 and src is empty
+    uint32_t n_max = 0;
+    DevBuf src;
     std::string err;
 };
 
@@ -4608,24 +4612,34 @@ int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *see
                                sizeof(usac_multi_output) / sizeof(float), prm->threshold, outs.pol, outs.mask);
 }
 
-// usac_multi_create / usac_multi_create_essential after their own checks (out is not NULL): the
-// arguments, before any device call, then the context
-int multi_create(usac_multi **out, int device, int estimator, const float *pts, const uint32_t *offsets, uint32_t P) {
-    const uint32_t m = estimator == USAC_FUNDAMENTAL ? 7 : estimator == USAC_ESSENTIAL ? 5 : 4;
-    if (P == 0 || P > usac::kMultiMaxActive || !pts || !offsets || offsets[0] != 0) return USAC_ERR_ARG;
-    for (uint32_t p = 0; p < P; p++)
-        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] < m) return USAC_ERR_ARG;
+uint32_t multi_sample_size(int estimator) {
+    return estimator == USAC_FUNDAMENTAL ? 7 : estimator == USAC_ESSENTIAL ? 5 : 4;
+}
+
+// a context of P problems without points yet; no device call
+usac_multi *multi_new(int device, int estimator, uint32_t P) {
     usac_multi *mc = new usac_multi();
     mc->device = device;
     mc->estimator = estimator;
     mc->P = P;
-    mc->m = m;
+    mc->m = multi_sample_size(estimator);
     mc->spk = estimator == USAC_FUNDAMENTAL ? 3 : 1;
-    mc->n_total = offsets[P];
     if (const char *es = getenv("USAC_MULTI_E5_SLICE")) {  // tests: a lower cap on the 5-point solve's slices
         const long v = atol(es);
         if (v > 0 && v < (long)usac::kMultiE5Slice) mc->e5_slice = (uint32_t)v;
     }
+    return mc;
+}
+
+// usac_multi_create / usac_multi_create_essential after their own checks (out is not NULL): the
+// arguments, before any device call, then the context
+int multi_create(usac_multi **out, int device, int estimator, const float *pts, const uint32_t *offsets, uint32_t P) {
+    const uint32_t m = multi_sample_size(estimator);
+    if (P == 0 || P > usac::kMultiMaxActive || !pts || !offsets || offsets[0] != 0) return USAC_ERR_ARG;
+    for (uint32_t p = 0; p < P; p++)
+        if (offsets[p + 1] < offsets[p] || offsets[p + 1] - offsets[p] < m) return USAC_ERR_ARG;
+    usac_multi *mc = multi_new(device, estimator, P);
+    mc->n_total = offsets[P];
     mc->offsets.assign(offsets, offsets + P + 1);
     hipError_t e = hipSetDevice(device);
     const char *what = "hipSetDevice";
@@ -4659,6 +4673,45 @@ int multi_run_uniform(usac_multi *mc, const usac_params *prm, const uint64_t *se
     if (prm->sprt || prm->lo != USAC_LO_NONE || prm->sampler != USAC_SAMPLER_UNIFORM)
         return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_run: uniform sampler only, no SPRT, no LO (LO: usac_multi_run_lo)");
     return multi_run_driver(mc, prm, seeds, out, MultiRunOutputs{nullptr, nullptr, nullptr, pol, mask});
+}
+
+// ---- device input (ABI 25)
+// what usac_multi_create_device refused its input for, kept for usac_multi_last_error(NULL): the context that
+// would hold the message does not survive the refusal
+thread_local std::string g_create_device_err;
+
+int create_device_fail(int code, const std::string &msg) {
+    g_create_device_err = "usac_multi_create_device: " + msg;
+    fprintf(stderr, "%s\n", g_create_device_err.c_str());
+    return code;
+}
+
+// the caller's pointer `name` must be device memory of `device` with room for `bytes` and aligned to `align`;
+// else the reason.  No launch has read it yet.  The extent is checked where the runtime knows the allocation.
+std::string device_pointer_problem(const void *ptr, const char *name, int device, size_t bytes, size_t align) {
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    const hipError_t e = hipPointerGetAttributes(&at, ptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // the sticky error of a pointer the runtime does not know
+        return std::string(name) + " is not device memory (" + hipGetErrorString(e) + ")";
+    }
+    if (at.type != hipMemoryTypeDevice) return std::string(name) + " is not device memory";
+    if (at.device != device)
+        return std::string(name) + " is memory of device " + std::to_string(at.device) + ", not " + std::to_string(device);
+    if (reinterpret_cast<uintptr_t>(ptr) % align)
+        return std::string(name) + " is not aligned to " + std::to_string(align) + " bytes";
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(ptr)) == hipSuccess) {
+        const size_t used = (size_t)(static_cast<const char *>(ptr) - static_cast<const char *>(base));
+        if (used > size || size - used < bytes)
+            return std::string(name) + " has room for " + std::to_string(size - used) + " bytes, " + std::to_string(bytes) +
+                   " are needed";
+    } else {
+        (void)hipGetLastError();
+    }
+    return "";
 }
 
 }  // namespace
@@ -4742,6 +4795,186 @@ int usac_multi_create_essential_pixels(usac_multi **out, int device, const float
     return USAC_OK;
 }
 
+int usac_multi_create_device(usac_multi **out, int device, int estimator, const usac_multi_device_input *in) {
+    if (!out) return USAC_ERR_ARG;
+    *out = nullptr;
+    g_create_device_err.clear();
+    if (!in) return create_device_fail(USAC_ERR_ARG, "NULL input");
+    if (estimator != USAC_HOMOGRAPHY && estimator != USAC_FUNDAMENTAL && estimator != USAC_ESSENTIAL)
+        return create_device_fail(USAC_ERR_UNSUPPORTED, "homography, fundamental or essential estimator only");
+    const uint32_t P = in->P, n_max = in->n_max;
+    if (P == 0 || P > usac::kMultiMaxActive) return create_device_fail(USAC_ERR_ARG, "P must be in 1..65535");
+    if (!usac::pack_extent_ok(P, n_max)) return create_device_fail(USAC_ERR_ARG, "n_max must be > 0 and P * n_max < 2^32");
+    const bool form_a = in->rows || in->valid || in->counts, form_b = in->kpts0 || in->kpts1 || in->match || in->n1;
+    if (form_a == form_b)
+        return create_device_fail(USAC_ERR_ARG, "give rows (form a) or kpts0 / kpts1 / match (form b), one of them");
+    if (form_a && !in->rows) return create_device_fail(USAC_ERR_ARG, "valid or counts without rows");
+    if (in->valid && in->counts) return create_device_fail(USAC_ERR_ARG, "valid and counts are alternatives");
+    if (form_b && (!in->kpts0 || !in->kpts1 || !in->match || in->n1 == 0))
+        return create_device_fail(USAC_ERR_ARG, "form b needs kpts0, kpts1, match and n1 > 0");
+    if (form_b && (uint64_t)P * in->n1 >= (1ull << 32)) return create_device_fail(USAC_ERR_ARG, "P * n1 must be < 2^32");
+    if ((in->K1 || in->K2) && estimator != USAC_ESSENTIAL)
+        return create_device_fail(USAC_ERR_ARG, "K1 / K2 are for the essential estimator");
+    if (in->K2 && !in->K1) return create_device_fail(USAC_ERR_ARG, "K2 without K1");
+    const float *K1 = in->K1, *K2 = in->K2 ? in->K2 : in->K1;
+    if (K1)
+        for (uint32_t p = 0; p < P; p++)
+            if (!usac::pixel_k_ok(K1 + 9 * (size_t)p) || !usac::pixel_k_ok(K2 + 9 * (size_t)p))
+                return create_device_fail(USAC_ERR_ARG, "problem " + std::to_string(p) + ": K must be finite and upper "
+                                                        "triangular with fx, fy > 0 and a last row of 0 0 1");
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return create_device_fail(USAC_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    // a host pointer must never reach a kernel: every pointer the kernels will read, before any launch
+    const size_t cells = (size_t)P * n_max;
+    struct { const void *p; const char *name; size_t bytes, align; } ptrs[] = {
+        {in->rows, "rows", cells * 16, 16},           {in->valid, "valid", cells, 1},
+        {in->counts, "counts", (size_t)P * 4, 4},     {in->kpts0, "kpts0", cells * 8, 8},
+        {in->kpts1, "kpts1", (size_t)P * in->n1 * 8, 8}, {in->match, "match", cells * 4, 4}};
+    for (const auto &q : ptrs) {
+        if (!q.p) continue;
+        const std::string why = device_pointer_problem(q.p, q.name, device, q.bytes, q.align);
+        if (!why.empty()) return create_device_fail(USAC_ERR_ARG, why);
+    }
+    usac::MultiPack pk{};
+    pk.P = P;
+    pk.n_max = n_max;
+    pk.n1 = in->n1;
+    pk.rows = reinterpret_cast<const uint4 *>(in->rows);
+    pk.valid = in->valid;
+    pk.counts = in->counts;
+    pk.kpts0 = reinterpret_cast<const uint2 *>(in->kpts0);
+    pk.kpts1 = reinterpret_cast<const uint2 *>(in->kpts1);
+    pk.match = in->match;
+    // every kernel that reads the caller's memory runs on the caller's stream, behind the producer's work
+    hipStream_t cs = static_cast<hipStream_t>(in->stream);
+    usac_multi *mc = multi_new(device, estimator, P);
+    mc->n_max = n_max;
+    DevBuf dcount, dcal;  // the counting pass's 2 P values; the intrinsics
+    PinBlock pin;
+    std::string msg;
+    const char *what = "hipStreamCreate";
+    auto done = [&](int code) {
+        dcount.release();
+        dcal.release();
+        if (pin.p) PinnedPool::get().give_back(pin.p, pin.bytes);
+        if (code == USAC_OK) {
+            *out = mc;
+            return code;
+        }
+        usac_multi_destroy(mc);
+        return create_device_fail(code, msg);
+    };
+    e = StreamPool::get().stream(&mc->stream);
+    if (e == hipSuccess) {
+        e = dcount.reserve(sizeof(uint32_t) * 2 * (size_t)P);
+        what = "hipMalloc counts";
+    }
+    if (e == hipSuccess && !(pin.p = PinnedPool::get().take(sizeof(uint32_t) * 2 * (size_t)P, &pin.bytes))) {
+        msg = "hipHostMalloc failed";
+        return done(USAC_ERR_HIP);
+    }
+    uint32_t *sizes = static_cast<uint32_t *>(pin.p);
+    if (e == hipSuccess) {
+        e = usac::launch_multi_pack_count(cs, pk, dcount.as<uint32_t>(), dcount.as<uint32_t>() + P);
+        what = "k_multi_pack_count";
+    }
+    if (e == hipSuccess) {
+        e = hipMemcpyAsync(sizes, dcount.p, sizeof(uint32_t) * 2 * (size_t)P, hipMemcpyDeviceToHost, cs);
+        what = "hipMemcpy counts";
+    }
+    if (e == hipSuccess) e = stream_wait(cs);
+    if (e == hipSuccess) {
+        mc->offsets.assign((size_t)P + 1, 0u);
+        uint32_t bad = 0;
+        const usac::PackStatus st = usac::pack_offsets(sizes, sizes + P, P, mc->m, n_max, mc->offsets.data(), &bad);
+        if (st != usac::kPackOk) {
+            msg = usac::pack_message(st, bad, sizes[bad], mc->m);
+            return done(USAC_ERR_ARG);
+        }
+        mc->n_total = mc->offsets[P];
+        e = mc->pts.reserve(sizeof(float) * 4 * (size_t)mc->n_total);
+        what = "hipMalloc points";
+    }
+    if (e == hipSuccess) e = mc->src.reserve(sizeof(uint32_t) * (size_t)mc->n_total);
+    if (e == hipSuccess) e = mc->offs.reserve(sizeof(uint32_t) * ((size_t)P + 1));
+    if (e == hipSuccess) e = mc->running.reserve(sizeof(usac_record) * (size_t)P);
+    if (e == hipSuccess) {
+        e = hipMemcpyAsync(mc->offs.p, mc->offsets.data(), sizeof(uint32_t) * ((size_t)P + 1), hipMemcpyHostToDevice, cs);
+        what = "hipMemcpy offsets";
+    }
+    if (e == hipSuccess) {
+        e = usac::launch_multi_pack(cs, pk, mc->offs.as<uint32_t>(), mc->pts.as<float4>(), mc->src.as<uint32_t>());
+        what = "k_multi_pack";
+    }
+    std::vector<float> calib;
+    if (e == hipSuccess && K1) {  // pixels -> calibrated rows, as usac_multi_create_essential_pixels, behind the pack
+        mc->k1.assign(K1, K1 + 9 * (size_t)P);
+        mc->k2.assign(K2, K2 + 9 * (size_t)P);
+        calib.resize(usac::kCalibFloats * (size_t)P);
+        for (uint32_t p = 0; p < P; p++)
+            usac::pixel_pack(K1 + 9 * (size_t)p, K2 + 9 * (size_t)p, calib.data() + usac::kCalibFloats * (size_t)p);
+        e = dcal.reserve(sizeof(float) * calib.size());
+        what = "hipMalloc intrinsics";
+        if (e == hipSuccess) {
+            e = hipMemcpyAsync(dcal.p, calib.data(), sizeof(float) * calib.size(), hipMemcpyHostToDevice, cs);
+            what = "hipMemcpy intrinsics";
+        }
+        if (e == hipSuccess) {
+            e = usac::launch_multi_calibrate(cs, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), P, mc->n_total,
+                                             static_cast<const float *>(dcal.p));
+            what = "k_multi_calibrate";
+        }
+    }
+    // the context holds its own copy from here on: the caller may overwrite or free its tensors
+    if (e == hipSuccess) {
+        e = stream_wait(cs);
+        what = "the caller's stream";
+    }
+    if (e != hipSuccess) {
+        msg = std::string(what) + ": " + hipGetErrorString(e);
+        return done(USAC_ERR_HIP);
+    }
+    return done(USAC_OK);
+}
+
+int usac_multi_get_offsets(const usac_multi *mc, uint32_t *offsets) {
+    if (!mc || !offsets) return USAC_ERR_ARG;
+    std::copy(mc->offsets.begin(), mc->offsets.end(), offsets);
+    return USAC_OK;
+}
+
+int usac_multi_get_source(usac_multi *mc, uint32_t *src) {
+    if (!mc) return USAC_ERR_ARG;
+    if (mc->n_max == 0)
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_get_source: the context was not created from device input "
+                                              "(usac_multi_create_device)");
+    if (!src) return fail(mc, USAC_ERR_ARG, "usac_multi_get_source: NULL argument");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    HIP_TRY(mc, hipMemcpy(src, mc->src.p, sizeof(uint32_t) * (size_t)mc->n_total, hipMemcpyDeviceToHost));
+    return USAC_OK;
+}
+
+int usac_multi_padded_mask(usac_multi *mc, const uint8_t *mask, uint8_t *d_out, void *stream) {
+    if (!mc) return USAC_ERR_ARG;
+    if (mc->n_max == 0)
+        return fail(mc, USAC_ERR_UNSUPPORTED, "usac_multi_padded_mask: the context was not created from device input "
+                                              "(usac_multi_create_device)");
+    if (!mask || !d_out) return fail(mc, USAC_ERR_ARG, "usac_multi_padded_mask: NULL argument");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    const size_t cells = (size_t)mc->P * mc->n_max;
+    const std::string why = device_pointer_problem(d_out, "d_out", mc->device, cells, 1);
+    if (!why.empty()) return fail(mc, USAC_ERR_ARG, "usac_multi_padded_mask: " + why);
+    hipStream_t cs = static_cast<hipStream_t>(stream);
+    // every call of this context has waited for its stream: mc->mask is free to stage the upload
+    HIP_TRY(mc, mc->mask.reserve(mc->n_total));
+    HIP_TRY(mc, hipMemcpyAsync(mc->mask.p, mask, mc->n_total, hipMemcpyHostToDevice, cs));
+    HIP_TRY(mc, hipMemsetAsync(d_out, 0, cells, cs));
+    HIP_TRY(mc, usac::launch_multi_unpack_mask(cs, mc->mask.as<uint8_t>(), mc->src.as<uint32_t>(), mc->offs.as<uint32_t>(),
+                                               mc->P, mc->n_total, mc->n_max, d_out));
+    HIP_TRY(mc, stream_wait(cs));
+    return USAC_OK;
+}
+
 void usac_multi_destroy(usac_multi *mc) {
     if (!mc) return;
     (void)hipSetDevice(mc->device);
@@ -4753,13 +4986,17 @@ void usac_multi_destroy(usac_multi *mc) {
         b->release();
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
                       &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
-                      &mc->pol_out, &mc->lo_state, &mc->e5_ws, &mc->thrs, &mc->lo_steps})
+                      &mc->pol_out, &mc->lo_state, &mc->e5_ws, &mc->thrs, &mc->lo_steps, &mc->src})
         b->release();
     if (mc->stream) StreamPool::get().give_back(mc->stream);
     delete mc;
 }
 
-const char *usac_multi_last_error(const usac_multi *mc) { return mc ? mc->err.c_str() : "null context"; }
+const char *usac_multi_last_error(const usac_multi *mc) {
+    if (mc) return mc->err.c_str();
+    // no context: what this thread's last usac_multi_create_device refused its input for, if it did
+    return g_create_device_err.empty() ? "null context" : g_create_device_err.c_str();
+}
 uint32_t usac_multi_num_problems(const usac_multi *mc) { return mc ? mc->P : 0; }
 
 // ---- per-problem thresholds (ABI 22)

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/usac_gpu.h"
+#include "usac_pack.hpp"
 #include "usac_pixels.hpp"
 
 namespace usac {
@@ -467,6 +468,27 @@ hipError_t launch_multi_lo(hipStream_t st, int estimator, const float4 *pts, con
 // ABI 24): calib holds kCalibFloats floats per problem in pixel_pack's layout (usac_pixels.hpp), 16-byte aligned
 hipError_t launch_multi_calibrate(hipStream_t st, float4 *pts, const uint32_t *offsets, uint32_t P, uint32_t n_total,
                                   const float *calib);
+
+// Device input (kernels_multi_pack.hip, ABI 25): padded per-problem input -> the concatenated rows.  Form a: rows
+// (P x n_max x 4 fp32, 16-byte aligned) with valid (P x n_max bytes, nonzero keeps), or counts (P, the leading
+// columns kept), or neither (all kept).  Form b: match != nullptr, column j kept when match[p, j] >= 0, its row
+// (kpts0[p, j], kpts1[p, match[p, j]]); an index >= n1 is not dereferenced and raises kPackFlagMatch.
+struct MultiPack {
+    uint32_t P, n_max, n1;
+    const uint4 *rows;
+    const uint8_t *valid;
+    const int32_t *counts;
+    const uint2 *kpts0, *kpts1;
+    const int32_t *match;
+};
+// per problem the kept columns and the kPackFlag* it must be refused for (usac_pack.hpp)
+hipError_t launch_multi_pack_count(hipStream_t st, const MultiPack &a, uint32_t *sizes, uint32_t *flags);
+// the kept rows in ascending column order at offsets[p] onwards, and src: the column of every packed row;
+// offsets: the exclusive sum of launch_multi_pack_count's sizes
+hipError_t launch_multi_pack(hipStream_t st, const MultiPack &a, const uint32_t *offsets, float4 *pts, uint32_t *src);
+// out[p, src[i]] = mask[i] over the n_total packed rows; out (P x n_max bytes) is cleared by the caller
+hipError_t launch_multi_unpack_mask(hipStream_t st, const uint8_t *mask, const uint32_t *src, const uint32_t *offsets,
+                                    uint32_t P, uint32_t n_total, uint32_t n_max, uint8_t *out);
 
 // k nearest neighbours of every point (kernels_knn.hip, nearest_neighbors.cpp:69-128):
 // idx / d2 (nullable) n x k, self excluded, ascending distance, ties by index; 1 <= k <= 32

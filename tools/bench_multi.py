@@ -660,6 +660,101 @@ def main_pixels(a, model):
     return 0 if equal and rows_equal and thr_equal else 1
 
 
+def main_device(a, model, est, sets):
+    """--device-input: from padded device tensors to the polished inliers as a (P, n_max) bool tensor on the device,
+    what a caller does today (pipeline A: down to numpy, ragged sets, MultiContext, run, mask built in numpy, up
+    again) against from_padded + run + padded_mask (pipeline B), alternated, host-timed; both end synchronised"""
+    import torch
+
+    P, n = len(sets), a.points
+    n_max = n + n // 4  # a matcher's padded width: a fifth of the columns hold no match
+    rng = np.random.default_rng(17)
+    rows = np.zeros((P, n_max, 4), dtype=np.float32)
+    valid = np.zeros((P, n_max), dtype=bool)
+    for p, pts in enumerate(sets):
+        cols = np.sort(rng.permutation(n_max)[:len(pts)])  # the pair's order survives
+        rows[p, cols] = pts
+        valid[p, cols] = True
+    dev = torch.device("cuda:0")
+    rows_t, valid_t = torch.from_numpy(rows).to(dev), torch.from_numpy(valid).to(dev)
+    torch.cuda.synchronize()
+    essential = est == usac.ESTIMATOR.Essential
+
+    def create_a():
+        r, v = rows_t.cpu().numpy(), valid_t.cpu().numpy()
+        host_sets = [r[p][v[p]] for p in range(P)]
+        return (usac.MultiContext.essential(host_sets) if essential else usac.MultiContext(est, host_sets)), v
+
+    def create_b():
+        return usac.MultiContext.from_padded(est, rows_t, valid=valid_t)
+
+    def pipe_a():
+        mc, v = create_a()
+        res = mc.run(model, polish=True)
+        pad = np.zeros((P, n_max), dtype=bool)
+        for p, r in enumerate(res):
+            pad[p, np.flatnonzero(v[p])[r["inliers"]]] = True
+        out = torch.from_numpy(pad).to(dev)
+        torch.cuda.synchronize()
+        mc.close()
+        return out, res
+
+    def pipe_b():
+        mc = create_b()
+        res = mc.run(model, polish=True)
+        out = mc.padded_mask()
+        mc.close()
+        return out, res
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        r = fn()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    for _ in range(a.warmup):
+        pipe_a()
+        pipe_b()
+    ta, tb, tca, tcb, trun, tmask = [], [], [], [], [], []
+    for _ in range(a.reps):
+        (mask_a, res_a), ms = timed(pipe_a)
+        ta.append(ms)
+        (mask_b, res_b), ms = timed(pipe_b)
+        tb.append(ms)
+        (mc, _), ms = timed(create_a)
+        tca.append(ms)
+        mc.close()
+        mc, ms = timed(create_b)
+        tcb.append(ms)
+        _, ms = timed(lambda: mc.run(model, polish=True))
+        trun.append(ms)
+        _, ms = timed(mc.padded_mask)
+        tmask.append(ms)
+        mc.close()
+    masks_equal = bool(torch.equal(mask_a, mask_b))
+    models_equal = same_bits([r["polished"] for r in res_a], [r["polished"] for r in res_b]) and \
+        same_bits([r["best"] for r in res_a], [r["best"] for r in res_b])
+
+    def summary(ms):
+        return {"min_ms": round(min(ms), 3), "median_ms": round(statistics.median(ms), 3), "max_ms": round(max(ms), 3)}
+
+    line = {"bench": "multi_device", "estimator": a.estimator, "pairs": P, "points": n, "n_max": n_max, "round": a.R,
+            "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio, "dlt": a.dlt, "reps": a.reps,
+            "pipeline_a_host_round_trip": summary(ta), "pipeline_b_device_input": summary(tb),
+            "ratio_a_over_b": round(statistics.median(ta) / statistics.median(tb), 2),
+            "creation_a_numpy_sets_and_constructor": summary(tca), "creation_b_from_padded": summary(tcb),
+            "run_polished_alone_on_b": summary(trun), "padded_mask_alone": summary(tmask),
+            "masks_equal": masks_equal, "polished_models_bit_equal": bool(models_equal),
+            "mean_polished_inliers": round(float(np.mean([r["polished"]["inliers"] for r in res_b])), 2),
+            "mask_cells_set": int(mask_b.sum().item())}
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    return 0 if masks_equal and models_equal else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=512)
@@ -697,7 +792,13 @@ def main():
                     help="--estimator essential: creation from pixel coordinates (MultiContext.essential_pixels + "
                          "set_pixel_thresholds) against the numpy conversion + MultiContext.essential + set_thresholds; "
                          "the two contexts' polished runs must be bit-equal")
+    ap.add_argument("--device-input", action="store_true",
+                    help="padded torch device tensors in, the polished inliers as a (pairs, n_max) bool device tensor "
+                         "out: the host round trip (numpy sets, MultiContext, run, numpy mask, upload) against "
+                         "MultiContext.from_padded + run(polish=True) + padded_mask; masks and models must be equal")
     a = ap.parse_args()
+    if a.device_input and (a.pixels or a.sprt or a.lo or a.per_problem_thr or a.sampler != "uniform" or a.polish):
+        ap.error("--device-input goes with --estimator alone")
     if a.pixels and (a.estimator != "essential" or a.sprt or a.lo or a.per_problem_thr or a.sampler != "uniform"):
         ap.error("--pixels goes with --estimator essential alone")
     if a.reps < 5:
@@ -724,6 +825,8 @@ def main():
     seeds = [model.seed + p for p in range(a.pairs)]
     if a.pixels:
         return main_pixels(a, model)
+    if a.device_input:
+        return main_device(a, model, est, sets)
 
     mc = usac.MultiContext.essential(sets) if essential else usac.MultiContext(est, sets)
     if a.per_problem_thr:
