@@ -15,10 +15,11 @@
 //   max(|ex_m|, |ey_m|) > |zr_m| + F_m   ==>   max(|ex_fma|, |ey_fma|) > trm |Z_fma| + F,
 // the packed stage A of k_score_hf (usac_hscore.hpp stage_a_keep2), which proves the reference's
 // error is not below thr.  zr is the Z row times trm (1 + 2^-10).  The derivation: |f~ - f| <=
-// 2^-11 |f| + 2^-25 (fp16 rounding, subnormal floor), |g~ - g| likewise plus the coefficients' own
-// fp32 rounding (<= 2^-21 of the sum a_k of their terms' magnitudes), the MFMA's fp32 accumulation of 16
-// exact fp16 products <= 2^-19 sum |g~ f~|; |f| <= fmax (dataset constants), so per row
-// D = sum_k |g~_k| (2^-10 fmax_k + 2^-25) + fmax_k (2^-10 |g_k| + 2^-25 + 2^-21 a_k) + 2^-19 |g~_k| (fmax_k
+// rf |f| + 2^-25 with rf = 2^-11 (1 + 2^-12) (double -> float -> fp16, subnormal floor), |g~ - g| <=
+// 2^-11 |g| + 2^-25 (one fp32 -> fp16 rounding) plus the coefficients' own fp32 rounding (<= 2^-21 of the
+// sum a_k of their terms' magnitudes), the MFMA's fp32 accumulation of 16 exact fp16 products <= 2^-19
+// sum |g~ f~|; |f| <= fmax (dataset constants), so per row
+// D = sum_k |g~_k| (rf fmax_k + 2^-25) + fmax_k (2^-11 |g_k| + 2^-25 + 2^-21 a_k) + 2^-19 |g~_k| (fmax_k
 // + 2^-24), and with the FMA chains' own errors (|ex_fma - ex| <= c.z dZ + dX, |Z_fma - Z| <= dZ,
 // stage_a_bounds) F_m = [F + max(D_ex + c.z dZ + dX, D_ey + c.w dZ + dY) + trm' dZ + D_zr](1 + 2^-20),
 // everything in the hypothesis' power-of-two scale 2^-c.  The (1 + 2^-10) on trm dominates the

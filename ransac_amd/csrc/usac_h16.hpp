@@ -1,8 +1,10 @@
 #pragma once
-// usac_h16.hpp -- the matrix-core scorer's per-hypothesis fp16 rows and prefilter slack (device),
+// usac_h16.hpp -- the matrix-core scorer's per-hypothesis fp16 rows and prefilter slack,
 // shared by k_h16_rows (kernels_h16.hip) and the homography solvers' epilogue (kernels.hip:
 // usac_hypothesize* batches write the rows as they solve, one launch and one pass over the
-// models fewer per batch).
+// models fewer per batch).  Host-callable too (plain fp32 arithmetic, libm's ilogbf / ldexpf, the
+// compiler's fp32 -> fp16 round-to-nearest-even): tests/cpp_h16_slack/slack_check.cpp runs this very
+// function against long double.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -13,12 +15,32 @@ namespace usac {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
+// The fp16 roundings the slack pays for, relative to the value rounded (DESIGN.md §6 derives them):
+// a row coefficient is rounded once, fp32 -> fp16 to nearest: half an ulp of 11 significant bits = 2^-11;
+// a feature is rounded twice, double -> float -> half (k_h16_points): 2^-11 of the float, plus the float's
+// own 2^-24 and the three fp64 operations in front of it, together below 2^-11 (1 + 2^-12).
+// (Overridable for tests/cpp_h16_slack only, which shows how loose 2^-10 was; the library never sets them.)
+#ifndef USAC_H16_ROW_ROUND
+#define USAC_H16_ROW_ROUND 0x1p-11f
+#endif
+#ifndef USAC_H16_FEAT_ROUND
+#define USAC_H16_FEAT_ROUND 0x1.001p-11f
+#endif
+
 // rows[(3 h + r) * 2 + half]: row r (0 ex, 1 ey, 2 zr) of hypothesis h, coefficients 8 half .. 8 half + 7.
 // fp32 throughout (the dataset's centres are fp32 numbers, its scales powers of two): a coefficient's
 // own rounding is <= 2^-21 of the sum a_k of its terms' magnitudes, the bound's sums are rounded up by
 // (1 + 2^-18) -- both far inside the fp16 terms they sit beside.
-__device__ __forceinline__ void h16_rows_of(const float (&Hm)[9], const H16Consts *__restrict__ kc, float thr, uint32_t h,
-                                            half8 *__restrict__ rows, float *__restrict__ fm) {
+// bounds (tests only; the kernels pass none and the stores fold away): the rows' scale 2^e and the tile
+// bounds D of the three rows, |tile value - exact row value 2^e| <= D[r]; D = +inf where F_m is.
+struct H16RowBounds {
+    int e;
+    float D[3];
+};
+
+__host__ __device__ __forceinline__ void h16_rows_of(const float (&Hm)[9], const H16Consts *__restrict__ kc, float thr,
+                                                     uint32_t h, half8 *__restrict__ rows, float *__restrict__ fm,
+                                                     H16RowBounds *bounds = nullptr) {
     const float4 ext = kc->ext;
     HModel M;
 #pragma unroll
@@ -93,8 +115,8 @@ __device__ __forceinline__ void h16_rows_of(const float (&Hm)[9], const H16Const
                 out[r][c >> 3][c & 7] = gt;
                 if (c < 9) {
                     const float agt = fabsf((float)gt), fk = (float)kc->fmax[c];
-                    d += agt * (0x1p-10f * fk + 0x1p-25f) +
-                         fk * (0x1p-10f * fabsf(gh) + 0x1p-25f + 0x1p-21f * ldexpf(a[r][c], e)) +
+                    d += agt * (USAC_H16_FEAT_ROUND * fk + 0x1p-25f) +
+                         fk * (USAC_H16_ROW_ROUND * fabsf(gh) + 0x1p-25f + 0x1p-21f * ldexpf(a[r][c], e)) +
                          0x1p-19f * agt * (fk + 0x1p-24f);
                 }
             }
@@ -105,6 +127,15 @@ __device__ __forceinline__ void h16_rows_of(const float (&Hm)[9], const H16Const
         const float Fm = (M.F * sc + fmaxf(D[0] + ex_fma * sc, D[1] + ey_fma * sc) + trmi * M.dZ * sc + D[2]) *
                          1.00000381469726562f;
         fmv = isfinite(Fm) ? Fm : INFINITY;
+        if (bounds) {
+            bounds->e = e;
+#pragma unroll
+            for (int r = 0; r < 3; r++) bounds->D[r] = isfinite(Fm) ? D[r] : INFINITY;
+        }
+    }
+    if (bounds && !fin) {
+        bounds->e = 0;
+        bounds->D[0] = bounds->D[1] = bounds->D[2] = INFINITY;
     }
 #pragma unroll
     for (int r = 0; r < 3; r++)

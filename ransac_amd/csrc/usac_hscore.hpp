@@ -29,7 +29,7 @@ struct HModel {
 // replaced by its dataset maximum trm (band_max from the box: Mp <= c.x + c.y + c.z + c.w)
 // and tr (|Z| + dZ) + E by |Z| trm + F with F = (trm dZ + E)(1 + 2^-20) -- never a smaller
 // radius, so never a wrong rejection, and one v_fma_f32 (|Z| as an abs modifier) per point.
-__device__ __forceinline__ void stage_a_bounds(HModel &M, float4 c, float T) {
+__host__ __device__ __forceinline__ void stage_a_bounds(HModel &M, float4 c, float T) {
     const float kx = fabsf(M.h[0]) * c.x + fabsf(M.h[1]) * c.y + fabsf(M.h[2]);
     const float ky = fabsf(M.h[3]) * c.x + fabsf(M.h[4]) * c.y + fabsf(M.h[5]);
     const float kz = fabsf(M.h[6]) * c.x + fabsf(M.h[7]) * c.y + fabsf(M.h[8]);

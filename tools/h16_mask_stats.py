@@ -3,7 +3,12 @@ CPU: how many (hypothesis, point) pairs the fp16 tile keeps, and how they fall i
 ballot masks -- the figures that size the kept-pair append and the drains.
 
 numpy only, no GPU.  Points: synthetic.homography_points (cfg2: 10 000 points, 30 % inliers).
-Hypotheses: 4-point DLT models of random minimal samples (fp64 null vector, rounded to fp32).
+Hypotheses: 4-point DLT models of random minimal samples (fp64 null vector, rounded to fp32), or with
+--models a batch as the library solved it (B x 9 float32: Context.estimate_models of
+Context.draw_samples) -- the two differ: the fp64 models pass through their sample points, the library's
+fp32 thin-DLT models of ill-conditioned samples do not, and keep about 2.4x fewer pairs.
+The statistics are printed for three slacks: the 2^-10 fp16 roundings the bound charged before, the
+round-to-nearest constants of h16_rows_of (USAC_H16_ROW_ROUND, USAC_H16_FEAT_ROUND), and F_m = 0.
 Rows and slack: a float32 mirror of usac_h16.hpp h16_rows_of / usac_hscore.hpp stage_a_bounds and
 of k_h16_consts / k_h16_points (the same expressions in the same order; the exact slack, not an
 approximation of it).  The tile: the fp16 rows times the fp16 features summed in fp64 and rounded
@@ -14,7 +19,7 @@ Layout: a wave owns 20 consecutive hypotheses and one point chunk; one iteration
 block; one mask = 64 lanes = hypotheses (10 a + j, 10 a + 5 + j) x the block's 32 points, ten
 masks per iteration.
 
-  python3 tools/h16_mask_stats.py [--seed 1] [--hyps 2000] [--points 10000] [--chunks 5]
+  python3 tools/h16_mask_stats.py [--seed 1] [--hyps 2000] [--points 10000] [--chunks 5] [--models FILE.npy]
 """
 import argparse
 import os
@@ -55,7 +60,15 @@ def features64(p, cc, s1, s2):
     return np.stack([u, v, np.ones_like(u), pp * u, pp * v, pp, q * u, q * v, q], 1)
 
 
-def rows_and_slack(H, cc, s1, s2, fmax, ext, thr):
+ROW_ROUND, FEAT_ROUND = f32(2.0 ** -11), f32(2.0 ** -11 * (1.0 + 2.0 ** -12))  # usac_h16.hpp USAC_H16_*_ROUND
+SLACKS = {  # name -> (row rounding, feature rounding) charged per fp16 value; None: F_m = 0, the unreachable floor
+    "2^-10 (the bound before)": (f32(2.0 ** -10), f32(2.0 ** -10)),
+    "round to nearest (h16_rows_of)": (ROW_ROUND, FEAT_ROUND),
+    "F_m = 0 (floor)": None,
+}
+
+
+def rows_and_slack(H, cc, s1, s2, fmax, ext, thr, row_round=ROW_ROUND, feat_round=FEAT_ROUND):
     """h16_rows_of for every row of H (B x 9 fp32): fp16 rows (B x 3 x 9) and the slack F_m (B)."""
     H = H.astype(np.float32)
     aH = np.abs(H)
@@ -105,8 +118,8 @@ def rows_and_slack(H, cc, s1, s2, fmax, ext, thr):
     agt = np.abs(gt.astype(np.float32))
     fk = fmax.astype(np.float32)[None, None, :]
     ae = np.ldexp(a, e[:, None, None]).astype(np.float32)
-    term = agt * (f32(2.0 ** -10) * fk + f32(2.0 ** -25)) + \
-        fk * (f32(2.0 ** -10) * np.abs(gh) + f32(2.0 ** -25) + f32(2.0 ** -21) * ae) + \
+    term = agt * (feat_round * fk + f32(2.0 ** -25)) + \
+        fk * (row_round * np.abs(gh) + f32(2.0 ** -25) + f32(2.0 ** -21) * ae) + \
         f32(2.0 ** -19) * agt * (fk + f32(2.0 ** -24))
     D = np.full((len(H), 3), f32(2.0 ** -100), np.float32)
     for c in range(9):  # the device's summation order
@@ -137,6 +150,18 @@ def dlt_models(pts, B, rng):
     return h.astype(np.float32)
 
 
+def mask_lanes(acc, Fm, nblk):
+    """kept lanes of every ballot mask: (wave, block, mask) for hypotheses x padded points of acc (3 x B x P)"""
+    B = acc.shape[1]
+    with np.errstate(invalid="ignore"):
+        R = np.abs(acc[2]) + Fm[:, None]
+        keep = (np.abs(acc[0]) <= R) & (np.abs(acc[1]) <= R)  # B x points
+    # mask (wave w, block b, tile a, j): hypotheses 20 w + 10 a + j and + 5, the block's 32 points
+    k = keep.reshape(B // 20, 2, 2, 5, nblk, 32)  # wave, a, half, j, block, point
+    lanes = k.sum((2, 5))  # wave, a, j, block: kept lanes of the mask
+    return lanes.transpose(0, 3, 1, 2).reshape(B // 20, nblk, 10)  # wave, block, mask
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--seed", type=int, default=1)
@@ -145,43 +170,57 @@ def main():
     ap.add_argument("--inlier-ratio", type=float, default=0.3)
     ap.add_argument("--threshold", type=float, default=2.0)
     ap.add_argument("--chunks", type=int, default=5, help="point chunks (the library's choice at cfg2: 5)")
+    ap.add_argument("--models", metavar="FILE.npy", default=None,
+                    help="hypotheses from a file (B x 9 float32, e.g. a batch as the library solved it: "
+                         "Context.estimate_models(Context.draw_samples(...))) instead of random DLT models; "
+                         "--hyps then takes the file's first rows")
     args = ap.parse_args()
-    B = (args.hyps + 19) // 20 * 20
     pts, _, _ = synthetic.homography_points(n=args.points, inlier_ratio=args.inlier_ratio, seed=args.seed)
     cc, s1, s2, fmax, ext = dataset_consts(pts)
-    H = dlt_models(pts, B, np.random.default_rng(args.seed))
-    rows, Fm = rows_and_slack(H, cc, s1, s2, fmax, ext, args.threshold)
+    if args.models:
+        H = np.load(args.models).astype(np.float32).reshape(-1, 9)
+        B = min(len(H), args.hyps) // 20 * 20
+        H, source = H[:B], "the first %d models of %s" % (B, args.models)
+    else:
+        B = (args.hyps + 19) // 20 * 20
+        H, source = dlt_models(pts, B, np.random.default_rng(args.seed)), "random 4-point DLT models"
     feat = features64(pts.astype(np.float64), cc, s1, s2).astype(np.float32).astype(np.float16)
     n = len(pts)
     nblk = (n + 31) // 32
     fpad = np.full((nblk * 32, 9), np.nan)
     fpad[:n] = feat.astype(np.float64)  # padding points: NaN features, never kept
-    acc = np.einsum("hrk,pk->rhp", rows.astype(np.float64), fpad).astype(np.float32)
-    with np.errstate(invalid="ignore"):
-        R = np.abs(acc[2]) + Fm[:, None]
-        keep = (np.abs(acc[0]) <= R) & (np.abs(acc[1]) <= R)  # B x points
-    # mask (wave w, block b, tile a, j): hypotheses 20 w + 10 a + j and + 5, the block's 32 points
-    k = keep.reshape(B // 20, 2, 2, 5, nblk, 32)  # wave, a, half, j, block, point
-    lanes = k.sum((2, 5))  # wave, a, j, block: kept lanes of the mask
-    lanes = lanes.transpose(0, 3, 1, 2).reshape(B // 20, nblk, 10)  # wave, block, mask
-    nonempty = lanes > 0
-    pairs = int(lanes.sum())
-    iters = lanes.shape[0] * lanes.shape[1]
     per = (nblk + args.chunks - 1) // args.chunks
-    print("h16 keep-mask statistics: seed %d, %d hypotheses (%d waves), %d points (%d blocks), thr %g, "
-          "%d point chunks of %d blocks" % (args.seed, B, B // 20, n, nblk, args.threshold, args.chunks, per))
-    print("slack: float32 mirror of h16_rows_of (exact form); F_m median %.4g, non-finite hypotheses %d"
-          % (float(np.median(Fm[np.isfinite(Fm)])), int((~np.isfinite(Fm)).sum())))
-    print("keep rate                                   %.4f %%  (%d of %d pairs)"
-          % (100.0 * pairs / (B * n), pairs, B * n))
-    print("non-empty masks per iteration (of ten)      %.3f" % (nonempty.sum() / iters))
-    print("iterations with a non-empty mask            %.1f %%" % (100.0 * nonempty.any(2).mean()))
-    print("one-lane share of non-empty masks           %.1f %%" % (100.0 * (lanes == 1).sum() / nonempty.sum()))
-    print("kept pairs in one-lane masks                %.1f %%" % (100.0 * (lanes == 1).sum() / pairs))
-    print("kept pairs in masks of 8 or more lanes      %.1f %%" % (100.0 * lanes[lanes >= 8].sum() / pairs))
-    print("kept pairs per wave (one chunk of %d)        %.1f" % (args.chunks, pairs / (lanes.shape[0] * args.chunks)))
-    hist = np.bincount(np.minimum(lanes[nonempty], 9), minlength=10)[1:]
-    print("non-empty masks by kept lanes 1..8, 9+      " + " ".join("%d" % c for c in hist))
+    print("h16 keep-mask statistics: seed %d, %d hypotheses (%d waves; %s), %d points (%d blocks), thr %g, "
+          "%d point chunks of %d blocks" % (args.seed, B, B // 20, source, n, nblk, args.threshold, args.chunks, per))
+    lanes = {name: [] for name in SLACKS}
+    slack = {name: [] for name in SLACKS}
+    for at in range(0, B, 2000):  # 100 waves at a time: the tile of 2 000 x 10 000 pairs is 0.5 GB in fp64
+        Hc = H[at:at + 2000]
+        rows, _ = rows_and_slack(Hc, cc, s1, s2, fmax, ext, args.threshold)
+        acc = np.einsum("hrk,pk->rhp", rows.astype(np.float64), fpad).astype(np.float32)
+        for name, rounds in SLACKS.items():
+            Fm = rows_and_slack(Hc, cc, s1, s2, fmax, ext, args.threshold, *rounds)[1] if rounds else \
+                np.zeros(len(Hc), np.float32)
+            slack[name].append(Fm)
+            lanes[name].append(mask_lanes(acc, Fm, nblk))
+    for name in SLACKS:
+        ln, Fm = np.concatenate(lanes[name]), np.concatenate(slack[name])
+        nonempty = ln > 0
+        pairs = int(ln.sum())
+        iters = ln.shape[0] * ln.shape[1]
+        print("\nslack: %s -- float32 mirror of h16_rows_of (exact form); F_m median %.4g, non-finite hypotheses %d"
+              % (name, float(np.median(Fm[np.isfinite(Fm)])), int((~np.isfinite(Fm)).sum())))
+        print("keep rate                                   %.4f %%  (%d of %d pairs)"
+              % (100.0 * pairs / (B * n), pairs, B * n))
+        print("non-empty masks per iteration (of ten)      %.3f" % (nonempty.sum() / iters))
+        print("iterations with a non-empty mask            %.1f %%" % (100.0 * nonempty.any(2).mean()))
+        print("one-lane share of non-empty masks           %.1f %%" % (100.0 * (ln == 1).sum() / nonempty.sum()))
+        print("kept pairs in one-lane masks                %.1f %%" % (100.0 * (ln == 1).sum() / pairs))
+        print("kept pairs in masks of 8 or more lanes      %.1f %%" % (100.0 * ln[ln >= 8].sum() / pairs))
+        print("kept pairs per wave (one chunk of %d)        %.1f" % (args.chunks, pairs / (ln.shape[0] * args.chunks)))
+        print("non-empty masks per wave (one chunk of %d)   %.1f" % (args.chunks, nonempty.sum() / (ln.shape[0] * args.chunks)))
+        hist = np.bincount(np.minimum(ln[nonempty], 9), minlength=10)[1:]
+        print("non-empty masks by kept lanes 1..8, 9+      " + " ".join("%d" % c for c in hist))
 
 
 if __name__ == "__main__":
