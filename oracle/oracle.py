@@ -625,6 +625,24 @@ def hypothesis_loop_mt(kind, points, thr, seed, count, threads, dlt_mode=DLT_THI
     return dt, best.value
 
 
+TRACE_FIELDS = ("f7_fallback", "e5_fallback", "cubic_c0_0", "cubic_c0_1", "cubic_c0_2", "cubic_d_le0", "cubic_gen_1",
+                "cubic_gen_2", "cubic_gen_3", "f8_zero", "epipole2", "eig_exit", "eig_steps")  # usac_oracle.h ORC_TRACE_*
+EIG_EXITS = ("trace", "cholesky", "nn", "converged", "slow", "steps")  # usac_oracle.h ORC_EIG_*
+
+
+def trace_reset():
+    """Zero the calling thread's path counters (eig_exit: -1, no eigen call yet)."""
+    lib().orc_trace_reset()
+
+
+def trace_get():
+    """The calling thread's path counters since trace_reset() as a dict over TRACE_FIELDS; eig_exit /
+    eig_steps describe the last eig_min_invit call (an index into EIG_EXITS, -1 for none)."""
+    out = (ctypes.c_int * len(TRACE_FIELDS))()
+    lib().orc_trace_get(out)
+    return dict(zip(TRACE_FIELDS, list(out)))
+
+
 def sym_eig_min(A):
     """The LSQ fits' 9x9 eigen spec: (smallest-eigenvalue eigenvector, True if inverse iteration
     converged / False if the Jacobi fall-back ran)."""

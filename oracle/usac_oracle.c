@@ -106,6 +106,20 @@ int orc_inv3x3(const float *m, float *dst) {
     return 1;
 }
 
+/* Path counters (usac_oracle.h orc_trace_*): thread-local, write-only for the solvers -- no
+ * result depends on them. */
+static __thread int g_trace[ORC_TRACE_N];
+void orc_trace_reset(void) {
+    memset(g_trace, 0, sizeof(g_trace));
+    g_trace[ORC_TRACE_EIG_EXIT] = -1;
+}
+void orc_trace_get(int *out) { memcpy(out, g_trace, sizeof(g_trace)); }
+static int eig_exit(int code, int steps) {
+    g_trace[ORC_TRACE_EIG_EXIT] = code;
+    g_trace[ORC_TRACE_EIG_STEPS] = steps;
+    return code == ORC_EIG_CONVERGED;
+}
+
 /* One-sided (Hestenes) Jacobi on the ROWS of an r x 9 matrix, r <= 9, fp64.
  * Restates the row space part of cv::SVD::compute (thin, default flags) used by
  * dlt.cpp:43 / dlt.cpp:92: after convergence the rows are mutually orthogonal,
@@ -330,13 +344,13 @@ static void sym_eig_min_jacobi(double A[9][9], double *v) {
 static int eig_min_invit(double A[9][9], double *v) {
     double tr = 0.0;
     for (int k = 0; k < 9; k++) tr += A[k][k];
-    if (!(tr > 0.0) || !isfinite(tr)) return 0;
+    if (!(tr > 0.0) || !isfinite(tr)) return eig_exit(ORC_EIG_TRACE, 0);
     const double mu = tr * 1e-12;
     double L[9][9], inv[9];
     for (int j = 0; j < 9; j++) {
         double d = A[j][j] + mu;
         for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k];
-        if (!(d > 0.0)) return 0;
+        if (!(d > 0.0)) return eig_exit(ORC_EIG_CHOLESKY, 0);
         L[j][j] = sqrt(d);
         inv[j] = 1.0 / L[j][j];
         for (int i = j + 1; i < 9; i++) {
@@ -361,7 +375,7 @@ static int eig_min_invit(double A[9][9], double *v) {
         }
         double nn = 0.0;
         for (int k = 0; k < 9; k++) nn += z[k] * z[k];
-        if (!(nn > 0.0) || !isfinite(nn)) return 0;
+        if (!(nn > 0.0) || !isfinite(nn)) return eig_exit(ORC_EIG_NN, it + 1);
         const double r = 1.0 / sqrt(nn);
         double d = 0.0;
         for (int k = 0; k < 9; k++) {
@@ -372,12 +386,12 @@ static int eig_min_invit(double A[9][9], double *v) {
         }
         if (d <= 1e-13) {
             for (int k = 0; k < 9; k++) v[k] = x[k];
-            return 1;
+            return eig_exit(ORC_EIG_CONVERGED, it + 1);
         }
-        if (it >= 2 && d > 0.25 * dprev) return 0;
+        if (it >= 2 && d > 0.25 * dprev) return eig_exit(ORC_EIG_SLOW, it + 1);
         dprev = d;
     }
-    return 0;
+    return eig_exit(ORC_EIG_STEPS, 30);
 }
 
 static void sym_eig_min(double A[9][9], double *v) {
@@ -928,22 +942,22 @@ static double cubic_bisect(double a, double b, double c, double lo, double hi) {
 static int cubic_roots(double c0, double c1, double c2, double c3, double *r) {
     if (c0 == 0.0) {
         if (c1 == 0.0) {
-            if (c2 == 0.0) return 0;
+            if (c2 == 0.0) return g_trace[ORC_TRACE_CUBIC_C0_0]++, 0;
             r[0] = -c3 / c2;
-            return 1;
+            return g_trace[ORC_TRACE_CUBIC_C0_1]++, 1;
         }
         double D = c2 * c2 - 4.0 * c1 * c3;
-        if (D < 0.0) return 0;
+        if (D < 0.0) return g_trace[ORC_TRACE_CUBIC_C0_0]++, 0;
         if (D == 0.0) {
             r[0] = -c2 / (2.0 * c1);
-            return 1;
+            return g_trace[ORC_TRACE_CUBIC_C0_1]++, 1;
         }
         double s = sqrt(D);
         double q = -0.5 * (c2 + (c2 >= 0.0 ? s : -s));
         double x1 = q / c1, x2 = c3 / q;
         r[0] = x1 < x2 ? x1 : x2;
         r[1] = x1 < x2 ? x2 : x1;
-        return 2;
+        return g_trace[ORC_TRACE_CUBIC_C0_2]++, 2;
     }
     const double a = c1 / c0, b = c2 / c0, c = c3 / c0;
     double R = fabs(a);
@@ -954,6 +968,7 @@ static int cubic_roots(double c0, double c1, double c2, double c3, double *r) {
     int n = 0;
     if (!(D > 0.0)) {
         r[n++] = cubic_bisect(a, b, c, -R, R);
+        g_trace[ORC_TRACE_CUBIC_D_LE0]++;
         return n;
     }
     const double s = sqrt(D);
@@ -962,6 +977,7 @@ static int cubic_roots(double c0, double c1, double c2, double c3, double *r) {
     if (v1 >= 0.0) r[n++] = cubic_bisect(a, b, c, -R, m1);
     if (v1 > 0.0 && v2 < 0.0) r[n++] = cubic_bisect(a, b, c, m1, m2);
     if (v2 <= 0.0) r[n++] = cubic_bisect(a, b, c, m2, R);
+    if (n >= 1 && n <= 3) g_trace[ORC_TRACE_CUBIC_GEN_1 + n - 1]++;
     return n;
 }
 
@@ -974,6 +990,7 @@ static int fund_is_valid(const float *pts, const float *F, const int *sample) {
     float e2 = F[0] * F[7] - F[1] * F[6];
     if (!((e0 > 1.9984e-15 || e0 < -1.9984e-15) || (e1 > 1.9984e-15 || e1 < -1.9984e-15) ||
           (e2 > 1.9984e-15 || e2 < -1.9984e-15))) {
+        g_trace[ORC_TRACE_EPIPOLE2]++;
         e0 = F[4] * F[8] - F[5] * F[7];
         e1 = F[5] * F[6] - F[3] * F[8];
         e2 = F[3] * F[7] - F[4] * F[6];
@@ -1007,6 +1024,7 @@ static int fundamental_7pt(const orc_est *e, const int *sample, float *models) {
     double N[2][9], W0[7][9];
     memcpy(W0, W, sizeof(W0));
     if (!qr_null(W, 7, N)) {
+        g_trace[ORC_TRACE_F7_FALLBACK]++;
         row_jacobi(W0, 7);
         null_complement(W0, 7, 2, N);
     }
@@ -1047,6 +1065,7 @@ static int fundamental_7pt(const orc_est *e, const int *sample, float *models) {
             F[8] = 1.f;
         } else {
             F[8] = 0.f;
+            g_trace[ORC_TRACE_F8_ZERO]++;
         }
         for (int i = 0; i < 8; i++) F[i] = f1[i] * lambda + f2[i] * mu;
         if (fund_is_valid(e->pts, F, sample)) {
@@ -2130,6 +2149,7 @@ static void e5_poly(double W[9][9], double N[4][9], double a[11]) {
     double W0[5][9];
     memcpy(W0, W, sizeof(W0));
     if (!qr_null(W, 5, N)) {
+        g_trace[ORC_TRACE_E5_FALLBACK]++;
         row_jacobi(W0, 5);
         null_complement(W0, 5, 4, N);
     }

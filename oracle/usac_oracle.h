@@ -67,6 +67,27 @@ int orc_est_nonminimal(orc_est *e, const int *sample, unsigned int n, float *mod
 /* the LSQ fits' 9x9 eigen spec (inverse iteration, Jacobi fall-back): smallest-eigenvalue
  * eigenvector of the symmetric A (row-major 81); returns 1 if inverse iteration converged */
 int orc_sym_eig_min(const double *A81, double *v);
+/* Path counters of the calling thread (tests only; no result depends on them): which branches
+ * the solvers took since orc_trace_reset().  orc_trace_get copies ORC_TRACE_N ints. */
+enum {
+    ORC_TRACE_F7_FALLBACK = 0, /* 7-point: qr_null refused -> row_jacobi + null_complement */
+    ORC_TRACE_E5_FALLBACK,     /* 5-point: the same */
+    ORC_TRACE_CUBIC_C0_0,      /* cubic_roots, c0 == 0: no root */
+    ORC_TRACE_CUBIC_C0_1,      /*   one root (linear, or D == 0) */
+    ORC_TRACE_CUBIC_C0_2,      /*   two roots */
+    ORC_TRACE_CUBIC_D_LE0,     /* not (a^2 - 3b > 0): one bisection over [-R, R] */
+    ORC_TRACE_CUBIC_GEN_1,     /* general arm: one, */
+    ORC_TRACE_CUBIC_GEN_2,     /*   two, */
+    ORC_TRACE_CUBIC_GEN_3,     /*   three roots */
+    ORC_TRACE_F8_ZERO,         /* 7-point: |s| <= DBL_EPSILON, F[8] = 0 stored */
+    ORC_TRACE_EPIPOLE2,        /* oriented test: the second epipole (row1 x row2) used */
+    ORC_TRACE_EIG_EXIT,        /* exit of the last eig_min_invit call (ORC_EIG_*; -1: none since reset) */
+    ORC_TRACE_EIG_STEPS,       /*   and the inverse-iteration steps it ran */
+    ORC_TRACE_N
+};
+enum { ORC_EIG_TRACE = 0, ORC_EIG_CHOLESKY, ORC_EIG_NN, ORC_EIG_CONVERGED, ORC_EIG_SLOW, ORC_EIG_STEPS };
+void orc_trace_reset(void);
+void orc_trace_get(int *out);
 /* the weighted overload (weights[point index]): homography / fundamental; -1 for the others */
 int orc_est_nonminimal_weighted(orc_est *e, const int *sample, unsigned int n, const float *weights, float *model);
 void orc_est_set_model(orc_est *e, const float *model);
