@@ -80,7 +80,10 @@
  *                                  ABI 25: usac_multi_create_device, a multi context from padded device memory
  *                                  (rows with a validity mask or counts, or keypoints with a match index),
  *                                  packed on the device, with usac_multi_get_offsets, usac_multi_get_source
- *                                  and usac_multi_padded_mask, a host mask scattered into P x n_max device bytes
+ *                                  and usac_multi_padded_mask, a host mask scattered into P x n_max device bytes;
+ *                                  ABI 26: usac_multi_create_device_sorted, the same context with every problem's
+ *                                  kept rows sorted on the device by a score per column, the better first, so
+ *                                  that usac_multi_run_prosac runs on a matcher's output as it is
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -95,7 +98,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 25
+#define USAC_ABI_VERSION 26
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -620,9 +623,38 @@ int usac_multi_create_device(usac_multi **out, int device, int estimator, const 
 /* The context's offsets (ABI 25): offsets[P + 1], host.  Any multi context; what a caller of
  * usac_multi_create_device sizes its arrays by (N_total = offsets[P]).  USAC_ERR_ARG for a NULL argument. */
 int usac_multi_get_offsets(const usac_multi *mc, uint32_t *offsets);
+/* Device input in quality order (ABI 26): usac_multi_create_device with the kept columns of every problem sorted
+ * by a score per column before anything else sees them -- what usac_multi_run_prosac expects of its input, from
+ * a matcher that emits matches in keypoint order and a score per keypoint.  scores[p, j] is the quality of column j
+ * of problem p: P x n_max fp32 of device memory of `device`, 4-byte aligned, checked as every pointer of `in` and
+ * read on in->stream.  The order within problem p:
+ *   - the better score first: the larger with descending != 0 (a confidence), the smaller with 0 (a distance);
+ *   - equal scores in ascending column order; +0 and -0 are equal;
+ *   - +inf and -inf are ordinary numbers;
+ *   - a NaN, whatever its sign or payload, after every number in either direction, in ascending column order;
+ *   - scores of columns that are not kept are never looked at.
+ * In numpy, for the kept columns cols (ascending) and k = scores[p, cols]:
+ *   nan = isnan(k); k2 = where(nan, 0, k); order = lexsort((cols, -k2 if descending else k2, nan)).
+ * The sort is stable and deterministic.  Rows are moved, not computed with; with K1 / K2 the conversion runs
+ * after the sort, on the sorted rows. */
+typedef struct usac_multi_device_order {
+    const float *scores;   /* DEVICE, P x n_max fp32: the quality of column j of problem p */
+    int descending;        /* nonzero: larger is better; 0: smaller is better */
+} usac_multi_device_order;
+/* usac_multi_create_device over `in`, the kept rows of every problem in the order above.  Everything
+ * usac_multi_create_device refuses is refused here with the same code at the same stage; also USAC_ERR_ARG before
+ * any device call for a NULL order or order->scores, and before any launch for scores that are not device memory
+ * of `device`, misaligned, or an allocation too short.  The result is an ordinary device-input context:
+ * usac_multi_get_offsets, usac_multi_get_source (the sorted order) and usac_multi_padded_mask work on it, and per
+ * problem it equals, bit for bit, a context created from the host over the kept rows in that order.
+ * usac_multi_run_prosac keeps refusing problems of 20 points or fewer.  A refusal is reported as
+ * usac_multi_create_device's, under this entry's name. */
+int usac_multi_create_device_sorted(usac_multi **out, int device, int estimator, const usac_multi_device_input *in,
+                                    const usac_multi_device_order *order);
 /* The column of every packed row (ABI 25): src[N_total], host; row offsets[p] + i of the context is column
- * src[offsets[p] + i] of problem p's padded input, ascending within a problem.  USAC_ERR_UNSUPPORTED on a context
- * not created by usac_multi_create_device, USAC_ERR_ARG for a NULL argument. */
+ * src[offsets[p] + i] of problem p's padded input: ascending within a problem on a context from
+ * usac_multi_create_device, in quality order (ABI 26) on one from usac_multi_create_device_sorted.
+ * USAC_ERR_UNSUPPORTED on a context created from the host, USAC_ERR_ARG for a NULL argument. */
 int usac_multi_get_source(usac_multi *mc, uint32_t *src);
 /* A mask over the packed rows back in the padded layout (ABI 25).  mask: HOST, N_total bytes, what
  * usac_multi_inliers, usac_multi_polish or a polished run wrote; d_out: P x n_max bytes of device memory of the

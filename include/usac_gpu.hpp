@@ -589,6 +589,21 @@ public:
         mc.check(usac_multi_get_offsets(mc.mc_, mc.offsets_.data()), "MultiContext::fromDevice");
         return mc;
     }
+    // fromDevice with every problem's kept rows sorted by a score per column, the better first
+    // (usac_multi_create_device_sorted, ABI 26; the rule: usac_gpu.h): order.scores is P x n_max fp32 of device
+    // memory, read on in.stream.  What runProsac expects of its input.  Ownership as fromDevice's: the context
+    // holds its own copy when the call returns; source() then returns the sorted order.
+    static MultiContext fromDeviceSorted(int estimator, const usac_multi_device_input &in,
+                                         const usac_multi_device_order &order, int device = 0) {
+        MultiContext mc((std::vector<uint32_t>()));
+        mc.est_ = (ESTIMATOR)estimator;
+        const int rc = usac_multi_create_device_sorted(&mc.mc_, device, estimator, &in, &order);
+        if (rc != USAC_OK) throw Error(rc, usac_multi_last_error(nullptr));
+        mc.offsets_.resize((size_t)in.P + 1);
+        mc.n_max_ = in.n_max;
+        mc.check(usac_multi_get_offsets(mc.mc_, mc.offsets_.data()), "MultiContext::fromDeviceSorted");
+        return mc;
+    }
     ~MultiContext() {
         if (mc_) usac_multi_destroy(mc_);
     }
@@ -651,8 +666,9 @@ public:
     // the context's offsets[P + 1], and the padded width of a context from fromDevice (else 0)
     const std::vector<uint32_t> &offsets() const { return offsets_; }
     unsigned int paddedWidth() const { return n_max_; }
-    // usac_multi_get_source (ABI 25, a context from fromDevice): per packed row the column of the padded input
-    // it came from, ascending within a problem.  Throws USAC_ERR_UNSUPPORTED on any other context.
+    // usac_multi_get_source (ABI 25, a context from fromDevice / fromDeviceSorted): per packed row the column of
+    // the padded input it came from, ascending within a problem (fromDeviceSorted: in quality order).  Throws
+    // USAC_ERR_UNSUPPORTED on any other context.
     std::vector<uint32_t> source() const {
         std::vector<uint32_t> out(offsets_.empty() ? 0u : offsets_.back());
         check(usac_multi_get_source(mc_, out.empty() ? nullptr : out.data()), "MultiContext::source");

@@ -186,6 +186,11 @@ class _MultiDeviceInput(ctypes.Structure):
                 ("stream", ctypes.c_void_p)]
 
 
+class _MultiDeviceOrder(ctypes.Structure):
+    """usac_multi_device_order (ABI 26): the scores' device pointer as an integer, and the direction"""
+    _fields_ = [("scores", ctypes.c_void_p), ("descending", ctypes.c_int)]
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -216,6 +221,7 @@ ABI_SYMBOLS = [
     "usac_multi_create_essential_pixels", "usac_multi_set_pixel_thresholds", "usac_multi_pixel_models",
     "usac_multi_get_points",
     "usac_multi_create_device", "usac_multi_get_offsets", "usac_multi_get_source", "usac_multi_padded_mask",
+    "usac_multi_create_device_sorted",
 ]
 
 
@@ -320,6 +326,8 @@ def lib():
         "usac_multi_pixel_models": (ctypes.c_int, [_vp, f32p, f32p]),
         "usac_multi_get_points": (ctypes.c_int, [_vp, f32p]),
         "usac_multi_create_device": (ctypes.c_int, [_P(_vp), ctypes.c_int, ctypes.c_int, _P(_MultiDeviceInput)]),
+        "usac_multi_create_device_sorted": (ctypes.c_int, [_P(_vp), ctypes.c_int, ctypes.c_int, _P(_MultiDeviceInput),
+                                                           _P(_MultiDeviceOrder)]),
         "usac_multi_get_offsets": (ctypes.c_int, [_vp, u32p]),
         "usac_multi_get_source": (ctypes.c_int, [_vp, u32p]),
         "usac_multi_padded_mask": (ctypes.c_int, [_vp, u8p, _vp, _vp]),
@@ -864,11 +872,15 @@ class MultiContext:
     comes down at creation (`points` is None, resident_points() fetches the rows), `n_max` is the padded width and
     `source_index` the column of every packed row.  Such a context has inlier_lists = False: a polished run keeps
     its host mask as `last_mask` and returns no index lists, and padded_mask() hands the mask back as a
-    (P, n_max) device tensor."""
+    (P, n_max) device tensor.  With scores=(P, n_max) float32 device tensor (usac_multi_create_device_sorted) the
+    device also sorts every problem's kept rows by score, the better first and ties in column order: the input
+    run_prosac expects, from a matcher's output as it is.  `sorted_by_score` is then True, `source_index` is in
+    that order, and padded_mask() still lands every bit on its column."""
 
     inlier_lists = True  # False: polish(with_inliers=True) and the polished runs return no index lists
     last_mask = None     # the N_total host mask bytes of the last call that computed inliers
     n_max = None         # the padded width of a context from device input
+    sorted_by_score = False  # True: from_padded / from_matches with scores, the rows are in quality order
     device = 0
 
     def __init__(self, estimator, point_sets, device=0):
@@ -947,33 +959,42 @@ class MultiContext:
             self.points = self.resident_points()
 
     @classmethod
-    def from_padded(cls, estimator, rows, valid=None, counts=None, K1=None, K2=None, stream=None, device=None):
+    def from_padded(cls, estimator, rows, valid=None, counts=None, K1=None, K2=None, stream=None, device=None,
+                    scores=None, descending=True):
         """usac_multi_create_device, form a: rows is a (P, n_max, 4) float32 device tensor, with valid (P, n_max)
         bool or uint8, nonzero keeps the row, or counts (P,) int32, the first counts[p] rows are kept, or neither
         (all rows are kept).  estimator: Homography, Fundamental or Essential; K1 / K2 (Essential only, host, as
         essential_pixels') convert the kept pixel rows on the device.  stream: the stream handle that orders the
         writes of the tensors (default: torch's current stream for torch tensors, else 0); the call waits for it.
         TypeError for host arrays, ValueError for a wrong shape, dtype or a non-contiguous layout, UsacError(-1)
-        naming the problem that keeps fewer rows than the sample size or has a count outside 0..n_max."""
+        naming the problem that keeps fewer rows than the sample size or has a count outside 0..n_max.
+        scores (usac_multi_create_device_sorted): a (P, n_max) float32 device tensor, the quality of every column;
+        the kept rows of a problem are then sorted on the device, the better score first (descending: the larger,
+        else the smaller), equal scores (+0 and -0 are) in column order, NaNs last in column order; scores of
+        columns that are not kept are not looked at.  None: column order, as without the argument."""
         r = _DevArray(rows, "rows").need((None, None, 4), ("f4",))
         P, n_max = r.shape[0], r.shape[1]
         v = None if valid is None else _DevArray(valid, "valid").need((P, n_max), ("b1", "u1"))
         c = None if counts is None else _DevArray(counts, "counts").need((P,), ("i4",))
         if v is not None and c is not None:
             raise ValueError("valid and counts are alternatives")
+        s = None if scores is None else _DevArray(scores, "scores").need((P, n_max), ("f4",))
         inp = _MultiDeviceInput(P=P, n_max=n_max, rows=r.ptr, valid=v and v.ptr, counts=c and c.ptr)
-        return cls._from_device(estimator, inp, [r, v, c], K1, K2, stream, device)
+        return cls._from_device(estimator, inp, [r, v, c, s], K1, K2, stream, device, s, descending)
 
     @classmethod
-    def from_matches(cls, estimator, kpts0, kpts1, matches, K1=None, K2=None, stream=None, device=None):
+    def from_matches(cls, estimator, kpts0, kpts1, matches, K1=None, K2=None, stream=None, device=None,
+                     scores=None, descending=True):
         """usac_multi_create_device, form b: kpts0 (P, n0, 2) and kpts1 (P, n1, 2) float32 device tensors and
         matches (P, n0) int32 (int64 is cast on the device): keypoint j of view 1 is kept when matches[p, j] >= 0,
         its row is (kpts0[p, j], kpts1[p, matches[p, j]]); n_max is n0.  Otherwise as from_padded; UsacError(-1)
-        also for a match index >= n1, which is never dereferenced."""
+        also for a match index >= n1, which is never dereferenced.  scores: (P, n0) float32, a matcher's score
+        per keypoint of view 1, as from_padded's."""
         a = _DevArray(kpts0, "kpts0").need((None, None, 2), ("f4",))
         P, n0 = a.shape[0], a.shape[1]
         b = _DevArray(kpts1, "kpts1").need((P, None, 2), ("f4",))
         m = _DevArray(matches, "matches").need((P, n0), ("i4", "i8"))
+        s = None if scores is None else _DevArray(scores, "scores").need((P, n0), ("f4",))
         if m.kind == "i8":
             if not m.torch:
                 raise ValueError("matches must be of dtype i4, got i8")
@@ -985,10 +1006,10 @@ class MultiContext:
             if stream is not None and int(stream) != cur.cuda_stream:
                 cur.synchronize()
         inp = _MultiDeviceInput(P=P, n_max=n0, kpts0=a.ptr, kpts1=b.ptr, n1=b.shape[1], match=m.ptr)
-        return cls._from_device(estimator, inp, [a, b, m], K1, K2, stream, device)
+        return cls._from_device(estimator, inp, [a, b, m, s], K1, K2, stream, device, s, descending)
 
     @classmethod
-    def _from_device(cls, estimator, inp, arrays, K1, K2, stream, device):
+    def _from_device(cls, estimator, inp, arrays, K1, K2, stream, device, scores=None, descending=True):
         arrays = [a for a in arrays if a is not None]
         self = cls.__new__(cls)
         self._h = None
@@ -1011,7 +1032,12 @@ class MultiContext:
         inp.stream = int(stream) or None
         L = lib()
         h = _vp()
-        rc = L.usac_multi_create_device(ctypes.byref(h), int(device), int(self.estimator), ctypes.byref(inp))
+        if scores is None:
+            rc = L.usac_multi_create_device(ctypes.byref(h), int(device), int(self.estimator), ctypes.byref(inp))
+        else:
+            order = _MultiDeviceOrder(scores=scores.ptr, descending=1 if descending else 0)
+            rc = L.usac_multi_create_device_sorted(ctypes.byref(h), int(device), int(self.estimator), ctypes.byref(inp),
+                                                   ctypes.byref(order))
         if rc != 0:
             msg = L.usac_multi_last_error(None)
             raise UsacError(rc, msg.decode() if msg else "usac_multi_create_device failed")
@@ -1026,13 +1052,15 @@ class MultiContext:
         self.m = {ESTIMATOR.Fundamental: 7, ESTIMATOR.Essential: 5}.get(self.estimator, 4)
         self.spk = 3 if self.estimator == ESTIMATOR.Fundamental else 1
         self.inlier_lists = False
+        self.sorted_by_score = scores is not None
         self._source = None
         return self
 
     @property
     def source_index(self):
         """usac_multi_get_source (a context from device input): per packed row the column of the padded input it
-        came from, a uint32 array of N_total values, ascending within a problem; fetched at first use."""
+        came from, a uint32 array of N_total values, ascending within a problem (sorted_by_score: in quality
+        order); fetched at first use."""
         if getattr(self, "_source", None) is None:
             src = np.zeros(int(self.offsets[-1]), dtype=np.uint32)
             self._check(lib().usac_multi_get_source(self._h, _ptr(src, ctypes.c_uint32)), "multi_get_source")

@@ -4679,9 +4679,10 @@ int multi_run_uniform(usac_multi *mc, const usac_params *prm, const uint64_t *se
 // what usac_multi_create_device refused its input for, kept for usac_multi_last_error(NULL): the context that
 // would hold the message does not survive the refusal
 thread_local std::string g_create_device_err;
+thread_local const char *g_create_device_entry = "usac_multi_create_device";  // the entry that reports
 
 int create_device_fail(int code, const std::string &msg) {
-    g_create_device_err = "usac_multi_create_device: " + msg;
+    g_create_device_err = std::string(g_create_device_entry) + ": " + msg;
     fprintf(stderr, "%s\n", g_create_device_err.c_str());
     return code;
 }
@@ -4795,10 +4796,14 @@ int usac_multi_create_essential_pixels(usac_multi **out, int device, const float
     return USAC_OK;
 }
 
-int usac_multi_create_device(usac_multi **out, int device, int estimator, const usac_multi_device_input *in) {
+// usac_multi_create_device (sorted false, order ignored) and usac_multi_create_device_sorted (ABI 26: order and its
+// scores are needed), reporting under the entry's name
+static int multi_create_device(const char *entry, usac_multi **out, int device, int estimator, const usac_multi_device_input *in,
+                               bool sorted, const usac_multi_device_order *order) {
     if (!out) return USAC_ERR_ARG;
     *out = nullptr;
     g_create_device_err.clear();
+    g_create_device_entry = entry;
     if (!in) return create_device_fail(USAC_ERR_ARG, "NULL input");
     if (estimator != USAC_HOMOGRAPHY && estimator != USAC_FUNDAMENTAL && estimator != USAC_ESSENTIAL)
         return create_device_fail(USAC_ERR_UNSUPPORTED, "homography, fundamental or essential estimator only");
@@ -4822,6 +4827,8 @@ int usac_multi_create_device(usac_multi **out, int device, int estimator, const 
             if (!usac::pixel_k_ok(K1 + 9 * (size_t)p) || !usac::pixel_k_ok(K2 + 9 * (size_t)p))
                 return create_device_fail(USAC_ERR_ARG, "problem " + std::to_string(p) + ": K must be finite and upper "
                                                         "triangular with fx, fy > 0 and a last row of 0 0 1");
+    if (sorted && (!order || !order->scores)) return create_device_fail(USAC_ERR_ARG, "NULL order or scores");
+    const float *scores = sorted ? order->scores : nullptr;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return create_device_fail(USAC_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
     // a host pointer must never reach a kernel: every pointer the kernels will read, before any launch
@@ -4829,7 +4836,8 @@ int usac_multi_create_device(usac_multi **out, int device, int estimator, const 
     struct { const void *p; const char *name; size_t bytes, align; } ptrs[] = {
         {in->rows, "rows", cells * 16, 16},           {in->valid, "valid", cells, 1},
         {in->counts, "counts", (size_t)P * 4, 4},     {in->kpts0, "kpts0", cells * 8, 8},
-        {in->kpts1, "kpts1", (size_t)P * in->n1 * 8, 8}, {in->match, "match", cells * 4, 4}};
+        {in->kpts1, "kpts1", (size_t)P * in->n1 * 8, 8}, {in->match, "match", cells * 4, 4},
+        {scores, "scores", cells * 4, 4}};
     for (const auto &q : ptrs) {
         if (!q.p) continue;
         const std::string why = device_pointer_problem(q.p, q.name, device, q.bytes, q.align);
@@ -4850,12 +4858,15 @@ int usac_multi_create_device(usac_multi **out, int device, int estimator, const 
     usac_multi *mc = multi_new(device, estimator, P);
     mc->n_max = n_max;
     DevBuf dcount, dcal;  // the counting pass's 2 P values; the intrinsics
+    DevBuf dtmp, druns;   // with scores: the pack's rows and columns before the sort; the sort's runs past its cap
     PinBlock pin;
     std::string msg;
     const char *what = "hipStreamCreate";
     auto done = [&](int code) {
         dcount.release();
         dcal.release();
+        dtmp.release();
+        druns.release();
         if (pin.p) PinnedPool::get().give_back(pin.p, pin.bytes);
         if (code == USAC_OK) {
             *out = mc;
@@ -4902,9 +4913,42 @@ int usac_multi_create_device(usac_multi **out, int device, int estimator, const 
         e = hipMemcpyAsync(mc->offs.p, mc->offsets.data(), sizeof(uint32_t) * ((size_t)P + 1), hipMemcpyHostToDevice, cs);
         what = "hipMemcpy offsets";
     }
-    if (e == hipSuccess) {
+    if (e == hipSuccess && !scores) {
         e = usac::launch_multi_pack(cs, pk, mc->offs.as<uint32_t>(), mc->pts.as<float4>(), mc->src.as<uint32_t>());
         what = "k_multi_pack";
+    }
+    if (e == hipSuccess && scores) {
+        // the pack as it is, into a temporary block of N_total x (16 + 4) bytes; the sort moves every row from it
+        // to its place in quality order (kernels_multi_sort.hip), on the same stream
+        usac::MultiSort so{};
+        so.cap = usac::kMultiSortLds;
+        if (const char *es = getenv("USAC_MULTI_SORT_LDS")) {  // tests: a lower cap on the rows sorted in LDS at once
+            const long v = atol(es);
+            if (v > 0 && v < (long)usac::kMultiSortLds) so.cap = (uint32_t)v;
+        }
+        const size_t n_total = mc->n_total;
+        e = dtmp.reserve((sizeof(float) * 4 + sizeof(uint32_t)) * n_total);
+        what = "hipMalloc the rows before the sort";
+        if (e == hipSuccess && *std::max_element(sizes, sizes + P) > so.cap) e = druns.reserve(sizeof(uint64_t) * n_total);
+        float4 *rows_in = dtmp.as<float4>();
+        uint32_t *src_in = reinterpret_cast<uint32_t *>(rows_in + n_total);
+        if (e == hipSuccess) {
+            e = usac::launch_multi_pack(cs, pk, mc->offs.as<uint32_t>(), rows_in, src_in);
+            what = "k_multi_pack";
+        }
+        if (e == hipSuccess) {
+            so.scores = reinterpret_cast<const uint32_t *>(scores);
+            so.n_max = n_max;
+            so.descending = order->descending != 0;
+            so.offsets = mc->offs.as<uint32_t>();
+            so.rows_in = reinterpret_cast<const uint4 *>(rows_in);
+            so.src_in = src_in;
+            so.pts = reinterpret_cast<uint4 *>(mc->pts.as<float4>());
+            so.src = mc->src.as<uint32_t>();
+            so.runs = druns.as<uint64_t>();
+            e = usac::launch_multi_sort(cs, P, so);
+            what = "k_multi_sort";
+        }
     }
     std::vector<float> calib;
     if (e == hipSuccess && K1) {  // pixels -> calibrated rows, as usac_multi_create_essential_pixels, behind the pack
@@ -4935,6 +4979,15 @@ int usac_multi_create_device(usac_multi **out, int device, int estimator, const 
         return done(USAC_ERR_HIP);
     }
     return done(USAC_OK);
+}
+
+int usac_multi_create_device(usac_multi **out, int device, int estimator, const usac_multi_device_input *in) {
+    return multi_create_device("usac_multi_create_device", out, device, estimator, in, false, nullptr);
+}
+
+int usac_multi_create_device_sorted(usac_multi **out, int device, int estimator, const usac_multi_device_input *in,
+                                    const usac_multi_device_order *order) {
+    return multi_create_device("usac_multi_create_device_sorted", out, device, estimator, in, true, order);
 }
 
 int usac_multi_get_offsets(const usac_multi *mc, uint32_t *offsets) {

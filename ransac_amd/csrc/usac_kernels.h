@@ -490,6 +490,23 @@ hipError_t launch_multi_pack(hipStream_t st, const MultiPack &a, const uint32_t 
 hipError_t launch_multi_unpack_mask(hipStream_t st, const uint8_t *mask, const uint32_t *src, const uint32_t *offsets,
                                     uint32_t P, uint32_t n_total, uint32_t n_max, uint8_t *out);
 
+// Device input in quality order (kernels_multi_sort.hip, ABI 26): per problem the packed rows rows_in / src_in
+// (launch_multi_pack's output, ascending columns) -> pts / src, stably sorted by scores[p, src_in[i]], the better
+// first (usac_sort_key.hpp).  scores: P x n_max fp32 read as their bits.  cap: 1..kMultiSortLds, the rows a
+// problem sorts in LDS at once; runs: 8 bytes per packed row, needed (else nullable) when a problem has more
+constexpr uint32_t kMultiSortLds = 4096;
+struct MultiSort {
+    const uint32_t *scores;
+    uint32_t n_max, descending, cap;
+    const uint32_t *offsets;
+    const uint4 *rows_in;
+    const uint32_t *src_in;
+    uint4 *pts;
+    uint32_t *src;
+    uint64_t *runs;
+};
+hipError_t launch_multi_sort(hipStream_t st, uint32_t P, const MultiSort &a);
+
 // k nearest neighbours of every point (kernels_knn.hip, nearest_neighbors.cpp:69-128):
 // idx / d2 (nullable) n x k, self excluded, ascending distance, ties by index; 1 <= k <= 32
 constexpr uint32_t kKnnMax = 32;

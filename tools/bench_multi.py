@@ -69,6 +69,14 @@ for both: min / median / max ms over the repetitions, the numpy conversion's sha
 entry alone (usac_multi_create_essential_pixels + usac_multi_destroy, no read-back).  The two contexts'
 run(polish=True) results must be equal bit for bit (exit status 1 otherwise).  The contexts are closed
 outside the timed windows.
+
+--device-input goes from padded torch device tensors to the polished inliers as a (pairs, n_max) bool device
+tensor: the host round trip against MultiContext.from_padded + run(polish=True) + padded_mask.  With --scores the
+input is a matcher's: the quality-sorted pairs of --sampler prosac with their columns permuted and a score per
+column that falls with the original rank.  Three pipelines are alternated: from_padded(scores=...) + run_prosac +
+padded_mask; from_padded + run + padded_mask; and torch.sort(stable=True) + gather + from_padded + run_prosac +
+padded_mask + the inverse permutation of the mask.  The first and the third must return equal masks and models
+(exit status 1 otherwise); the creation with and without scores is also timed alone.
 """
 import argparse
 import ctypes
@@ -755,6 +763,111 @@ def main_device(a, model, est, sets):
     return 0 if masks_equal and models_equal else 1
 
 
+def main_device_sorted(a, model, est, sets):
+    """--device-input --scores: a matcher's output -- matches in keypoint order and a score per keypoint -- as padded
+    device tensors in, the polished inliers as a (P, n_max) bool device tensor out, three ways, alternated,
+    host-timed, each ending synchronised.  S: from_padded(scores=...) + run_prosac + padded_mask.  U: from_padded +
+    run (uniform sampler) + padded_mask, the best without the scores.  T: torch.sort(stable=True) + gather +
+    from_padded + run_prosac + padded_mask + the inverse permutation of the mask, the caller's own reordering.
+    sets are quality-sorted pairs; every pair's columns are permuted and column j scores 1 - rank / n."""
+    import torch
+
+    P, n = len(sets), a.points
+    n_max = n + n // 4
+    rng = np.random.default_rng(17)
+    rows = np.zeros((P, n_max, 4), dtype=np.float32)
+    valid = np.zeros((P, n_max), dtype=bool)
+    scores = np.zeros((P, n_max), dtype=np.float32)
+    for p, pts in enumerate(sets):
+        cols = rng.permutation(n_max)[:len(pts)]  # rank i sits in column cols[i]: unsorted, with gaps
+        rows[p, cols] = pts
+        valid[p, cols] = True
+        scores[p, cols] = (1.0 - np.arange(len(pts)) / len(pts)).astype(np.float32)
+    dev = torch.device("cuda:0")
+    rows_t, valid_t, scores_t = (torch.from_numpy(x).to(dev) for x in (rows, valid, scores))
+    torch.cuda.synchronize()
+    pmodel = usac.Model(model.threshold, model.sample_size, model.desired_prob, 5, est, usac.SAMPLER.Prosac)
+    pmodel.max_iterations, pmodel.batch, pmodel.seed = model.max_iterations, model.batch, model.seed
+    pmodel.setDLTMode(model.dlt_mode)
+
+    def pipe_s():
+        mc = usac.MultiContext.from_padded(est, rows_t, valid=valid_t, scores=scores_t)
+        res = mc.run_prosac(pmodel, polish=True)
+        out = mc.padded_mask()
+        mc.close()
+        return out, res
+
+    def pipe_u():
+        mc = usac.MultiContext.from_padded(est, rows_t, valid=valid_t)
+        res = mc.run(model, polish=True)
+        out = mc.padded_mask()
+        mc.close()
+        return out, res
+
+    def pipe_t():
+        key = torch.where(valid_t, scores_t, torch.full_like(scores_t, float("-inf")))
+        perm = torch.sort(key, dim=1, descending=True, stable=True).indices
+        rows_s = torch.gather(rows_t, 1, perm[:, :, None].expand(-1, -1, 4)).contiguous()
+        valid_s = torch.gather(valid_t, 1, perm)
+        mc = usac.MultiContext.from_padded(est, rows_s, valid=valid_s)
+        res = mc.run_prosac(pmodel, polish=True)
+        sorted_mask = mc.padded_mask()
+        out = torch.zeros_like(sorted_mask).scatter_(1, perm, sorted_mask)
+        torch.cuda.synchronize()
+        mc.close()
+        return out, res
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        r = fn()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    for _ in range(a.warmup):
+        pipe_s(), pipe_u(), pipe_t()
+    ts, tu, tt, tcs, tcu = [], [], [], [], []
+    for _ in range(a.reps):
+        (mask_s, res_s), ms = timed(pipe_s)
+        ts.append(ms)
+        (mask_u, res_u), ms = timed(pipe_u)
+        tu.append(ms)
+        (mask_t, res_t), ms = timed(pipe_t)
+        tt.append(ms)
+        mc, ms = timed(lambda: usac.MultiContext.from_padded(est, rows_t, valid=valid_t, scores=scores_t))
+        tcs.append(ms)
+        mc.close()
+        mc, ms = timed(lambda: usac.MultiContext.from_padded(est, rows_t, valid=valid_t))
+        tcu.append(ms)
+        mc.close()
+    masks_equal = bool(torch.equal(mask_s, mask_t))
+    models_equal = same_bits([r["polished"] for r in res_s], [r["polished"] for r in res_t]) and \
+        same_bits([r["best"] for r in res_s], [r["best"] for r in res_t])
+
+    def summary(ms):
+        return {"min_ms": round(min(ms), 3), "median_ms": round(statistics.median(ms), 3), "max_ms": round(max(ms), 3)}
+
+    def outcome(res):
+        return {"mean_rounds": round(float(np.mean([r["rounds"] for r in res])), 2),
+                "mean_best_inliers": round(float(np.mean([r["best"]["inliers"] for r in res])), 2),
+                "mean_polished_inliers": round(float(np.mean([r["polished"]["inliers"] for r in res])), 2)}
+
+    line = {"bench": "multi_sorted", "estimator": a.estimator, "pairs": P, "points": n, "n_max": n_max, "round": a.R,
+            "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio, "dlt": a.dlt, "reps": a.reps,
+            "pipeline_s_scores_prosac": summary(ts), "pipeline_u_uniform": summary(tu),
+            "pipeline_t_torch_sort_prosac": summary(tt),
+            "ratio_u_over_s": round(statistics.median(tu) / statistics.median(ts), 2),
+            "ratio_t_over_s": round(statistics.median(tt) / statistics.median(ts), 2),
+            "creation_with_scores": summary(tcs), "creation_without_scores": summary(tcu),
+            "s": outcome(res_s), "u": outcome(res_u),
+            "masks_equal_s_t": masks_equal, "polished_models_bit_equal_s_t": bool(models_equal)}
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    return 0 if masks_equal and models_equal else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=512)
@@ -796,7 +909,13 @@ def main():
                     help="padded torch device tensors in, the polished inliers as a (pairs, n_max) bool device tensor "
                          "out: the host round trip (numpy sets, MultiContext, run, numpy mask, upload) against "
                          "MultiContext.from_padded + run(polish=True) + padded_mask; masks and models must be equal")
+    ap.add_argument("--scores", action="store_true",
+                    help="--device-input: unsorted columns with a score each (a matcher's output); from_padded(scores=) + "
+                         "run_prosac against from_padded + run and against torch.sort + gather + from_padded + run_prosac "
+                         "+ the inverse permutation; the first and the last must return equal masks and models")
     a = ap.parse_args()
+    if a.scores and not a.device_input:
+        ap.error("--scores goes with --device-input")
     if a.device_input and (a.pixels or a.sprt or a.lo or a.per_problem_thr or a.sampler != "uniform" or a.polish):
         ap.error("--device-input goes with --estimator alone")
     if a.pixels and (a.estimator != "essential" or a.sprt or a.lo or a.per_problem_thr or a.sampler != "uniform"):
@@ -816,7 +935,7 @@ def main():
     est = {"homography": usac.ESTIMATOR.Homography, "fundamental": usac.ESTIMATOR.Fundamental,
            "essential": usac.ESTIMATOR.Essential}[a.estimator]
     thr, prob = (0.002 if essential else 2.0), 0.95
-    sets = make_pairs(a.estimator, a.pairs, a.points, a.inlier_ratio, quality_sorted=a.sampler == "prosac",
+    sets = make_pairs(a.estimator, a.pairs, a.points, a.inlier_ratio, quality_sorted=a.sampler == "prosac" or a.scores,
                       cluster=a.cluster)
     model = usac.Model(thr, {"homography": 4, "fundamental": 7, "essential": 5}[a.estimator], prob, 5, est,
                        usac.SAMPLER.Uniform)
@@ -825,6 +944,8 @@ def main():
     seeds = [model.seed + p for p in range(a.pairs)]
     if a.pixels:
         return main_pixels(a, model)
+    if a.device_input and a.scores:
+        return main_device_sorted(a, model, est, sets)
     if a.device_input:
         return main_device(a, model, est, sets)
 
