@@ -229,6 +229,29 @@ struct PinnedAlloc {
 template <class T>
 using pinned_vector = std::vector<T, PinnedAlloc<T>>;
 
+// a pinned staging block (PinnedPool) that only grows
+struct PinBlock {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+
+// at least `need` bytes in a pinned block; growing it moves it, so its users take the pointer afterwards.
+// false: the allocation failed (the block is then empty)
+bool pin_grow(PinBlock &b, size_t need) {
+    if (need <= b.bytes) return true;
+    if (b.p) PinnedPool::get().give_back(b.p, b.bytes);
+    b.bytes = 0;
+    b.p = PinnedPool::get().take(need, &b.bytes);
+    return b.p != nullptr;
+}
+
+// the block back to the pool (usac_destroy, usac_multi_destroy: the owner's streams have drained)
+void pin_release(PinBlock &b) {
+    if (b.p) PinnedPool::get().give_back(b.p, b.bytes);
+    b.p = nullptr;
+    b.bytes = 0;
+}
+
 // Wait for a stream by polling it: the loop's host replay waits on the device dozens of
 // times per run (LO stages, batches, polish), and a blocking hipStreamSynchronize adds a wake-up
 // latency of ~20 us each time; polling returns within about a microsecond of completion.
@@ -317,19 +340,16 @@ struct usac_ctx {
     uint32_t spk = 1;       // model slots per hypothesis (3 for the 7-point solver)
     // single-model / polish buffers
     DevBuf one_model, inl_idx, inl_cnt, inl_sum, inl_scratch, q, partial, ws, nm_model, nm_ok;
-    uint32_t *grid_pin = nullptr;    // pinned words the grid build reads its two counts into
-    size_t grid_pin_bytes = 0;
+    PinBlock grid_pin;               // pinned words the grid build reads its two counts into
     DevBuf pol_res;                  // polish pass results (usac_kernels.h kPol*: per pass model, ok, count, sum)
     DevBuf pol_lists;                // the polish passes' inlier lists (4 x n)
-    void *pol_pin = nullptr;         // their pinned host copy (PinnedPool)
-    size_t pol_pin_bytes = 0;
+    PinBlock pol_pin;                // their pinned host copy (PinnedPool)
     DevBuf nm_seq;          // normalisation scratch of the non-minimal fits (polish and LO)
     DevBuf nm_w, nm_qw;     // usac_lsq_fit with weights: the weights, the weighted points
     DevBuf lo_io;           // one LO stage's inputs (two blocks, alternating) and outputs
     // the LO stages' Σerr passes run on their own stream beside the next stage's fit
     hipStream_t lo_stream = nullptr;
-    void *rec_pin = nullptr;  // usac_fetch_best's pinned staging (a pageable D2H copy is staged by the runtime)
-    size_t rec_pin_bytes = 0;
+    PinBlock rec_pin;  // usac_fetch_best's pinned staging (a pageable D2H copy is staged by the runtime)
     // the loop's next batch drawn and run ahead of the current batch's replay (usac_ransac_run)
     hipStream_t spec_stream = nullptr;
     hipEvent_t spec_ev = nullptr;
@@ -340,15 +360,14 @@ struct usac_ctx {
     int nranks = 1, rank = 0;
     DevBuf rec_send, rec_all;
     DevBuf x_send, x_recv;  // sharded-run all-gather buffers (RCCL path, device-packed)
-    void *x_pin = nullptr;  // their pinned host copy (the replay's counts / model words)
-    size_t x_pin_bytes = 0;
+    PinBlock x_pin;         // their pinned host copy (the replay's counts / model words)
     // batch-best exchange (usac_exchange_best_async / _wait): a dedicated stream ordered after
     // each batch by an event, a ring of in-flight all-gathers (device + pinned host records)
     hipStream_t xstream = nullptr;
     hipEvent_t xev_batch[USAC_XRING] = {}, xev_done[USAC_XRING] = {};
     DevBuf xring;
-    usac_record *xring_host = nullptr;
-    size_t xring_host_bytes = 0;
+    PinBlock xring_host;    // the ring's pinned host records
+    usac_record *xring_records() const { return static_cast<usac_record *>(xring_host.p); }
     // collectives on one communicator must run in one order on every rank: the two streams
     // that issue them are ordered by events -- a collective on `stream` waits for the last
     // exchange (x_last), an exchange waits for the last collective on `stream` (coll_ev)
@@ -532,15 +551,14 @@ int ensure_grid(usac_ctx *c, int cs) {
     c->grid_cs = 0;
     c->grid_gen++;
     if (!packable) return host_grid(c, cs);
-    if (!c->grid_pin && !(c->grid_pin = static_cast<uint32_t *>(PinnedPool::get().take(64, &c->grid_pin_bytes))))
-        return fail(c, USAC_ERR_HIP, "pinned host allocation failed");
+    if (!pin_grow(c->grid_pin, 64)) return fail(c, USAC_ERR_HIP, "pinned host allocation failed");
     HIP_TRY(c, c->grid_ws.reserve(usac::grid_workspace_bytes(c->n)));
     c->grid_cs = 0;
     c->grid_gen++;
     HIP_TRY(c, usac::build_grid(c->stream, c->pts.as<float4>(), c->n, cs, make_int4(lo[0], lo[1], lo[2], lo[3]),
                                 make_int4(bits[0], bits[1], bits[2], bits[3]), c->m, c->grid_ws.p,
                                 c->grid_cell(), c->grid_rank(), c->grid_start(), c->grid_members(),
-                                c->grid_elig.as<int32_t>(), c->grid_pin,
+                                c->grid_elig.as<int32_t>(), static_cast<uint32_t *>(c->grid_pin.p),
                                 &c->grid_n_cells, &c->grid_n_elig));
     c->grid_cs = cs;
     c->grid_gen++;
@@ -1815,9 +1833,7 @@ void usac_destroy(usac_ctx *c) {
     if (c->lo_stream) (void)hipStreamSynchronize(c->lo_stream);
     if (c->spec_stream) (void)hipStreamSynchronize(c->spec_stream);
     if (c->comm) ncclCommDestroy(c->comm);
-    if (c->pol_pin) PinnedPool::get().give_back(c->pol_pin, c->pol_pin_bytes);
-    if (c->x_pin) PinnedPool::get().give_back(c->x_pin, c->x_pin_bytes);
-    if (c->xring_host) PinnedPool::get().give_back(c->xring_host, c->xring_host_bytes);
+    for (PinBlock *b : {&c->pol_pin, &c->x_pin, &c->xring_host, &c->rec_pin, &c->grid_pin}) pin_release(*b);
     for (int k = 0; k < USAC_XRING; k++) {
         if (c->xev_batch[k]) StreamPool::get().give_back(c->xev_batch[k]);
         if (c->xev_done[k]) StreamPool::get().give_back(c->xev_done[k]);
@@ -1827,10 +1843,8 @@ void usac_destroy(usac_ctx *c) {
     for (auto &ev : c->lo_ev)
         if (ev) StreamPool::get().give_back(ev);
     if (c->lo_stream) StreamPool::get().give_back(c->lo_stream);
-    if (c->rec_pin) PinnedPool::get().give_back(c->rec_pin, c->rec_pin_bytes);
     if (c->spec_ev) StreamPool::get().give_back(c->spec_ev);
     if (c->spec_stream) StreamPool::get().give_back(c->spec_stream);
-    if (c->grid_pin) PinnedPool::get().give_back(c->grid_pin, c->grid_pin_bytes);
     for (DevBuf *b : {&c->pts, &c->rec, &c->perm, &c->samples, &c->models, &c->counts, &c->sums, &c->best, &c->hostmodels,
                       &c->argmax_part, &c->list, &c->list_n, &c->h4_fb, &c->h4_fb_n, &c->pool_idx, &c->pool_pts, &c->masks, &c->sprt_pts,
                       &c->sprt_tested, &c->sprt_surv, &c->sprt_surv_n, &c->sprt_starts, &c->inl_scratch, &c->e5_ws, &c->one_model,
@@ -2155,11 +2169,11 @@ int usac_last_counts(usac_ctx *c, int32_t *counts, float *sums, uint32_t n) {
 
 int usac_fetch_best(usac_ctx *c, usac_record *best) {
     if (!c || !best) return USAC_ERR_ARG;
-    if (!c->rec_pin && !(c->rec_pin = PinnedPool::get().take(sizeof(usac_record), &c->rec_pin_bytes)))
+    if (!pin_grow(c->rec_pin, sizeof(usac_record)))
         return fail(c, USAC_ERR_HIP, "pinned host allocation failed");
-    HIP_TRY(c, hipMemcpyAsync(c->rec_pin, c->best.p, sizeof(usac_record), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->rec_pin.p, c->best.p, sizeof(usac_record), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, stream_wait(c->stream));
-    memcpy(best, c->rec_pin, sizeof(usac_record));
+    memcpy(best, c->rec_pin.p, sizeof(usac_record));
     return USAC_OK;
 }
 
@@ -2446,14 +2460,7 @@ static int sharded_batch(usac_ctx *c, const int32_t *hs, uint32_t B, uint32_t it
     } else {
         HIP_TRY(c, c->x_send.reserve(bytes));
         HIP_TRY(c, c->x_recv.reserve(bytes * (size_t)nranks));
-        if (c->x_pin_bytes < bytes * (size_t)nranks) {
-            if (c->x_pin) PinnedPool::get().give_back(c->x_pin, c->x_pin_bytes);
-            c->x_pin = PinnedPool::get().take(bytes * (size_t)nranks, &c->x_pin_bytes);
-            if (!c->x_pin) {
-                c->x_pin_bytes = 0;
-                return fail(c, USAC_ERR_HIP, "pinned host allocation failed");
-            }
-        }
+        if (!pin_grow(c->x_pin, bytes * (size_t)nranks)) return fail(c, USAC_ERR_HIP, "pinned host allocation failed");
         HIP_TRY(c, usac::launch_pack_slice(c->stream, c->counts.as<int32_t>(), c->models.as<float>(),
                                            status == USAC_OK ? (uint32_t)Ss : 0u, (uint32_t)Ps, nc, status,
                                            c->x_send.as<int32_t>()));
@@ -2461,9 +2468,9 @@ static int sharded_batch(usac_ctx *c, const int32_t *hs, uint32_t B, uint32_t it
         HIP_TRY(c, order_after_exchanges(c));
         NCCL_TRY(c, ncclAllGather(c->x_send.p, c->x_recv.p, bytes, ncclUint8, c->comm, c->stream));
         HIP_TRY(c, mark_collective(c));
-        HIP_TRY(c, hipMemcpyAsync(c->x_pin, c->x_recv.p, bytes * (size_t)nranks, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->x_pin.p, c->x_recv.p, bytes * (size_t)nranks, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, stream_wait(c->stream));
-        recv = static_cast<const uint8_t *>(c->x_pin);
+        recv = static_cast<const uint8_t *>(c->x_pin.p);
     }
     for (int r = 0; r < nranks; r++) {
         const int32_t st = *reinterpret_cast<const int32_t *>(recv + (size_t)r * bytes);
@@ -2487,48 +2494,208 @@ static int sharded_batch(usac_ctx *c, const int32_t *hs, uint32_t B, uint32_t it
     return USAC_OK;
 }
 
-// Ransac::run with each batch's hypotheses sharded over nranks (SURVEY §8(e)): every rank
-// draws the same host sample stream, solves and scores only its contiguous slice of the
-// batch, and the slices' per-slot counts and models are all-gathered (gather(), or RCCL on
-// the context's communicator when gather is null); the replay -- records, termination, LO,
-// polish -- then runs on the merged batch identically on every rank (ransac.cpp:58-139 order).
-static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int rank, usac_allgather_fn gather,
-                           void *gather_user, usac_run_output *out, int32_t *inliers_out, usac_record *records,
-                           uint32_t rec_cap) {
-    if (!c || !prm || !out || nranks < 1 || rank < 0 || rank >= nranks) return USAC_ERR_ARG;
-    memset(out, 0, sizeof(*out));
+namespace {
+
+// The state of one Ransac::run and its stages, in the order ransac_run_impl calls them.  The members are
+// declared in the order the run builds them, so they are destroyed in the reverse of it: the pinned
+// staging vectors before lo (whose destructor drains the LO streams), lo before the samplers' generator.
+// Guards: the destructor body -- which runs before any member goes -- waits for a speculative batch
+// still copying into hs2 / hc2 / hmod2; the two guards that put c->h16_off, c->dlt_mode and c->sprt_on
+// back are locals of ransac_run_impl, declared before the RansacRun, so they act after it on every exit.
+struct RansacRun {
+    usac_ctx *const c;
+    const usac_params *const prm;
+    const int nranks, rank;
+    const usac_allgather_fn gather;
+    void *const gather_user;
+    usac_run_output *const out;
+    int32_t *const inliers_out;
+    usac_record *const records;
+    const uint32_t rec_cap;
+
+    // the parameter checks' flags
+    bool prosac = false, napsac = false, knn_mode = false, use_lo = false, use_gc = false, gc_knn = false;
+
+    std::chrono::steady_clock::time_point t0;
+    // wall-time split of the run, printed to stderr when USAC_PROFILE is set
+    enum { T_SETUP, T_DRAW, T_DEVICE, T_SUMS, T_REPLAY, T_LO, T_POLISH, T_N };
+    double tsplit[T_N] = {0, 0, 0, 0, 0, 0, 0};
+    double t_verify = 0.0, t_drawonly = 0.0;  // USAC_PROFILE detail: host SPRT walks, sample draws
+    std::chrono::steady_clock::time_point tmark;
+    // sub-split of the setup (USAC_PROFILE): buffers, neighbours, LO / GC reservations
+    double tsub[3] = {0, 0, 0};
+
+    const uint32_t batch;
+    const uint32_t n, m, spk;
+    const float thr;
+
+    usac::GlibcRandom grng;
+    std::unique_ptr<usac::UniformSampler> uni;
+    std::unique_ptr<usac::ProsacSampler> pro;
+    std::unique_ptr<usac::ProsacTerminationCriteria> pterm;
+    std::shared_ptr<const usac::GridNeighbors> grid;
+    std::unique_ptr<usac::NapsacSampler> nap;
+    std::unique_ptr<usac::NapsacKnnSampler> napk;
+    std::vector<int32_t> knn_tab;
+    std::unique_ptr<LoRansac> lo;
+    std::unique_ptr<GcLo> gc;
+    usac::StandardTerminationCriteria term;
+    std::unique_ptr<usac::Sprt> sprt;
+    const int max_before;
+    const uint32_t nw;
+    bool defer_pool = false;
+
+    const size_t SB;            // slot stride of the host copies
+    std::vector<uint8_t> xbuf;  // sharded runs: all-gather send + receive buffers
+    pinned_vector<int32_t> hs, hc;
+    std::vector<int32_t> slot_row;
+    std::vector<float> hsum;
+    pinned_vector<float> hmod;
+    pinned_vector<uint32_t> hlist;  // the SPRT batch's occupied-slot list, its count at [SB]
+    pinned_vector<uint32_t> hmask;  // words, PoolTail
+    std::vector<uint32_t> subset_at, largest_at;
+    std::vector<int32_t> last_sample;
+    bool spec_ok = false;
+    pinned_vector<int32_t> hs2, hc2;
+    pinned_vector<float> hmod2;
+    std::vector<int32_t> spec_last;
+    bool spec = false;          // a speculative batch is on the spec stream
+    uint32_t spec_B = 0;        // its size
+    uint32_t sampler_keep = 0;  // > 0: roll the sampler back and redraw this many samples
+    pinned_vector<int32_t> inl_list;
+    usac::Score best;
+    float best_model[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t iters = 0, max_iters;
+    int32_t nrec = 0;
+    // exact inliers of a model on the device -> (cnt, s) and c->inl_idx
+    int32_t cnt = 0;
+    float s = 0.f;
+    bool mask_list = false, mask_check = false;
+    std::vector<uint64_t> pt_bits;
+    uint32_t cap = 0;
+
+    // this batch
+    uint32_t B = 0;
+    bool have = false;  // this batch's device results are already on the host (speculation)
+    size_t spec_hst = 0;
+    std::unique_ptr<usac::ProsacSampler> snapshot;
+    uint32_t gen_term = 0;
+    size_t S = 0;
+    size_t hst = 0;            // host stride of hmod's components this batch
+    uint32_t rows = 0;
+    uint32_t mask_stride = 0;  // host row stride of hmask (SPRT)
+
+    // the polish: its passes, and what it leaves for emit() -- best_model's own inlier list on the device
+    static constexpr int kPasses = 4;
+    int32_t *cur = nullptr;
+    int32_t cur_cnt = 0;
+
+    RansacRun(usac_ctx *c_, const usac_params *prm_, int nranks_, int rank_, usac_allgather_fn gather_, void *gather_user_,
+              usac_run_output *out_, int32_t *inliers_out_, usac_record *records_, uint32_t rec_cap_)
+        : c(c_),
+          prm(prm_),
+          nranks(nranks_),
+          rank(rank_),
+          gather(gather_),
+          gather_user(gather_user_),
+          out(out_),
+          inliers_out(inliers_out_),
+          records(records_),
+          rec_cap(rec_cap_),
+          batch(prm->batch ? prm->batch : (prm->sprt ? 1024u : kDefaultBatch)),
+          n(c->n),
+          m(c->m),
+          spk(c->spk),
+          thr(prm->threshold),
+          grng(prm->seed),
+          term(prm->desired_prob, m, n, prm->max_iterations),
+          max_before(max_before_sprt(prm)),
+          nw((n + 31) / 32),
+          SB((size_t)batch * spk),
+          max_iters(prm->max_iterations) {}
+    // every exit waits for a speculative batch still copying into hs2 / hc2 / hmod2
+    ~RansacRun() {
+        if (spec) (void)hipStreamSynchronize(c->spec_stream);
+    }
+
+    void lap(int k) {
+        const auto t = std::chrono::steady_clock::now();
+        tsplit[k] += std::chrono::duration<double, std::milli>(t - tmark).count();
+        tmark = t;
+    }
+    void sub(int k) {
+        const auto t = std::chrono::steady_clock::now();
+        tsub[k] = std::chrono::duration<double, std::milli>(t - tmark).count();
+    }
+    void sampler_mark() {
+        if (nap) nap->mark();
+        else uni->mark();
+    }
+    void sampler_commit() {
+        if (nap) nap->commit();
+        else uni->commit();
+    }
+    void sampler_rollback() {
+        if (nap) nap->rollback();
+        else uni->rollback();
+    }
+
+    int check_params();
+    int begin();
+    int pool_upload();
+    int construct();
+    int host_buffers();
+    int score_inliers(const float *model_host, int32_t *list_pin = nullptr);
+    int32_t mask_inliers(const uint32_t *row, size_t stride, int32_t *list);
+    void draw_into(int32_t *buf, uint32_t count, usac::ProsacSampler *pro_, uint32_t term_len);
+    void settle_sampler();
+    hipError_t spec_wait();
+    int take_speculation();
+    void draw();
+    int one_rank_batch();
+    int device_batch();
+    int speculate_next();
+    int sums();
+    int replay();
+    void lo_counters();
+    int finish();
+    void polish_replay(int k0, int k1, const float *hres, int32_t *const *lists, int &prev, bool &stop);
+    int polish_fused_profile(int k_first);
+    int polish_pass(int k, float *dres, int32_t *dres_i, int32_t *const *lists, bool finish_score);
+    int polish();
+    int emit();
+};
+
+// 1. Parameter checks.  Reads prm and the context's shape; leaves the sampler / LO flags, and c->h16_off
+// set for the loop.
+int RansacRun::check_params() {
     // The loop scores homographies with k_score_hf, not the matrix-core scorer: its batches are
     // small (the ramp; h16's per-batch rows + finish launches cost more than they save: cfg5 3.30 ms
     // per run with k_score_hf, 3.8-3.9 with h16).  USAC_LOOP_H16=1 lets the loop use it (tests: the
     // round-5 miscount beside the speculative h16 batch was packed-fp32 VALU corruption beside MFMA
     // waves, gone since the library issues no packed fp32 instruction -- usac_pk.hpp).
-    struct H16Off {
-        usac_ctx *c;
-        bool saved;
-        ~H16Off() { c->h16_off = saved; }
-    } h16_off{c, c->h16_off};
     const bool loop_h16 = getenv("USAC_LOOP_H16") && atoi(getenv("USAC_LOOP_H16")) != 0;
     c->h16_off = !loop_h16;
     if (nranks > 1 && !gather && (!c->comm || c->nranks != nranks || c->rank != rank))
         return fail(c, USAC_ERR_ARG, "sharded run without a gather callback needs usac_comm_init(nranks, rank)");
-    const bool prosac = prm->sampler == USAC_SAMPLER_PROSAC;
-    const bool napsac = prm->sampler == USAC_SAMPLER_NAPSAC;
+    prosac = prm->sampler == USAC_SAMPLER_PROSAC;
+    napsac = prm->sampler == USAC_SAMPLER_NAPSAC;
     if (!prosac && !napsac && prm->sampler != USAC_SAMPLER_UNIFORM && prm->sampler != 0)
         return fail(c, USAC_ERR_UNSUPPORTED, "sampler not supported (Uniform, Napsac, Prosac)");
-    const bool knn_mode = napsac && prm->neighbors != USAC_NEIGHBORS_GRID;  // ransac.hpp:62-78
+    knn_mode = napsac && prm->neighbors != USAC_NEIGHBORS_GRID;  // ransac.hpp:62-78
     if (napsac && !knn_mode && c->cols != 4)
         return fail(c, USAC_ERR_ARG, "NAPSAC grid neighbours need 4-column points (SURVEY Q17)");
     if (napsac && !knn_mode && prm->cell_size <= 0) return fail(c, USAC_ERR_ARG, "NAPSAC cell_size must be > 0");
     if (knn_mode && (prm->knn == 0 || prm->knn > usac::kKnnMax || prm->knn + 1 < c->m))
         return fail(c, USAC_ERR_ARG, "NAPSAC KNN: k_nearest_neighbors must be in [sample_size - 1, 32] "
                                      "(napsac_sampler.hpp:48)");
-    const bool use_lo = prm->lo == USAC_LO_INITLORSC || prm->lo == USAC_LO_INITFLORSC;
-    const bool use_gc = prm->lo == USAC_LO_GC;
+    use_lo = prm->lo == USAC_LO_INITLORSC || prm->lo == USAC_LO_INITFLORSC;
+    use_gc = prm->lo == USAC_LO_GC;
     if (prm->lo != USAC_LO_NONE && !use_lo && !use_gc)
         return fail(c, USAC_ERR_UNSUPPORTED, "LO: InItLORsc / InItFLORsc / GC only");
     if (use_gc && napsac)  // ransac.hpp:62-78 gives the neighbours to the sampler only: GC's are unset
         return fail(c, USAC_ERR_UNSUPPORTED, "NAPSAC + GC: the reference leaves the graph cut without neighbours");
-    const bool gc_knn = use_gc && prm->neighbors != USAC_NEIGHBORS_GRID;
+    gc_knn = use_gc && prm->neighbors != USAC_NEIGHBORS_GRID;
     if (use_gc && !gc_knn && (c->cols != 4 || prm->cell_size <= 0))
         return fail(c, USAC_ERR_ARG, "GC grid neighbours need 4-column points and cell_size > 0");
     if (gc_knn && (prm->knn == 0 || prm->knn > usac::kKnnMax))
@@ -2538,57 +2705,42 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
     if (prosac && c->n <= 20) return fail(c, USAC_ERR_ARG, "PROSAC needs > 20 points (prosac_termination_criteria.hpp:158-163)");
     if (prosac && prm->max_iterations > usac::ProsacSampler::kGrowthMax)
         return fail(c, USAC_ERR_ARG, "PROSAC max_iterations > 200000 (reference draws outside the point range)");
-    const auto t0 = std::chrono::steady_clock::now();
-    // wall-time split of the run, printed to stderr when USAC_PROFILE is set
-    enum { T_SETUP, T_DRAW, T_DEVICE, T_SUMS, T_REPLAY, T_LO, T_POLISH, T_N };
-    double tsplit[T_N] = {0, 0, 0, 0, 0, 0, 0};
-    double t_verify = 0.0, t_drawonly = 0.0;  // USAC_PROFILE detail: host SPRT walks, sample draws
-    auto tmark = std::chrono::steady_clock::now();
-    auto lap = [&](int k) {
-        const auto t = std::chrono::steady_clock::now();
-        tsplit[k] += std::chrono::duration<double, std::milli>(t - tmark).count();
-        tmark = t;
-    };
+    return USAC_OK;
+}
+
+// The context for the run: its device, the batch and single-model buffers, the run's DLT mode, the batch
+// SPRT off.  Leaves t0 / tmark started.
+int RansacRun::begin() {
+    t0 = std::chrono::steady_clock::now();
+    tmark = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->device));
     c->batch_valid = false;  // the run's batches, LO and polish reuse the batch buffers
-    const uint32_t batch = prm->batch ? prm->batch : (prm->sprt ? 1024u : kDefaultBatch);
     int rc = ensure_batch(c, batch);
     if (rc) return rc;
     rc = ensure_single(c);
     if (rc) return rc;
-    // sub-split of the setup (USAC_PROFILE): buffers, neighbours, LO / GC reservations
-    double tsub[3] = {0, 0, 0};
-    auto sub = [&](int k) {
-        const auto t = std::chrono::steady_clock::now();
-        tsub[k] = std::chrono::duration<double, std::milli>(t - tmark).count();
-    };
     sub(0);
-    const int saved_mode = c->dlt_mode;
     c->dlt_mode = prm->dlt_mode;
-    const bool saved_sprt = c->sprt_on;  // the replay verifies exactly; the batch test is off
-    c->sprt_on = false;
-    struct Restore {
-        usac_ctx *c;
-        int mode;
-        bool sprt;
-        ~Restore() {
-            c->dlt_mode = mode;
-            c->sprt_on = sprt;
-        }
-    } restore{c, saved_mode, saved_sprt};
-    const uint32_t n = c->n, m = c->m, spk = c->spk;
-    const float thr = prm->threshold;
+    c->sprt_on = false;  // the replay verifies exactly; the batch test is off
+    return USAC_OK;
+}
 
+// the SPRT pool shuffled (n glibc draws) and the pool-ordered points on the device
+int RansacRun::pool_upload() {
+    sprt->shuffle_pool();
+    HIP_TRY(c, hipMemcpyAsync(c->pool_idx.p, sprt->pool().data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice,
+                              c->stream));
+    HIP_TRY(c, usac::launch_gather_points(c->stream, c->pts.p, c->cols, c->pool_idx.as<uint32_t>(), n,
+                                          c->pool_pts.p));
+    return USAC_OK;
+}
+
+// 2. Construction, in the reference's order.  Reads the flags; leaves the sampler, the termination
+// criteria, the neighbours, lo / gc (reserved), the exact-sum buffers, sprt and its pool.
+int RansacRun::construct() {
+    int rc;
     // Ransac ctor order (ransac.hpp:41-93): sampler, termination criteria, then SPRT -- the
     // SPRT pool shuffle draws n values of the glibc stream before the Uniform sampler's first.
-    usac::GlibcRandom grng(prm->seed);
-    std::unique_ptr<usac::UniformSampler> uni;
-    std::unique_ptr<usac::ProsacSampler> pro;
-    std::unique_ptr<usac::ProsacTerminationCriteria> pterm;
-    std::shared_ptr<const usac::GridNeighbors> grid;
-    std::unique_ptr<usac::NapsacSampler> nap;
-    std::unique_ptr<usac::NapsacKnnSampler> napk;
-    std::vector<int32_t> knn_tab;
     if (prosac) {
         pro.reset(new usac::ProsacSampler(prm->seed, n, m));
         pterm.reset(new usac::ProsacTerminationCriteria(pro->growth(), prm->desired_prob, m, n, prm->max_iterations));
@@ -2603,7 +2755,6 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
         uni.reset(new usac::UniformSampler(grng, n, m));
     }
     sub(1);
-    std::unique_ptr<LoRansac> lo;
     if (use_lo) {
         Shard shard;
         shard.nranks = nranks;
@@ -2613,7 +2764,6 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
         lo.reset(new LoRansac(c, prm, shard));
         if ((rc = lo->reserve())) return rc;
     }
-    std::unique_ptr<GcLo> gc;
     if (use_gc) {  // Ransac ctor neighbours for the graph cut (ransac.hpp:60-78)
         if (gc_knn) {
             knn_tab.resize((size_t)n * prm->knn);
@@ -2626,21 +2776,9 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
     }
     if (!prm->sprt && (rc = reserve_exact_sums(c))) return rc;
     sub(2);
-    usac::StandardTerminationCriteria term(prm->desired_prob, m, n, prm->max_iterations);
-    std::unique_ptr<usac::Sprt> sprt;
-    const int max_before = max_before_sprt(prm);
-    const uint32_t nw = (n + 31) / 32;
     // PROSAC + SPRT on one rank: the pool shuffle (n glibc draws, the sampler has its own
     // generator) runs after the first batch's solve is enqueued, overlapping it (pool_upload)
-    const bool defer_pool = prm->sprt && prosac && nranks == 1 && !getenv("USAC_NO_DEFER_POOL");
-    auto pool_upload = [&]() -> int {
-        sprt->shuffle_pool();
-        HIP_TRY(c, hipMemcpyAsync(c->pool_idx.p, sprt->pool().data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice,
-                                  c->stream));
-        HIP_TRY(c, usac::launch_gather_points(c->stream, c->pts.p, c->cols, c->pool_idx.as<uint32_t>(), n,
-                                              c->pool_pts.p));
-        return USAC_OK;
-    };
+    defer_pool = prm->sprt && prosac && nranks == 1 && !getenv("USAC_NO_DEFER_POOL");
     if (prm->sprt) {
         sprt.reset(new usac::Sprt(grng, c->estimator, n, m, prm->max_iterations, max_before_sprt(prm), defer_pool));
         HIP_TRY(c, c->pool_idx.reserve(sizeof(uint32_t) * n));
@@ -2649,30 +2787,34 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
         HIP_TRY(c, c->masks.reserve(sizeof(uint32_t) * ((size_t)nw + 2 + (size_t)ncomp(c)) * batch * spk + 4));
         if (!defer_pool && (rc = pool_upload())) return rc;
     }
+    return USAC_OK;
+}
 
-    const size_t SB = (size_t)batch * spk;  // slot stride of the host copies
-    std::vector<uint8_t> xbuf;               // sharded runs: all-gather send + receive buffers
-    pinned_vector<int32_t> hs((size_t)batch * m, 0), hc(SB);
-    std::vector<int32_t> slot_row(SB);
-    std::vector<float> hsum(SB);
-    pinned_vector<float> hmod((size_t)ncomp(c) * SB);
-    pinned_vector<uint32_t> hlist(SB + 1);  // the SPRT batch's occupied-slot list, its count at [SB]
-    pinned_vector<uint32_t> hmask(sprt ? ((size_t)nw + 2 + (size_t)ncomp(c)) * SB + 4 : 0);  // words, PoolTail
-    std::vector<uint32_t> subset_at(batch), largest_at(batch);
-    std::vector<int32_t> last_sample(m, 0);
+// 3. Host buffers and speculation state.  Reads batch, the samplers and sprt; leaves the pinned host copies
+// sized for a whole batch, spec_ok with its stream, event and reservations, the polish result block and
+// its pinned copy, mask_list / mask_check, and the first batch's cap.
+int RansacRun::host_buffers() {
+    hs.assign((size_t)batch * m, 0);
+    hc.resize(SB);
+    slot_row.resize(SB);
+    hsum.resize(SB);
+    hmod.resize((size_t)ncomp(c) * SB);
+    hlist.resize(SB + 1);
+    hmask.resize(sprt ? ((size_t)nw + 2 + (size_t)ncomp(c)) * SB + 4 : 0);
+    subset_at.resize(batch);
+    largest_at.resize(batch);
+    last_sample.assign(m, 0);
     // Speculation: the next batch is drawn and solved / scored on its own stream while the
     // current batch is replayed (its LO fits run meanwhile).  Its size assumes the replay
     // leaves max_iterations alone; a smaller actual batch takes the prefix of its results (the
     // same samples, the same kernels per hypothesis), and the sampler's extra draws are undone
     // (journal rollback, then a redraw of the kept prefix) before the sampler is used again.
     // Uniform / NAPSAC-grid without SPRT on one rank only (PROSAC's draws depend on the replay).
-    const bool spec_ok = !prosac && !prm->sprt && nranks == 1 && !napk && (nap || uni) && !getenv("USAC_NO_SPECULATION");
-    pinned_vector<int32_t> hs2(spec_ok ? (size_t)batch * m : 0), hc2(spec_ok ? SB : 0);
-    pinned_vector<float> hmod2(spec_ok ? (size_t)ncomp(c) * SB : 0);
-    std::vector<int32_t> spec_last(m, 0);
-    bool spec = false;          // a speculative batch is on the spec stream
-    uint32_t spec_B = 0;        // its size
-    uint32_t sampler_keep = 0;  // > 0: roll the sampler back and redraw this many samples
+    spec_ok = !prosac && !prm->sprt && nranks == 1 && !napk && (nap || uni) && !getenv("USAC_NO_SPECULATION");
+    hs2.resize(spec_ok ? (size_t)batch * m : 0);
+    hc2.resize(spec_ok ? SB : 0);
+    hmod2.resize(spec_ok ? (size_t)ncomp(c) * SB : 0);
+    spec_last.assign(m, 0);
     if (spec_ok) {
         if (!c->spec_stream) HIP_TRY(c, StreamPool::get().stream(&c->spec_stream));
         if (!c->spec_ev) HIP_TRY(c, StreamPool::get().event(&c->spec_ev));
@@ -2683,58 +2825,12 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
         if (listed(c)) HIP_TRY(c, c->tv_part.reserve(usac::tv_scratch_bytes(batch * c->spk, c->chunks)));
         if (is_e(c)) HIP_TRY(c, c->e5_ws.reserve(usac::e5_workspace_bytes(batch)));
     }
-    // every exit waits for a speculative batch still copying into hs2 / hc2 / hmod2
-    struct SpecDrain {
-        usac_ctx *c;
-        const bool &pending;
-        ~SpecDrain() {
-            if (pending) (void)hipStreamSynchronize(c->spec_stream);
-        }
-    } spec_drain{c, spec};
-    auto sampler_mark = [&]() {
-        if (nap) nap->mark();
-        else uni->mark();
-    };
-    auto sampler_commit = [&]() {
-        if (nap) nap->commit();
-        else uni->commit();
-    };
-    auto sampler_rollback = [&]() {
-        if (nap) nap->rollback();
-        else uni->rollback();
-    };
-    pinned_vector<int32_t> inl_list(prosac ? n : 0);
-    usac::Score best;
-    float best_model[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t iters = 0, max_iters = prm->max_iterations;
-    int32_t nrec = 0;
+    inl_list.resize(prosac ? n : 0);
 
-    // exact inliers of a model on the device -> (cnt, s) and c->inl_idx
-    int32_t cnt = 0, ok = 0;
-    float s = 0.f;
     // (count, sum) of a host model through one pinned D2H (polish result block, slots 12-13)
     HIP_TRY(c, c->pol_res.reserve(sizeof(float) * usac::kPolWords));
-    if (!c->pol_pin && !(c->pol_pin = PinnedPool::get().take(sizeof(float) * usac::kPolWords, &c->pol_pin_bytes)))
+    if (!pin_grow(c->pol_pin, sizeof(float) * usac::kPolWords))
         return fail(c, USAC_ERR_HIP, "pinned host allocation failed");
-    // list_pin (nullable): the whole n-word inlier list copied in the same submission (its
-    // first cnt words are the list) -- one host wait instead of a second, synchronous copy
-    auto score_inliers = [&](const float *model_host, int32_t *list_pin = nullptr) -> int {
-        float *dres = c->pol_res.as<float>();
-        HIP_TRY(c, hipMemcpyAsync(c->one_model.p, model_host, sizeof(float) * 9, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, c->inl_scratch.reserve(usac::inliers_scratch_bytes(c->n, 1)));
-        HIP_TRY(c, usac::launch_inliers_batch(c->stream, c->estimator, c->pts.p, c->n, c->one_model.as<float>(), 1, thr,
-                                              nullptr, nullptr, c->inl_idx.as<int32_t>(), 0,
-                                              reinterpret_cast<int32_t *>(dres + 12), dres + 13, c->inl_scratch.p));
-        HIP_TRY(c, hipMemcpyAsync(static_cast<float *>(c->pol_pin) + 12, dres + 12, sizeof(float) * 2,
-                                  hipMemcpyDeviceToHost, c->stream));
-        if (list_pin)
-            HIP_TRY(c, hipMemcpyAsync(list_pin, c->inl_idx.p, sizeof(int32_t) * (size_t)c->n, hipMemcpyDeviceToHost,
-                                      c->stream));
-        HIP_TRY(c, stream_wait(c->stream));
-        memcpy(&cnt, static_cast<const float *>(c->pol_pin) + 12, sizeof(int32_t));
-        memcpy(&s, static_cast<const float *>(c->pol_pin) + 13, sizeof(float));
-        return USAC_OK;
-    };
 
     // PROSAC + SPRT: a new best's inlier list (getUpBoundIterationsSorted's input) decoded from its
     // pool-order mask row on the host instead of a device getInliers round trip per update.  An
@@ -2742,23 +2838,9 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
     // model it keeps), and k_pool_mask evaluates the same residual (no contraction: Makefile) on
     // copies of the same points with the same model words -- except H, whose mask uses the
     // solver's H^-1 where getInliers inverts on the device.  USAC_CHECK_MASK_LIST=1 compares both.
-    const bool mask_list = prosac && sprt && c->estimator != USAC_HOMOGRAPHY && !getenv("USAC_DEVICE_INLIERS");
-    const bool mask_check = mask_list && getenv("USAC_CHECK_MASK_LIST");
-    std::vector<uint64_t> pt_bits(mask_list ? ((size_t)n + 63) / 64 : 0);
-    auto mask_inliers = [&](const uint32_t *row, size_t stride, int32_t *list) -> int32_t {
-        std::fill(pt_bits.begin(), pt_bits.end(), 0);
-        const uint32_t *pool = sprt->pool().data();
-        for (uint32_t w = 0; w < nw; w++)
-            for (uint32_t bits = row[(size_t)w * stride]; bits; bits &= bits - 1) {
-                const uint32_t p = pool[32 * w + (uint32_t)__builtin_ctz(bits)];
-                pt_bits[p >> 6] |= 1ull << (p & 63);
-            }
-        int32_t k = 0;
-        for (size_t w = 0; w < pt_bits.size(); w++)
-            for (uint64_t bits = pt_bits[w]; bits; bits &= bits - 1)
-                list[k++] = (int32_t)(64 * w + (uint32_t)__builtin_ctzll(bits));
-        return k;
-    };
+    mask_list = prosac && sprt && c->estimator != USAC_HOMOGRAPHY && !getenv("USAC_DEVICE_INLIERS");
+    mask_check = mask_list && getenv("USAC_CHECK_MASK_LIST");
+    pt_bits.assign(mask_list ? ((size_t)n + 63) / 64 : 0, 0);
 
     lap(T_SETUP);
     // with the library's default batch the batches ramp up (1024, 2048, ...): the termination
@@ -2767,339 +2849,428 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
     // PROSAC on quality-sorted points finds its model within a few dozen samples and its
     // termination bound then drops to about as many (cfg3: ~9 iterations a run), so its ramp
     // starts at 32
-    uint32_t cap = prm->batch ? batch : std::min<uint32_t>(batch, prosac ? kRampFirstProsac : kRampFirst);
-    // draws B samples into buf (the reference's sample array reuse for NAPSAC: a sample the
-    // sampler leaves (partly) unwritten keeps the previous sample's entries)
-    auto draw_into = [&](int32_t *buf, uint32_t B, usac::ProsacSampler *pro_, uint32_t gen_term) {
-        for (uint32_t j = 0; j < B; j++) {
-            int32_t *smp = buf + (size_t)j * m;
-            if (pro_) {
-                subset_at[j] = pro_->subset();
-                pro_->generateSample(smp, gen_term);
-                largest_at[j] = pro_->largest();
-            } else if (napk) {
-                napk->generateSample(smp);
-            } else if (napsac) {
-                if (j > 0) memcpy(smp, smp - m, sizeof(int32_t) * m);
-                else memcpy(smp, last_sample.data(), sizeof(int32_t) * m);
-                nap->generateSample(smp);
-                if (j + 1 == B) memcpy(last_sample.data(), smp, sizeof(int32_t) * m);
-            } else {
-                uni->generateSample(smp);
-            }
-        }
-    };
-    // the sampler exactly after the batches consumed so far (undo a speculation's extra draws)
-    auto settle_sampler = [&]() {
-        if (!sampler_keep) return;
-        sampler_rollback();
-        last_sample = spec_last;
-        draw_into(hs2.data(), sampler_keep, nullptr, n);  // hs2 is free again: the kept batch moved to hs
-        sampler_keep = 0;
-    };
-    auto spec_wait = [&]() -> hipError_t {
-        for (uint32_t spins = 0;; spins++) {
-            const hipError_t e = hipEventQuery(c->spec_ev);
-            if (e != hipErrorNotReady) return e;
-            if ((spins & 1023u) == 1023u) std::this_thread::yield();
-        }
-    };
-    while (iters < max_iters) {
-        const uint32_t B = std::min(std::min(batch, max_iters - iters), cap);
-        if (!prm->batch) cap = std::min<uint32_t>(batch, 2 * cap);
-        bool have = false;  // this batch's device results are already on the host (speculation)
-        size_t spec_hst = 0;
-        if (spec) {
-            spec = false;
-            HIP_TRY(c, spec_wait());
-            if (B <= spec_B) {  // its first B samples are this batch
-                std::swap(hs, hs2);
-                std::swap(hc, hc2);
-                std::swap(hmod, hmod2);
-                spec_hst = (size_t)spec_B * spk;
-                have = true;
-                if (B < spec_B) {
-                    sampler_keep = B;  // undone lazily, before the next draw
-                    out->spec_rollbacks++;
-                    out->spec_wasted += spec_B - B;
-                } else {
-                    sampler_commit();
-                }
-            } else {  // (max_iterations grew) the speculation is dropped
-                out->spec_wasted += spec_B;
-                sampler_rollback();
-                last_sample = spec_last;
-            }
-        }
-        // ---- draw the batch (speculatively for PROSAC)
-        std::unique_ptr<usac::ProsacSampler> snapshot;
-        const uint32_t gen_term = prosac ? pterm->terminationLength() : n;
-        if (!have) {
-            settle_sampler();
-            const auto td0 = std::chrono::steady_clock::now();
-            if (prosac) snapshot.reset(new usac::ProsacSampler(*pro));
-            draw_into(hs.data(), B, prosac ? pro.get() : nullptr, gen_term);
-            t_drawonly += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count();
-        }
-        lap(T_DRAW);
-        // ---- device: solve, then exact scores or pool-order flags
-        const size_t S = (size_t)B * spk;
-        size_t hst = SB;  // host stride of hmod's components this batch
-        uint32_t rows = (uint32_t)S;
-        uint32_t mask_stride = (uint32_t)S;  // host row stride of hmask (SPRT)
-        if (have) {
-            hst = spec_hst;
-        } else if (nranks > 1) {  // this rank's slice, then the all-gather of every slice's counts and models
-            if ((rc = sharded_batch(c, hs.data(), B, iters, thr, nranks, rank, gather, gather_user, xbuf, hc.data(),
-                                    hmod.data(), SB, sprt != nullptr, hmask.data())))
-                return rc;
-        } else {
-        HIP_TRY(c, hipMemcpyAsync(c->samples.p, hs.data(), sizeof(int32_t) * (size_t)B * m, hipMemcpyHostToDevice,
+    cap = prm->batch ? batch : std::min<uint32_t>(batch, prosac ? kRampFirstProsac : kRampFirst);
+    return USAC_OK;
+}
+
+// exact (count, sum) of a host model -> (cnt, s), its inliers in c->inl_idx.
+// list_pin (nullable): the whole n-word inlier list copied in the same submission (its
+// first cnt words are the list) -- one host wait instead of a second, synchronous copy
+int RansacRun::score_inliers(const float *model_host, int32_t *list_pin) {
+    float *dres = c->pol_res.as<float>();
+    HIP_TRY(c, hipMemcpyAsync(c->one_model.p, model_host, sizeof(float) * 9, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, c->inl_scratch.reserve(usac::inliers_scratch_bytes(c->n, 1)));
+    HIP_TRY(c, usac::launch_inliers_batch(c->stream, c->estimator, c->pts.p, c->n, c->one_model.as<float>(), 1, thr,
+                                          nullptr, nullptr, c->inl_idx.as<int32_t>(), 0,
+                                          reinterpret_cast<int32_t *>(dres + 12), dres + 13, c->inl_scratch.p));
+    HIP_TRY(c, hipMemcpyAsync(static_cast<float *>(c->pol_pin.p) + 12, dres + 12, sizeof(float) * 2,
+                              hipMemcpyDeviceToHost, c->stream));
+    if (list_pin)
+        HIP_TRY(c, hipMemcpyAsync(list_pin, c->inl_idx.p, sizeof(int32_t) * (size_t)c->n, hipMemcpyDeviceToHost,
                                   c->stream));
-        HIP_TRY(c, enqueue_solve(c, c->samples.as<int32_t>(), B, 0, iters, nullptr));
-        const size_t mstride = (size_t)B * spk;
-        // listed SPRT batches: the slot counts, list and models ride behind the words (PoolTail)
-        const bool tailed = sprt && listed(c) && !getenv("USAC_NO_POOL_TAIL");
-        const size_t tail_off = (size_t)nw * S, tail_words = (2 + (size_t)ncomp(c)) * S + 1;
-        if (sprt && !sprt->pool_ready() && (rc = pool_upload())) return rc;  // deferred: behind the solve
-        if (sprt) {
-            const usac::PoolTail tail{reinterpret_cast<const uint32_t *>(c->counts.p), c->list_n.as<uint32_t>(),
-                                      c->list.as<uint32_t>(), c->models.as<uint32_t>(), (uint32_t)S,
-                                      (uint32_t)(ncomp(c) * S), c->masks.as<uint32_t>() + tail_off};
-            HIP_TRY(c, usac::launch_pool_mask(c->stream, c->estimator, c->pool_pts.p, n, c->models.as<float>(), mstride,
-                                              listed(c) ? c->list.as<uint32_t>() : nullptr,
-                                              listed(c) ? c->list_n.as<uint32_t>() : nullptr, (uint32_t)S, thr,
-                                              c->masks.as<uint32_t>(), listed(c) ? 0u : (uint32_t)S,
-                                              tailed ? &tail : nullptr));
-        } else {  // exact counts from the fast multi-chunk scorer; exact sums below, where needed
-            HIP_TRY(c, enqueue_score(c, B, thr, loop_chunks(c, B)));
-            HIP_TRY(c, hipMemcpyAsync(hc.data(), c->counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, stream_wait(c->stream));
+    memcpy(&cnt, static_cast<const float *>(c->pol_pin.p) + 12, sizeof(int32_t));
+    memcpy(&s, static_cast<const float *>(c->pol_pin.p) + 13, sizeof(float));
+    return USAC_OK;
+}
+
+// the inlier list of a pool-order mask row, ascending (PROSAC + SPRT, mask_list)
+int32_t RansacRun::mask_inliers(const uint32_t *row, size_t stride, int32_t *list) {
+    std::fill(pt_bits.begin(), pt_bits.end(), 0);
+    const uint32_t *pool = sprt->pool().data();
+    for (uint32_t w = 0; w < nw; w++)
+        for (uint32_t bits = row[(size_t)w * stride]; bits; bits &= bits - 1) {
+            const uint32_t p = pool[32 * w + (uint32_t)__builtin_ctz(bits)];
+            pt_bits[p >> 6] |= 1ull << (p & 63);
         }
-        // the device's component-major [ncomp][S] block in one copy (host stride S this batch:
-        // every copy costs a fixed overhead, 18 per-component copies of a ramp batch cost more
-        // than the batch's kernels)
-        hst = S;
-        if (!tailed)
-            HIP_TRY(c, hipMemcpyAsync(hmod.data(), c->models.p, sizeof(float) * S * ncomp(c), hipMemcpyDeviceToHost,
-                                      c->stream));
-        const uint32_t *htail = nullptr;  // the batch's PoolTail on the host
-        auto untail = [&]() {
-            memcpy(hc.data(), htail, sizeof(int32_t) * S);
-            hlist[SB] = htail[S];
-            memcpy(hlist.data(), htail + S + 1, sizeof(uint32_t) * S);
-            memcpy(hmod.data(), htail + 2 * S + 1, sizeof(float) * S * ncomp(c));
-        };
-        if (tailed) {
-            // small batches (the PROSAC ramp's first ones, where a cfg3 run ends): words and tail in
-            // one copy, one host wait; larger ones: the tail first, then only the rows' words (the
-            // words are packed [nw][rows] on the device: k_pool_mask, row stride 0)
-            const bool whole = (size_t)nw * S * sizeof(uint32_t) <= kMaskWholeCopy;
-            if (whole) {
-                HIP_TRY(c, hipMemcpyAsync(hmask.data(), c->masks.p, sizeof(uint32_t) * (tail_off + tail_words),
-                                          hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, stream_wait(c->stream));
-                htail = hmask.data() + tail_off;
-                untail();
-            } else {
-                HIP_TRY(c, hipMemcpyAsync(hmask.data() + (size_t)nw * SB, c->masks.as<uint32_t>() + tail_off,
-                                          sizeof(uint32_t) * tail_words, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, stream_wait(c->stream));
-                htail = hmask.data() + (size_t)nw * SB;
-                untail();
-                rows = hlist[SB];
-                if (rows) HIP_TRY(c, hipMemcpyAsync(hmask.data(), c->masks.p, sizeof(uint32_t) * (size_t)rows * nw,
-                                                    hipMemcpyDeviceToHost, c->stream));
-            }
-        } else if (sprt) {
-            // listed: the occupied rows' words packed [nw][rows] on the device (k_pool_mask, row
-            // stride 0).  Small batches (the PROSAC ramp's first ones, where a cfg3 run ends): the
-            // whole block with the list in the same submission -- one host wait; larger ones: the
-            // list count first, then only the rows' words (a plain copy: hipMemcpy2DAsync's first
-            // call in a process cost ~7 ms, round 5)
-            const bool whole = !listed(c) || (size_t)nw * S * sizeof(uint32_t) <= kMaskWholeCopy;
-            if (listed(c)) {  // occupied slots -> mask rows
-                HIP_TRY(c, hipMemcpyAsync(hc.data(), c->counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipMemcpyAsync(hlist.data() + SB, c->list_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                          c->stream));
-                if (whole) {
-                    HIP_TRY(c, hipMemcpyAsync(hlist.data(), c->list.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost,
-                                              c->stream));
-                } else {
-                    HIP_TRY(c, stream_wait(c->stream));
-                    rows = hlist[SB];
-                    if (rows) HIP_TRY(c, hipMemcpyAsync(hlist.data(), c->list.p, sizeof(uint32_t) * rows,
-                                                        hipMemcpyDeviceToHost, c->stream));
-                }
-            } else {
-                std::fill(hc.begin(), hc.begin() + S, 0);
-            }
-            if (whole) {
-                mask_stride = (uint32_t)S;  // listed: the row count, below
-                HIP_TRY(c, hipMemcpyAsync(hmask.data(), c->masks.p, sizeof(uint32_t) * S * nw, hipMemcpyDeviceToHost,
-                                          c->stream));
-            } else if (rows) {
-                HIP_TRY(c, hipMemcpyAsync(hmask.data(), c->masks.p, sizeof(uint32_t) * (size_t)rows * nw,
-                                          hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-        HIP_TRY(c, stream_wait(c->stream));
-        if (sprt && listed(c)) mask_stride = rows = hlist[SB];
-        }
-        if (sprt) {
-            if (listed(c) && nranks == 1) {
-                std::fill(slot_row.begin(), slot_row.begin() + S, -1);
-                for (uint32_t r = 0; r < rows; r++) slot_row[hlist[r]] = (int32_t)r;
-            } else {
-                for (size_t sl = 0; sl < S; sl++) slot_row[sl] = (int32_t)sl;
-            }
-        }
-        // ---- speculation: the next batch, as if the replay leaves max_iterations alone -- unless
-        // this batch certainly ends the run: the replay leaves max_iters <= the termination bound
-        // of its final best, whose count is at least every count of this batch (Score::bigger
-        // orders by count first; LO only adds inliers) and the bound does not grow with the count
-        bool spec_next = spec_ok && iters + B < max_iters;
-        if (spec_next) {
-            int maxc = best.inlier_number;
-            for (size_t sl = 0; sl < S; sl++) maxc = std::max(maxc, hc[sl]);
-            spec_next = term.getUpBoundIterations((uint32_t)maxc) > iters + B;
-        }
-        if (spec_next) {
-            settle_sampler();
-            const uint32_t B2 = std::min(std::min(batch, max_iters - (iters + B)), cap);
-            sampler_mark();
-            spec_last = last_sample;
-            draw_into(hs2.data(), B2, nullptr, n);
-            const size_t S2 = (size_t)B2 * spk;
-            std::swap(c->stream, c->spec_stream);  // the launchers enqueue on c->stream
-            hipError_t e = hipMemcpyAsync(c->samples.p, hs2.data(), sizeof(int32_t) * (size_t)B2 * m,
-                                          hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = enqueue_solve(c, c->samples.as<int32_t>(), B2, 0, iters + B, nullptr);
-            if (e == hipSuccess) e = enqueue_score(c, B2, thr, loop_chunks(c, B2));
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(hc2.data(), c->counts.p, sizeof(int32_t) * S2, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(hmod2.data(), c->models.p, sizeof(float) * S2 * ncomp(c), hipMemcpyDeviceToHost,
-                                   c->stream);
-            if (e == hipSuccess) e = hipEventRecord(c->spec_ev, c->stream);
-            std::swap(c->stream, c->spec_stream);
-            if (e != hipSuccess) {
-                (void)hipStreamSynchronize(c->spec_stream);
-                return fail(c, USAC_ERR_HIP, std::string("speculative batch: ") + hipGetErrorString(e));
-            }
-            spec = true;
-            spec_B = B2;
-            out->spec_batches++;
-        }
-        lap(T_DEVICE);
-        if (!sprt && (rc = exact_sums(c, thr, best.inlier_number, hc.data(), hmod.data(), hst, S, hsum.data(),
-                                      &out->sum_models)))
-            return rc;
-        lap(T_SUMS);
-        out->batches++;
-        // ---- sequential replay
-        uint32_t j = 0;
-        bool rewind = false;
-        for (; j < B && iters < max_iters; j++) {
-            for (uint32_t q = 0; q < spk; q++) {
-                const size_t sl = (size_t)j * spk + q;
-                if (hc[sl] < 0) break;  // empty slot: the sample has no more models
-                usac::Score cur;
-                int32_t r = 0;
-                if (sprt) {
-                    r = slot_row[sl];
-                    const auto tv0 = std::chrono::steady_clock::now();
-                    const bool good = sprt->verify(hmask.data() + r, (int)iters, (uint32_t)best.inlier_number,
-                                                   cur.inlier_number, cur.score, mask_stride);
-                    t_verify += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tv0).count();
-                    if (!good) {
-                        out->sprt_rejected++;
-                        if ((int)iters >= max_before) {  // max_hypothesis_test_before_sprt (model.hpp:40), Q9
-                            iters++;
-                            continue;
-                        }
-                    }
-                } else {
-                    cur.inlier_number = hc[sl];
-                    cur.score = hsum[sl];
-                }
-                if (!cur.bigger(best)) continue;
-                float model[9];
-                for (int k = 0; k < 9; k++) model[k] = k < ncomp(c) ? hmod[(size_t)k * hst + sl] : 0.f;
-                if (lo) {  // ransac.cpp:110-112, before the best is replaced
-                    lap(T_REPLAY);
-                    lo->run(model, cur.inlier_number, cur.score);
-                    if (lo->rc) return lo->rc;
-                    lap(T_LO);
-                }
-                if (gc) {
-                    lap(T_REPLAY);
-                    gc->run(model, cur.inlier_number, cur.score);
-                    if (gc->rc) return gc->rc;
-                    lap(T_LO);
-                }
-                best = cur;
-                memcpy(best_model, model, sizeof(best_model));
-                if (prosac && mask_list) {
-                    cnt = mask_inliers(hmask.data() + r, mask_stride, inl_list.data());
-                    if (mask_check) {
-                        std::vector<int32_t> dl(n);
-                        const int32_t mc = cnt;
-                        if ((rc = score_inliers(best_model, dl.data()))) return rc;
-                        const std::vector<int32_t> tmp(inl_list.data(), inl_list.data() + mc);
-                        if (cnt != mc || cnt != cur.inlier_number ||
-                            !std::equal(tmp.begin(), tmp.end(), dl.begin()))
-                            return fail(c, USAC_ERR_HIP, "mask-decoded inlier list differs from getInliers");
-                        cnt = mc;
-                    }
-                    max_iters = pterm->getUpBoundIterationsSorted(iters, inl_list.data(), (uint32_t)cnt, largest_at[j]);
-                } else if (prosac) {
-                    if ((rc = score_inliers(best_model, inl_list.data()))) return rc;
-                    // (the list is ascending: the compaction keeps point order)
-                    max_iters = pterm->getUpBoundIterationsSorted(iters, inl_list.data(), (uint32_t)cnt, largest_at[j]);
-                } else {
-                    max_iters = term.getUpBoundIterations((uint32_t)best.inlier_number);
-                }
-                if (sprt) max_iters = std::min(max_iters, sprt->getUpperBoundIterations(best.inlier_number));
-                if (records && (uint32_t)nrec < rec_cap) {
-                    usac_record &rr = records[nrec];
-                    rr.hyp_index = iters;
-                    rr.inliers = cur.inlier_number;
-                    rr.score = cur.score;
-                    memcpy(rr.model, best_model, sizeof(best_model));
-                    rr.valid = 1;
-                }
-                nrec++;
-            }
-            iters++;
-            if (prosac && pterm->terminationLength() != gen_term && j + 1 < B) {
-                // would the NEXT sample be drawn differently (prosac_sampler.hpp: a subset above the
-                // termination length takes the uniform draw)?  The subsets only grow and the length
-                // only shrinks, so the batch's samples stay valid up to the first one that would --
-                // the replay goes on through them (the run often ends there) and rewinds at it
-                const uint32_t tl = pterm->terminationLength();
-                rewind = (subset_at[j + 1] > gen_term) || (subset_at[j + 1] > tl);
-                if (rewind) break;
-            }
-        }
-        if (rewind) {  // sampler state just after sample j: replay the first j + 1 draws
-            pro = std::move(snapshot);
-            std::vector<int32_t> tmp(m);
-            for (uint32_t k = 0; k <= j; k++) pro->generateSample(tmp.data(), gen_term);
-            out->rollbacks++;
+    int32_t k = 0;
+    for (size_t w = 0; w < pt_bits.size(); w++)
+        for (uint64_t bits = pt_bits[w]; bits; bits &= bits - 1)
+            list[k++] = (int32_t)(64 * w + (uint32_t)__builtin_ctzll(bits));
+    return k;
+}
+
+// draws count samples into buf (the reference's sample array reuse for NAPSAC: a sample the
+// sampler leaves (partly) unwritten keeps the previous sample's entries)
+void RansacRun::draw_into(int32_t *buf, uint32_t count, usac::ProsacSampler *pro_, uint32_t term_len) {
+    for (uint32_t j = 0; j < count; j++) {
+        int32_t *smp = buf + (size_t)j * m;
+        if (pro_) {
+            subset_at[j] = pro_->subset();
+            pro_->generateSample(smp, term_len);
+            largest_at[j] = pro_->largest();
+        } else if (napk) {
+            napk->generateSample(smp);
+        } else if (napsac) {
+            if (j > 0) memcpy(smp, smp - m, sizeof(int32_t) * m);
+            else memcpy(smp, last_sample.data(), sizeof(int32_t) * m);
+            nap->generateSample(smp);
+            if (j + 1 == count) memcpy(last_sample.data(), smp, sizeof(int32_t) * m);
+        } else {
+            uni->generateSample(smp);
         }
     }
+}
+
+// the sampler exactly after the batches consumed so far (undo a speculation's extra draws)
+void RansacRun::settle_sampler() {
+    if (!sampler_keep) return;
+    sampler_rollback();
+    last_sample = spec_last;
+    draw_into(hs2.data(), sampler_keep, nullptr, n);  // hs2 is free again: the kept batch moved to hs
+    sampler_keep = 0;
+}
+
+hipError_t RansacRun::spec_wait() {
+    for (uint32_t spins = 0;; spins++) {
+        const hipError_t e = hipEventQuery(c->spec_ev);
+        if (e != hipErrorNotReady) return e;
+        if ((spins & 1023u) == 1023u) std::this_thread::yield();
+    }
+}
+
+// 4. The batch's size, and the batch drawn ahead taken (its first B samples are this batch: have) or dropped.
+// Reads spec / spec_B; leaves B, cap, have, spec_hst, the sampler marks and the spec_* counters.
+int RansacRun::take_speculation() {
+    B = std::min(std::min(batch, max_iters - iters), cap);
+    if (!prm->batch) cap = std::min<uint32_t>(batch, 2 * cap);
+    have = false;  // this batch's device results are already on the host (speculation)
+    spec_hst = 0;
+    if (spec) {
+        spec = false;
+        HIP_TRY(c, spec_wait());
+        if (B <= spec_B) {  // its first B samples are this batch
+            std::swap(hs, hs2);
+            std::swap(hc, hc2);
+            std::swap(hmod, hmod2);
+            spec_hst = (size_t)spec_B * spk;
+            have = true;
+            if (B < spec_B) {
+                sampler_keep = B;  // undone lazily, before the next draw
+                out->spec_rollbacks++;
+                out->spec_wasted += spec_B - B;
+            } else {
+                sampler_commit();
+            }
+        } else {  // (max_iterations grew) the speculation is dropped
+            out->spec_wasted += spec_B;
+            sampler_rollback();
+            last_sample = spec_last;
+        }
+    }
+    return USAC_OK;
+}
+
+// 5. Draw.  Reads have; leaves B samples in hs (PROSAC: gen_term, the sampler's snapshot, subset_at / largest_at).
+void RansacRun::draw() {
+    // ---- draw the batch (speculatively for PROSAC)
+    snapshot.reset();
+    gen_term = prosac ? pterm->terminationLength() : n;
+    if (!have) {
+        settle_sampler();
+        const auto td0 = std::chrono::steady_clock::now();
+        if (prosac) snapshot.reset(new usac::ProsacSampler(*pro));
+        draw_into(hs.data(), B, prosac ? pro.get() : nullptr, gen_term);
+        t_drawonly += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count();
+    }
+    lap(T_DRAW);
+}
+
+// 6a. The one-rank device batch: solve, then the scorer's counts or (SPRT) the pool-order words, and the
+// download ladder (PoolTail / whole copy / rows only).  Reads hs, B, S; leaves hc, hmod (stride hst), and
+// with SPRT hlist, hmask, rows, mask_stride.
+int RansacRun::one_rank_batch() {
+    int rc;
+    HIP_TRY(c, hipMemcpyAsync(c->samples.p, hs.data(), sizeof(int32_t) * (size_t)B * m, hipMemcpyHostToDevice,
+                              c->stream));
+    HIP_TRY(c, enqueue_solve(c, c->samples.as<int32_t>(), B, 0, iters, nullptr));
+    const size_t mstride = (size_t)B * spk;
+    // listed SPRT batches: the slot counts, list and models ride behind the words (PoolTail)
+    const bool tailed = sprt && listed(c) && !getenv("USAC_NO_POOL_TAIL");
+    const size_t tail_off = (size_t)nw * S, tail_words = (2 + (size_t)ncomp(c)) * S + 1;
+    if (sprt && !sprt->pool_ready() && (rc = pool_upload())) return rc;  // deferred: behind the solve
+    if (sprt) {
+        const usac::PoolTail tail{reinterpret_cast<const uint32_t *>(c->counts.p), c->list_n.as<uint32_t>(),
+                                  c->list.as<uint32_t>(), c->models.as<uint32_t>(), (uint32_t)S,
+                                  (uint32_t)(ncomp(c) * S), c->masks.as<uint32_t>() + tail_off};
+        HIP_TRY(c, usac::launch_pool_mask(c->stream, c->estimator, c->pool_pts.p, n, c->models.as<float>(), mstride,
+                                          listed(c) ? c->list.as<uint32_t>() : nullptr,
+                                          listed(c) ? c->list_n.as<uint32_t>() : nullptr, (uint32_t)S, thr,
+                                          c->masks.as<uint32_t>(), listed(c) ? 0u : (uint32_t)S,
+                                          tailed ? &tail : nullptr));
+    } else {  // exact counts from the fast multi-chunk scorer; exact sums below, where needed
+        HIP_TRY(c, enqueue_score(c, B, thr, loop_chunks(c, B)));
+        HIP_TRY(c, hipMemcpyAsync(hc.data(), c->counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
+    }
+    // the device's component-major [ncomp][S] block in one copy (host stride S this batch:
+    // every copy costs a fixed overhead, 18 per-component copies of a ramp batch cost more
+    // than the batch's kernels)
+    hst = S;
+    if (!tailed)
+        HIP_TRY(c, hipMemcpyAsync(hmod.data(), c->models.p, sizeof(float) * S * ncomp(c), hipMemcpyDeviceToHost,
+                                  c->stream));
+    const uint32_t *htail = nullptr;  // the batch's PoolTail on the host
+    auto untail = [&]() {
+        memcpy(hc.data(), htail, sizeof(int32_t) * S);
+        hlist[SB] = htail[S];
+        memcpy(hlist.data(), htail + S + 1, sizeof(uint32_t) * S);
+        memcpy(hmod.data(), htail + 2 * S + 1, sizeof(float) * S * ncomp(c));
+    };
+    if (tailed) {
+        // small batches (the PROSAC ramp's first ones, where a cfg3 run ends): words and tail in
+        // one copy, one host wait; larger ones: the tail first, then only the rows' words (the
+        // words are packed [nw][rows] on the device: k_pool_mask, row stride 0)
+        const bool whole = (size_t)nw * S * sizeof(uint32_t) <= kMaskWholeCopy;
+        if (whole) {
+            HIP_TRY(c, hipMemcpyAsync(hmask.data(), c->masks.p, sizeof(uint32_t) * (tail_off + tail_words),
+                                      hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, stream_wait(c->stream));
+            htail = hmask.data() + tail_off;
+            untail();
+        } else {
+            HIP_TRY(c, hipMemcpyAsync(hmask.data() + (size_t)nw * SB, c->masks.as<uint32_t>() + tail_off,
+                                      sizeof(uint32_t) * tail_words, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, stream_wait(c->stream));
+            htail = hmask.data() + (size_t)nw * SB;
+            untail();
+            rows = hlist[SB];
+            if (rows) HIP_TRY(c, hipMemcpyAsync(hmask.data(), c->masks.p, sizeof(uint32_t) * (size_t)rows * nw,
+                                                hipMemcpyDeviceToHost, c->stream));
+        }
+    } else if (sprt) {
+        // listed: the occupied rows' words packed [nw][rows] on the device (k_pool_mask, row
+        // stride 0).  Small batches (the PROSAC ramp's first ones, where a cfg3 run ends): the
+        // whole block with the list in the same submission -- one host wait; larger ones: the
+        // list count first, then only the rows' words (a plain copy: hipMemcpy2DAsync's first
+        // call in a process cost ~7 ms, round 5)
+        const bool whole = !listed(c) || (size_t)nw * S * sizeof(uint32_t) <= kMaskWholeCopy;
+        if (listed(c)) {  // occupied slots -> mask rows
+            HIP_TRY(c, hipMemcpyAsync(hc.data(), c->counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(hlist.data() + SB, c->list_n.p, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                      c->stream));
+            if (whole) {
+                HIP_TRY(c, hipMemcpyAsync(hlist.data(), c->list.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost,
+                                          c->stream));
+            } else {
+                HIP_TRY(c, stream_wait(c->stream));
+                rows = hlist[SB];
+                if (rows) HIP_TRY(c, hipMemcpyAsync(hlist.data(), c->list.p, sizeof(uint32_t) * rows,
+                                                    hipMemcpyDeviceToHost, c->stream));
+            }
+        } else {
+            std::fill(hc.begin(), hc.begin() + S, 0);
+        }
+        if (whole) {
+            mask_stride = (uint32_t)S;  // listed: the row count, below
+            HIP_TRY(c, hipMemcpyAsync(hmask.data(), c->masks.p, sizeof(uint32_t) * S * nw, hipMemcpyDeviceToHost,
+                                      c->stream));
+        } else if (rows) {
+            HIP_TRY(c, hipMemcpyAsync(hmask.data(), c->masks.p, sizeof(uint32_t) * (size_t)rows * nw,
+                                      hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    HIP_TRY(c, stream_wait(c->stream));
+    if (sprt && listed(c)) mask_stride = rows = hlist[SB];
+    return USAC_OK;
+}
+
+// 6. Device batch: already here (speculation), sharded, or one rank.  Leaves S, hst, rows, mask_stride,
+// the host arrays and slot_row.
+int RansacRun::device_batch() {
+    int rc;
+    // ---- device: solve, then exact scores or pool-order flags
+    S = (size_t)B * spk;
+    hst = SB;  // host stride of hmod's components this batch
+    rows = (uint32_t)S;
+    mask_stride = (uint32_t)S;  // host row stride of hmask (SPRT)
+    if (have) {
+        hst = spec_hst;
+    } else if (nranks > 1) {  // this rank's slice, then the all-gather of every slice's counts and models
+        if ((rc = sharded_batch(c, hs.data(), B, iters, thr, nranks, rank, gather, gather_user, xbuf, hc.data(),
+                                hmod.data(), SB, sprt != nullptr, hmask.data())))
+            return rc;
+    } else if ((rc = one_rank_batch())) {
+        return rc;
+    }
+    if (sprt) {
+        if (listed(c) && nranks == 1) {
+            std::fill(slot_row.begin(), slot_row.begin() + S, -1);
+            for (uint32_t r = 0; r < rows; r++) slot_row[hlist[r]] = (int32_t)r;
+        } else {
+            for (size_t sl = 0; sl < S; sl++) slot_row[sl] = (int32_t)sl;
+        }
+    }
+    return USAC_OK;
+}
+
+// 7. Speculate the next batch on the spec stream.  Reads hc, best, max_iters; leaves spec, spec_B, hs2 /
+// hc2 / hmod2 in flight.
+int RansacRun::speculate_next() {
+    // ---- speculation: the next batch, as if the replay leaves max_iterations alone -- unless
+    // this batch certainly ends the run: the replay leaves max_iters <= the termination bound
+    // of its final best, whose count is at least every count of this batch (Score::bigger
+    // orders by count first; LO only adds inliers) and the bound does not grow with the count
+    bool spec_next = spec_ok && iters + B < max_iters;
+    if (spec_next) {
+        int maxc = best.inlier_number;
+        for (size_t sl = 0; sl < S; sl++) maxc = std::max(maxc, hc[sl]);
+        spec_next = term.getUpBoundIterations((uint32_t)maxc) > iters + B;
+    }
+    if (spec_next) {
+        settle_sampler();
+        const uint32_t B2 = std::min(std::min(batch, max_iters - (iters + B)), cap);
+        sampler_mark();
+        spec_last = last_sample;
+        draw_into(hs2.data(), B2, nullptr, n);
+        const size_t S2 = (size_t)B2 * spk;
+        std::swap(c->stream, c->spec_stream);  // the launchers enqueue on c->stream
+        hipError_t e = hipMemcpyAsync(c->samples.p, hs2.data(), sizeof(int32_t) * (size_t)B2 * m,
+                                      hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = enqueue_solve(c, c->samples.as<int32_t>(), B2, 0, iters + B, nullptr);
+        if (e == hipSuccess) e = enqueue_score(c, B2, thr, loop_chunks(c, B2));
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(hc2.data(), c->counts.p, sizeof(int32_t) * S2, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(hmod2.data(), c->models.p, sizeof(float) * S2 * ncomp(c), hipMemcpyDeviceToHost,
+                               c->stream);
+        if (e == hipSuccess) e = hipEventRecord(c->spec_ev, c->stream);
+        std::swap(c->stream, c->spec_stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(c->spec_stream);
+            return fail(c, USAC_ERR_HIP, std::string("speculative batch: ") + hipGetErrorString(e));
+        }
+        spec = true;
+        spec_B = B2;
+        out->spec_batches++;
+    }
+    lap(T_DEVICE);
+    return USAC_OK;
+}
+
+// Exact sums of the slots the replay can read.  Reads hc, hmod; leaves hsum.
+int RansacRun::sums() {
+    int rc;
+    if (!sprt && (rc = exact_sums(c, thr, best.inlier_number, hc.data(), hmod.data(), hst, S, hsum.data(),
+                                  &out->sum_models)))
+        return rc;
+    lap(T_SUMS);
+    out->batches++;
+    return USAC_OK;
+}
+
+// 8. Sequential replay of the batch, the PROSAC rewind included.  Reads the host arrays; leaves best,
+// best_model, iters, max_iters, the records and the run counters.
+int RansacRun::replay() {
+    int rc;
+    // ---- sequential replay
+    uint32_t j = 0;
+    bool rewind = false;
+    for (; j < B && iters < max_iters; j++) {
+        for (uint32_t q = 0; q < spk; q++) {
+            const size_t sl = (size_t)j * spk + q;
+            if (hc[sl] < 0) break;  // empty slot: the sample has no more models
+            usac::Score cur;
+            int32_t r = 0;
+            if (sprt) {
+                r = slot_row[sl];
+                const auto tv0 = std::chrono::steady_clock::now();
+                const bool good = sprt->verify(hmask.data() + r, (int)iters, (uint32_t)best.inlier_number,
+                                               cur.inlier_number, cur.score, mask_stride);
+                t_verify += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tv0).count();
+                if (!good) {
+                    out->sprt_rejected++;
+                    if ((int)iters >= max_before) {  // max_hypothesis_test_before_sprt (model.hpp:40), Q9
+                        iters++;
+                        continue;
+                    }
+                }
+            } else {
+                cur.inlier_number = hc[sl];
+                cur.score = hsum[sl];
+            }
+            if (!cur.bigger(best)) continue;
+            float model[9];
+            for (int k = 0; k < 9; k++) model[k] = k < ncomp(c) ? hmod[(size_t)k * hst + sl] : 0.f;
+            if (lo) {  // ransac.cpp:110-112, before the best is replaced
+                lap(T_REPLAY);
+                lo->run(model, cur.inlier_number, cur.score);
+                if (lo->rc) return lo->rc;
+                lap(T_LO);
+            }
+            if (gc) {
+                lap(T_REPLAY);
+                gc->run(model, cur.inlier_number, cur.score);
+                if (gc->rc) return gc->rc;
+                lap(T_LO);
+            }
+            best = cur;
+            memcpy(best_model, model, sizeof(best_model));
+            if (prosac && mask_list) {
+                cnt = mask_inliers(hmask.data() + r, mask_stride, inl_list.data());
+                if (mask_check) {
+                    std::vector<int32_t> dl(n);
+                    const int32_t mc = cnt;
+                    if ((rc = score_inliers(best_model, dl.data()))) return rc;
+                    const std::vector<int32_t> tmp(inl_list.data(), inl_list.data() + mc);
+                    if (cnt != mc || cnt != cur.inlier_number ||
+                        !std::equal(tmp.begin(), tmp.end(), dl.begin()))
+                        return fail(c, USAC_ERR_HIP, "mask-decoded inlier list differs from getInliers");
+                    cnt = mc;
+                }
+                max_iters = pterm->getUpBoundIterationsSorted(iters, inl_list.data(), (uint32_t)cnt, largest_at[j]);
+            } else if (prosac) {
+                if ((rc = score_inliers(best_model, inl_list.data()))) return rc;
+                // (the list is ascending: the compaction keeps point order)
+                max_iters = pterm->getUpBoundIterationsSorted(iters, inl_list.data(), (uint32_t)cnt, largest_at[j]);
+            } else {
+                max_iters = term.getUpBoundIterations((uint32_t)best.inlier_number);
+            }
+            if (sprt) max_iters = std::min(max_iters, sprt->getUpperBoundIterations(best.inlier_number));
+            if (records && (uint32_t)nrec < rec_cap) {
+                usac_record &rr = records[nrec];
+                rr.hyp_index = iters;
+                rr.inliers = cur.inlier_number;
+                rr.score = cur.score;
+                memcpy(rr.model, best_model, sizeof(best_model));
+                rr.valid = 1;
+            }
+            nrec++;
+        }
+        iters++;
+        if (prosac && pterm->terminationLength() != gen_term && j + 1 < B) {
+            // would the NEXT sample be drawn differently (prosac_sampler.hpp: a subset above the
+            // termination length takes the uniform draw)?  The subsets only grow and the length
+            // only shrinks, so the batch's samples stay valid up to the first one that would --
+            // the replay goes on through them (the run often ends there) and rewinds at it
+            const uint32_t tl = pterm->terminationLength();
+            rewind = (subset_at[j + 1] > gen_term) || (subset_at[j + 1] > tl);
+            if (rewind) break;
+        }
+    }
+    if (rewind) {  // sampler state just after sample j: replay the first j + 1 draws
+        pro = std::move(snapshot);
+        std::vector<int32_t> tmp(m);
+        for (uint32_t k = 0; k <= j; k++) pro->generateSample(tmp.data(), gen_term);
+        out->rollbacks++;
+    }
+    return USAC_OK;
+}
+
+void RansacRun::lo_counters() {
+    out->lo_inner_iters = lo ? lo->inner_count : gc ? gc->gc_iters : 0;
+    out->lo_iterative_iters = lo ? lo->iterative_count : gc ? gc->labelings : 0;
+    out->lo_rounds = lo ? lo->rounds : gc ? gc->labelings : 0;
+    out->lo_stages = lo ? lo->stages : gc ? gc->stages : 0;
+    out->lo_fits = lo ? lo->fits : 0;
+}
+
+// 9. Finish: the loop's out fields, no-model exit, the forced graph cut.  Reads best / best_model; may raise them.
+int RansacRun::finish() {
     if (spec) out->spec_wasted += spec_B;  // the run ended before the batch drawn ahead
     out->iters = iters;
     out->n_records = nrec;
     out->sprt_histories = sprt ? (int32_t)sprt->histories() : 0;
     out->prosac_term_len = prosac ? pterm->terminationLength() : n;
-    auto lo_counters = [&]() {
-        out->lo_inner_iters = lo ? lo->inner_count : gc ? gc->gc_iters : 0;
-        out->lo_iterative_iters = lo ? lo->iterative_count : gc ? gc->labelings : 0;
-        out->lo_rounds = lo ? lo->rounds : gc ? gc->labelings : 0;
-        out->lo_stages = lo ? lo->stages : gc ? gc->stages : 0;
-        out->lo_fits = lo ? lo->fits : 0;
-    };
     lo_counters();
     memcpy(out->minimal_model, best_model, sizeof(best_model));
     out->minimal_inliers = best.inlier_number;
@@ -3118,6 +3289,82 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
     }
 
     lap(T_REPLAY);
+    return USAC_OK;
+}
+
+// ransac.cpp:170-200 on the results of passes k0 .. k1 - 1 (pol_pin)
+void RansacRun::polish_replay(int k0, int k1, const float *hres, int32_t *const *lists, int &prev, bool &stop) {
+    int32_t ok = 0;
+    for (int k = k0; k < k1; k++) {
+        const float *r = hres + usac::kPolPass * k;
+        memcpy(&ok, r + 9, sizeof(int32_t));
+        memcpy(&cnt, r + 10, sizeof(int32_t));
+        memcpy(&s, r + 11, sizeof(float));
+        if (!ok || (double)((float)cnt / (float)best.inlier_number) < 0.8 || cnt <= prev) {
+            stop = true;
+            break;
+        }
+        prev = cnt;
+        best.inlier_number = cnt;
+        best.score = s;
+        memcpy(best_model, r, sizeof(best_model));
+        cur = lists[k + 1];
+        cur_cnt = cnt;
+        out->polish_passes++;
+    }
+}
+
+// the fused polish's phases (us): getInliers, then per pass gather, means,
+// distance terms, distances, A^T A, finish, score, Σerr
+int RansacRun::polish_fused_profile(int k_first) {
+    uint64_t st[64] = {0};
+    HIP_TRY(c, hipMemcpy(st, c->partial.p, sizeof(st), hipMemcpyDeviceToHost));
+    fprintf(stderr, "polish_fused us: init %.1f %.1f |", (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01);
+    uint64_t last = st[2];
+    for (int k = 0; k < k_first; k++) {
+        for (int i = 0; i < 8; i++) {
+            const uint64_t v = st[3 + 8 * k + i];
+            fprintf(stderr, " %.1f", v >= last ? (v - last) * 0.01 : -1.0);
+            if (v >= last) last = v;
+        }
+        fprintf(stderr, " |");
+    }
+    fprintf(stderr, " walked segments: 4ch %llu 2ch %llu 1ch %llu\n", (unsigned long long)st[44],
+            (unsigned long long)st[42], (unsigned long long)st[41]);
+    return USAC_OK;
+}
+
+// pass k of the multi-launch polish enqueued: the fit of list k, its scoring into list k + 1
+int RansacRun::polish_pass(int k, float *dres, int32_t *dres_i, int32_t *const *lists, bool finish_score) {
+    float *pres = dres + usac::kPolPass * k;
+    int32_t *dok = dres_i + usac::kPolPass * k + 9;
+    // the pass's finish, scoring and acceptance in one workgroup (k_finish_score) when the
+    // points fit its LDS and the fit takes the multi-launch path
+    const uint32_t nfit = k == 0 ? (uint32_t)best.inlier_number : c->n;
+    const bool fs = finish_score && nfit > usac::kSmallFitMax;
+    usac::NmBatch nb{};
+    if (k == 0)
+        HIP_TRY(c, enqueue_nonminimal(c, lists[0], nfit, pres, dok, nullptr, nullptr, fs ? &nb : nullptr));
+    else  // the count pass k - 1's acceptance left on the device; c->n bounds it
+        HIP_TRY(c, enqueue_nonminimal(c, lists[k], nfit, pres, dok, nullptr,
+                                      reinterpret_cast<const uint32_t *>(dres_i + usac::kPolNs + k),
+                                      fs ? &nb : nullptr));
+    if (fs) {
+        HIP_TRY(c, usac::launch_finish_score(c->stream, c->estimator, nb, c->pts.p, c->n, thr, lists[k + 1],
+                                             dok + 1, pres + 11, dres_i, k + 1 < kPasses ? k : -1,
+                                             best.inlier_number));
+        return USAC_OK;
+    }
+    HIP_TRY(c, usac::launch_inliers_batch(c->stream, c->estimator, c->pts.p, c->n, pres, 1, thr, nullptr,
+                                          nullptr, lists[k + 1], 0, dok + 1, pres + 11, c->inl_scratch.p, dok));
+    if (k + 1 < kPasses) HIP_TRY(c, usac::launch_polish_prep(c->stream, dres_i, k, best.inlier_number));
+    return USAC_OK;
+}
+
+// 10. Polish.  Reads best / best_model; leaves them polished, cur / cur_cnt (best_model's own inlier list on
+// the device) and out->polish_passes.
+int RansacRun::polish() {
+    int rc;
     // ---- polish (ransac.cpp:157-207) on the device, the passes submitted in groups: pass k
     // fits the list pass k - 1 scored (the initial getInliers(best_model) list for pass 0) and
     // scores the fitted model from device memory into list k + 1 (compaction gated on the fit's
@@ -3129,11 +3376,11 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
     HIP_TRY(c, c->pol_res.reserve(sizeof(float) * usac::kPolWords));
     HIP_TRY(c, c->pol_lists.reserve(sizeof(int32_t) * 4 * (size_t)std::max<uint32_t>(c->n, 1)));
     HIP_TRY(c, c->inl_scratch.reserve(usac::inliers_scratch_bytes(c->n, 1)));
-    if (!c->pol_pin && !(c->pol_pin = PinnedPool::get().take(sizeof(float) * usac::kPolWords, &c->pol_pin_bytes)))
+    if (!pin_grow(c->pol_pin, sizeof(float) * usac::kPolWords))
         return fail(c, USAC_ERR_HIP, "pinned host allocation failed");
     float *dres = c->pol_res.as<float>();
     int32_t *dres_i = c->pol_res.as<int32_t>();
-    const float *hres = static_cast<const float *>(c->pol_pin);
+    const float *hres = static_cast<const float *>(c->pol_pin.p);
     int32_t *lists[5] = {c->inl_idx.as<int32_t>(), c->pol_lists.as<int32_t>(), nullptr, nullptr, nullptr};
     for (int k = 2; k < 5; k++) lists[k] = lists[1] + (size_t)(k - 1) * std::max<uint32_t>(c->n, 1);
     HIP_TRY(c, hipMemcpyAsync(c->one_model.p, best_model, sizeof(float) * 9, hipMemcpyHostToDevice, c->stream));
@@ -3166,95 +3413,41 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
     // four at once for a best model of <= 8192 inliers (cfg3 exact: 1.15 vs 1.20-1.28 ms per run
     // with groups of 2), two above (cfg5's 17 k-inlier fits: a rejected pass's no-op successors
     // cost 0.1 ms; profiles/r4c/ab_polish.txt, profiles/r5/polish_ab.txt)
-    constexpr int kPasses = 4;
     const int kGroup = [&] {
         const char *g = getenv("USAC_POLISH_GROUP");
         const int v = g ? atoi(g) : best.inlier_number <= 8192 ? 4 : 2;
         return v < 1 ? 1 : v > kPasses ? kPasses : v;
     }();
-    int32_t *cur = lists[0];
-    int32_t cur_cnt = 0;
+    cur = lists[0];
+    cur_cnt = 0;
     int prev = 0;
     bool stop = false;
-    // ransac.cpp:170-200 on the results of passes k0 .. k1 - 1 (pol_pin)
-    auto replay = [&](int k0, int k1) {
-        for (int k = k0; k < k1; k++) {
-            const float *r = hres + usac::kPolPass * k;
-            memcpy(&ok, r + 9, sizeof(int32_t));
-            memcpy(&cnt, r + 10, sizeof(int32_t));
-            memcpy(&s, r + 11, sizeof(float));
-            if (!ok || (double)((float)cnt / (float)best.inlier_number) < 0.8 || cnt <= prev) {
-                stop = true;
-                break;
-            }
-            prev = cnt;
-            best.inlier_number = cnt;
-            best.score = s;
-            memcpy(best_model, r, sizeof(best_model));
-            cur = lists[k + 1];
-            cur_cnt = cnt;
-            out->polish_passes++;
-        }
-    };
     int k_first = 0;  // the first pass for the multi-launch path
     const bool finish_score = c->estimator != USAC_LINE2D && c->n <= usac::kPolPtsMax;
     if (fused) {
-        HIP_TRY(c, hipMemcpyAsync(c->pol_pin, dres, sizeof(float) * usac::kPolWords, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->pol_pin.p, dres, sizeof(float) * usac::kPolWords, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, stream_wait(c->stream));
         memcpy(&cur_cnt, hres + 12, sizeof(int32_t));
         memcpy(&k_first, hres + usac::kPolStop, sizeof(int32_t));
         if (k_first < 0 || k_first > kPasses) return fail(c, USAC_ERR_HIP, "fused polish: bad pass count");
-        replay(0, k_first);
-        if (pol_prof) {  // the fused polish's phases (us): getInliers, then per pass gather, means,
-            // distance terms, distances, A^T A, finish, score, Σerr
-            uint64_t st[64] = {0};
-            HIP_TRY(c, hipMemcpy(st, c->partial.p, sizeof(st), hipMemcpyDeviceToHost));
-            fprintf(stderr, "polish_fused us: init %.1f %.1f |", (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01);
-            uint64_t last = st[2];
-            for (int k = 0; k < k_first; k++) {
-                for (int i = 0; i < 8; i++) {
-                    const uint64_t v = st[3 + 8 * k + i];
-                    fprintf(stderr, " %.1f", v >= last ? (v - last) * 0.01 : -1.0);
-                    if (v >= last) last = v;
-                }
-                fprintf(stderr, " |");
-            }
-            fprintf(stderr, " walked segments: 4ch %llu 2ch %llu 1ch %llu\n", (unsigned long long)st[44],
-                    (unsigned long long)st[42], (unsigned long long)st[41]);
-        }
+        polish_replay(0, k_first, hres, lists, prev, stop);
+        if (pol_prof && (rc = polish_fused_profile(k_first))) return rc;
     }
     for (int k0 = k_first; k0 < kPasses && !stop; k0 += kGroup) {
         const int k1 = std::min(k0 + kGroup, kPasses);
-        for (int k = k0; k < k1; k++) {
-            float *pres = dres + usac::kPolPass * k;
-            int32_t *dok = dres_i + usac::kPolPass * k + 9;
-            // the pass's finish, scoring and acceptance in one workgroup (k_finish_score) when the
-            // points fit its LDS and the fit takes the multi-launch path
-            const uint32_t nfit = k == 0 ? (uint32_t)best.inlier_number : c->n;
-            const bool fs = finish_score && nfit > usac::kSmallFitMax;
-            usac::NmBatch nb{};
-            if (k == 0)
-                HIP_TRY(c, enqueue_nonminimal(c, lists[0], nfit, pres, dok, nullptr, nullptr, fs ? &nb : nullptr));
-            else  // the count pass k - 1's acceptance left on the device; c->n bounds it
-                HIP_TRY(c, enqueue_nonminimal(c, lists[k], nfit, pres, dok, nullptr,
-                                              reinterpret_cast<const uint32_t *>(dres_i + usac::kPolNs + k),
-                                              fs ? &nb : nullptr));
-            if (fs) {
-                HIP_TRY(c, usac::launch_finish_score(c->stream, c->estimator, nb, c->pts.p, c->n, thr, lists[k + 1],
-                                                     dok + 1, pres + 11, dres_i, k + 1 < kPasses ? k : -1,
-                                                     best.inlier_number));
-                continue;
-            }
-            HIP_TRY(c, usac::launch_inliers_batch(c->stream, c->estimator, c->pts.p, c->n, pres, 1, thr, nullptr,
-                                                  nullptr, lists[k + 1], 0, dok + 1, pres + 11, c->inl_scratch.p, dok));
-            if (k + 1 < kPasses) HIP_TRY(c, usac::launch_polish_prep(c->stream, dres_i, k, best.inlier_number));
-        }
-        HIP_TRY(c, hipMemcpyAsync(c->pol_pin, dres, sizeof(float) * usac::kPolPass * k1, hipMemcpyDeviceToHost,
+        for (int k = k0; k < k1; k++)
+            if ((rc = polish_pass(k, dres, dres_i, lists, finish_score))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->pol_pin.p, dres, sizeof(float) * usac::kPolPass * k1, hipMemcpyDeviceToHost,
                                   c->stream));
         HIP_TRY(c, stream_wait(c->stream));
         if (k0 == 0) memcpy(&cur_cnt, hres + 12, sizeof(int32_t));
-        replay(k0, k1);
+        polish_replay(k0, k1, hres, lists, prev, stop);
     }
+    return USAC_OK;
+}
+
+// 11. The USAC_PROFILE line, the inlier list and the last out fields.
+int RansacRun::emit() {
     const auto t1 = std::chrono::steady_clock::now();
     lap(T_POLISH);
     if (getenv("USAC_PROFILE"))
@@ -3278,6 +3471,52 @@ static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int 
     out->inliers = best.inlier_number;
     out->time_us = std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
     return USAC_OK;
+}
+
+}  // namespace
+
+// Ransac::run with each batch's hypotheses sharded over nranks (SURVEY §8(e)): every rank
+// draws the same host sample stream, solves and scores only its contiguous slice of the
+// batch, and the slices' per-slot counts and models are all-gathered (gather(), or RCCL on
+// the context's communicator when gather is null); the replay -- records, termination, LO,
+// polish -- then runs on the merged batch identically on every rank (ransac.cpp:58-139 order).
+static int ransac_run_impl(usac_ctx *c, const usac_params *prm, int nranks, int rank, usac_allgather_fn gather,
+                           void *gather_user, usac_run_output *out, int32_t *inliers_out, usac_record *records,
+                           uint32_t rec_cap) {
+    if (!c || !prm || !out || nranks < 1 || rank < 0 || rank >= nranks) return USAC_ERR_ARG;
+    memset(out, 0, sizeof(*out));
+    // what the run changes in the context goes back on every exit, after the run's state is gone
+    struct H16Off {
+        usac_ctx *c;
+        bool saved;
+        ~H16Off() { c->h16_off = saved; }
+    } h16_off{c, c->h16_off};
+    struct Restore {
+        usac_ctx *c;
+        int mode;
+        bool sprt;
+        ~Restore() {
+            c->dlt_mode = mode;
+            c->sprt_on = sprt;
+        }
+    } restore{c, c->dlt_mode, c->sprt_on};
+    RansacRun r(c, prm, nranks, rank, gather, gather_user, out, inliers_out, records, rec_cap);
+    int rc;
+    if ((rc = r.check_params())) return rc;
+    if ((rc = r.begin())) return rc;
+    if ((rc = r.construct())) return rc;
+    if ((rc = r.host_buffers())) return rc;
+    while (r.iters < r.max_iters) {
+        if ((rc = r.take_speculation())) return rc;
+        r.draw();
+        if ((rc = r.device_batch())) return rc;
+        if ((rc = r.speculate_next())) return rc;
+        if ((rc = r.sums())) return rc;
+        if ((rc = r.replay())) return rc;
+    }
+    if ((rc = r.finish())) return rc;
+    if ((rc = r.polish())) return rc;
+    return r.emit();
 }
 
 int usac_ransac_run(usac_ctx *c, const usac_params *prm, usac_run_output *out, int32_t *inliers_out,
@@ -3335,9 +3574,8 @@ int usac_exchange_best_async(usac_ctx *c, usac_ctx *batch, uint32_t slot) {
             HIP_TRY(c, StreamPool::get().event(&c->xev_done[k]));
         }
         HIP_TRY(c, c->xring.reserve(sizeof(usac_record) * (size_t)USAC_XRING * (size_t)(c->nranks + 1)));
-        c->xring_host = static_cast<usac_record *>(
-            PinnedPool::get().take(sizeof(usac_record) * (size_t)USAC_XRING * (size_t)c->nranks, &c->xring_host_bytes));
-        if (!c->xring_host) return fail(c, USAC_ERR_HIP, "pinned host allocation failed");
+        if (!pin_grow(c->xring_host, sizeof(usac_record) * (size_t)USAC_XRING * (size_t)c->nranks))
+            return fail(c, USAC_ERR_HIP, "pinned host allocation failed");
     }
     // the batch's argmax record is copied into the ring's send slot on the batch stream (the
     // batch's next use of that stream overwrites its record); the exchange stream waits for
@@ -3352,7 +3590,7 @@ int usac_exchange_best_async(usac_ctx *c, usac_ctx *batch, uint32_t slot) {
         c->coll_pending = false;
     }
     NCCL_TRY(c, ncclAllGather(dsend, dall, sizeof(usac_record), ncclUint8, c->comm, c->xstream));
-    HIP_TRY(c, hipMemcpyAsync(c->xring_host + (size_t)slot * c->nranks, dall, sizeof(usac_record) * (size_t)c->nranks,
+    HIP_TRY(c, hipMemcpyAsync(c->xring_records() + (size_t)slot * c->nranks, dall, sizeof(usac_record) * (size_t)c->nranks,
                               hipMemcpyDeviceToHost, c->xstream));
     HIP_TRY(c, hipEventRecord(c->xev_done[slot], c->xstream));
     c->x_last = (int)slot;
@@ -3368,7 +3606,7 @@ int usac_exchange_best_wait(usac_ctx *c, uint32_t slot, usac_record *all) {
         if (e != hipErrorNotReady) return fail(c, USAC_ERR_HIP, std::string("exchange: ") + hipGetErrorString(e));
         if ((spins & 1023u) == 1023u) std::this_thread::yield();
     }
-    memcpy(all, c->xring_host + (size_t)slot * c->nranks, sizeof(usac_record) * (size_t)c->nranks);
+    memcpy(all, c->xring_records() + (size_t)slot * c->nranks, sizeof(usac_record) * (size_t)c->nranks);
     return USAC_OK;
 }
 
@@ -3846,12 +4084,6 @@ void usac_lo_destroy(usac_lo *h) {
 //     all problems in one launch (kernels_multi_grid.hip) and kept for the cell size; the standard
 //     termination criterion; with LO, not with SPRT.
 
-// a pinned staging block (PinnedPool) that only grows
-struct PinBlock {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
 struct usac_multi {
     int device = 0;
     int estimator = 0;
@@ -3909,16 +4141,6 @@ int fail(usac_multi *mc, int code, const std::string &msg) {
     return code;
 }
 
-// at least `need` bytes in a pinned block; growing it moves it, so its users take the pointer afterwards
-int pin_grow(usac_multi *mc, PinBlock &b, size_t need) {
-    if (need <= b.bytes) return USAC_OK;
-    if (b.p) PinnedPool::get().give_back(b.p, b.bytes);
-    b.bytes = 0;
-    b.p = PinnedPool::get().take(need, &b.bytes);
-    if (!b.p) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
-    return USAC_OK;
-}
-
 bool multi_round_ok(uint32_t R) { return R >= 64 && R <= 8192 && R % 64 == 0; }
 
 bool multi_is_e(const usac_multi *mc) { return mc->estimator == USAC_ESSENTIAL; }
@@ -3953,7 +4175,9 @@ int multi_ensure(usac_multi *mc, uint32_t A, uint32_t R, bool host_samples) {
     }
     if (multi_is_e(mc))
         HIP_TRY(mc, mc->e5_ws.reserve(usac::multi_e5_workspace_bytes(A, R, usac::multi_e5_slice_samples(mc->e5_slice, R))));
-    return pin_grow(mc, mc->pin, (sizeof(usac::MultiItem) + sizeof(usac_record)) * (size_t)A);
+    if (!pin_grow(mc->pin, (sizeof(usac::MultiItem) + sizeof(usac_record)) * (size_t)A))
+        return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
+    return USAC_OK;
 }
 
 usac::MultiItem *multi_items_pin(usac_multi *mc) { return static_cast<usac::MultiItem *>(mc->pin.p); }
@@ -4050,8 +4274,7 @@ int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, c
                                           mask ? mc->mask.as<uint8_t>() : nullptr));
     // results and mask come down through pinned staging, then into the caller's (pageable) buffers
     const size_t out_bytes = sizeof(usac_multi_polish_output) * (size_t)P, need = out_bytes + (mask ? mc->n_total : 0);
-    int rc = pin_grow(mc, mc->pol_pin, need);
-    if (rc) return rc;
+    if (!pin_grow(mc->pol_pin, need)) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
     uint8_t *stage = static_cast<uint8_t *>(mc->pol_pin.p);
     HIP_TRY(mc, hipMemcpyAsync(stage, mc->pol_out.p, out_bytes, hipMemcpyDeviceToHost, mc->stream));
     if (mask) HIP_TRY(mc, hipMemcpyAsync(stage + out_bytes, mc->mask.p, mc->n_total, hipMemcpyDeviceToHost, mc->stream));
@@ -4060,8 +4283,8 @@ int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, c
     if (mask) memcpy(mask, stage + out_bytes, mc->n_total);
     for (uint32_t p = 0; p < P; p++) {
         if (out[p].status != usac::kMultiPolishDefer) continue;
-        rc = multi_polish_single(mc, p, hstart + (size_t)p * hstride, multi_thr_of(mc, p, thr), out + p,
-                                 mask ? mask + mc->offsets[p] : nullptr);
+        const int rc = multi_polish_single(mc, p, hstart + (size_t)p * hstride, multi_thr_of(mc, p, thr), out + p,
+                                           mask ? mask + mc->offsets[p] : nullptr);
         if (rc) return rc;
     }
     return USAC_OK;
@@ -4091,8 +4314,8 @@ int multi_prosac_ensure(usac_multi *mc) {
     HIP_TRY(mc, mc->non_random.reserve(bytes));
     HIP_TRY(mc, hipMemcpy(mc->growth.p, g.data(), bytes, hipMemcpyHostToDevice));
     HIP_TRY(mc, hipMemcpy(mc->non_random0.p, nr.data(), bytes, hipMemcpyHostToDevice));
-    const int rc = pin_grow(mc, mc->pro_pin, sizeof(uint32_t) * (2 * usac::multi_cand_capacity(mc->n_total, mc->P) + mc->P));
-    if (rc) return rc;
+    if (!pin_grow(mc->pro_pin, sizeof(uint32_t) * (2 * usac::multi_cand_capacity(mc->n_total, mc->P) + mc->P)))
+        return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
     mc->growth_host.swap(tabs);
     return USAC_OK;
 }
@@ -4278,8 +4501,10 @@ int multi_sprt_ensure(usac_multi *mc, uint32_t A, uint32_t R, bool starts) {
     HIP_TRY(mc, mc->out.reserve((sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A));
     HIP_TRY(mc, mc->sprt_surv.reserve(usac::multi_sprt_survivor_bytes() * S));
     if (starts) HIP_TRY(mc, mc->sprt_starts.reserve(sizeof(uint32_t) * S));
-    return pin_grow(mc, mc->sprt_pin,
-                    (sizeof(usac::SprtConsts) + sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A);
+    if (!pin_grow(mc->sprt_pin,
+                  (sizeof(usac::SprtConsts) + sizeof(usac_record) + sizeof(usac_multi_sprt_stats)) * (size_t)A))
+        return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
+    return USAC_OK;
 }
 static_assert(sizeof(usac_record) % 8 == 0 && sizeof(usac::SprtConsts) % 8 == 0 && sizeof(usac_multi_sprt_stats) == 32,
               "the records, then the statistics, 8-byte aligned");
@@ -4354,8 +4579,7 @@ int multi_grid_ensure(usac_multi *mc, int cs) {
     const size_t N = mc->n_total, P = mc->P;
     HIP_TRY(mc, hipSetDevice(mc->device));
     HIP_TRY(mc, mc->grid.reserve(sizeof(uint32_t) * (5 * N + 4 * P)));
-    int rc = pin_grow(mc, mc->pin, sizeof(uint32_t) * 3 * P);
-    if (rc) return rc;
+    if (!pin_grow(mc->pin, sizeof(uint32_t) * 3 * P)) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
     mc->grid_cs = 0;
     const usac::MultiGrid g = multi_grid_args(mc);
     HIP_TRY(mc, usac::launch_multi_grid(mc->stream, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), mc->P, cs, mc->m, g));
@@ -4364,7 +4588,10 @@ int multi_grid_ensure(usac_multi *mc, int cs) {
     const uint32_t *down = static_cast<const uint32_t *>(mc->pin.p);
     mc->grid_counts.assign(down, down + 3 * P);
     for (uint32_t p = 0; p < mc->P; p++)
-        if (mc->grid_counts[p] == usac::kMultiGridDefer && (rc = multi_grid_single(mc, g, p, cs))) return rc;
+        if (mc->grid_counts[p] == usac::kMultiGridDefer) {
+            const int rc = multi_grid_single(mc, g, p, cs);
+            if (rc) return rc;
+        }
     mc->grid_cs = cs;
     return USAC_OK;
 }
@@ -5032,8 +5259,7 @@ void usac_multi_destroy(usac_multi *mc) {
     if (!mc) return;
     (void)hipSetDevice(mc->device);
     if (mc->stream) (void)hipStreamSynchronize(mc->stream);
-    for (PinBlock *b : {&mc->pin, &mc->pol_pin, &mc->pro_pin, &mc->sprt_pin})
-        if (b->p) PinnedPool::get().give_back(b->p, b->bytes);
+    for (PinBlock *b : {&mc->pin, &mc->pol_pin, &mc->pro_pin, &mc->sprt_pin}) pin_release(*b);
     for (DevBuf *b : {&mc->growth, &mc->non_random0, &mc->non_random, &mc->grid}) b->release();
     for (DevBuf *b : {&mc->sprt_pts, &mc->sprt_idx, &mc->sprt_consts, &mc->sprt_surv, &mc->sprt_surv_n, &mc->sprt_starts})
         b->release();
