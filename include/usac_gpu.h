@@ -83,7 +83,11 @@
  *                                  and usac_multi_padded_mask, a host mask scattered into P x n_max device bytes;
  *                                  ABI 26: usac_multi_create_device_sorted, the same context with every problem's
  *                                  kept rows sorted on the device by a score per column, the better first, so
- *                                  that usac_multi_run_prosac runs on a matcher's output as it is
+ *                                  that usac_multi_run_prosac runs on a matcher's output as it is;
+ *                                  ABI 27: usac_multi_export_device, the result of the last polishing call --
+ *                                  models, counts, the padded mask, the inliers' columns, pixel-space models --
+ *                                  written into device memory on the caller's stream, and usac_multi_set_resident,
+ *                                  polishing calls that bring no mask to the host
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -98,7 +102,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 26
+#define USAC_ABI_VERSION 27
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -660,10 +664,60 @@ int usac_multi_get_source(usac_multi *mc, uint32_t *src);
  * usac_multi_inliers, usac_multi_polish or a polished run wrote; d_out: P x n_max bytes of device memory of the
  * context's device (checked as usac_multi_create_device's pointers).  out[p, src[i]] = mask[i], every other cell
  * 0.  The upload, the memset and the scatter are enqueued on `stream` (a hipStream_t; NULL: the null stream) and
- * the call waits for it.  Stateless: the host mask is the one source that is right for a problem the polish
- * deferred to its host path.  USAC_ERR_UNSUPPORTED on a context not created by usac_multi_create_device,
- * USAC_ERR_ARG for a NULL mc, mask or d_out. */
+ * the call waits for it.  Stateless: it scatters the host mask it is given, whichever call wrote it, and its
+ * upload ends the context's resident result; usac_multi_export_device (ABI 27) is the alternative that writes
+ * the last polishing call's mask from the device, with nothing N_total-sized crossing.  USAC_ERR_UNSUPPORTED on
+ * a context not created by usac_multi_create_device, USAC_ERR_ARG for a NULL mc, mask or d_out. */
 int usac_multi_padded_mask(usac_multi *mc, const uint8_t *mask, uint8_t *d_out, void *stream);
+/* Device output (ABI 27).  A multi context remembers that its device buffers hold the complete result of its
+ * last polishing call: usac_multi_polish, usac_multi_run_polished, or usac_multi_run_prosac, _run_lo,
+ * _run_lo_essential, _run_sprt or _run_napsac with a non-NULL pol.  Complete includes the problems the polish
+ * defers to its host path (more than 16 384 points, or a list to fit above 4 096): their results and mask bytes
+ * are written back to the device, so the resident bytes equal what the caller received.  The result stops being
+ * valid through usac_multi_inliers and usac_multi_padded_mask (both write the mask buffer), through a polishing
+ * call that computed no mask (mask == NULL with resident mode off), and through a polishing call that failed
+ * after it passed its argument checks (a call refused for its arguments changes nothing).
+ * usac_multi_set_resident: resident mode, off at creation.  While on, a polishing call whose mask argument is
+ * NULL still computes the device mask (a deferred problem's on the host, uploaded) and copies no mask to the
+ * host: nothing N_total-sized crosses.  While off every call behaves as before ABI 27.  Returns USAC_OK, or
+ * USAC_ERR_ARG for a NULL mc. */
+int usac_multi_set_resident(usac_multi *mc, int on);
+typedef struct usac_multi_device_output {
+    uint32_t n_max;        /* columns per problem of mask */
+    uint32_t k_max;        /* entries per problem of inlier_cols; 0 with a NULL inlier_cols */
+    float   *models;       /* DEVICE, P x 9: the polished model (usac_multi_polish_output.model) */
+    float   *pixel_models; /* DEVICE, P x 9: F_p = K2_p^-T E_p K1_p^-1, contexts with intrinsics only */
+    int32_t *inliers;      /* DEVICE, P: the polished model's inlier count, never truncated */
+    int32_t *status;       /* DEVICE, P: usac_multi_polish_output.status */
+    uint8_t *mask;         /* DEVICE, P x n_max bytes of 0 / 1 */
+    int32_t *inlier_cols;  /* DEVICE, P x k_max: the inliers' columns, -1 behind the last */
+    void    *stream;       /* hipStream_t the writes are enqueued on; NULL: the null stream */
+} usac_multi_device_output;
+/* The resident result of the last polishing call, written into the caller's device memory by one launch on
+ * o->stream (one workgroup per problem, no memset before it); the call waits for that stream.  Every pointer is
+ * nullable, not all of them.
+ *   mask[p, src[offsets[p] + i]] = the resident mask byte of packed row offsets[p] + i, every other cell of row p
+ *     0: what usac_multi_padded_mask writes from the host mask.
+ *   inlier_cols[p, :]: the columns src[offsets[p] + i] of problem p's inlier rows in packed-row order -- ascending
+ *     columns on a context from usac_multi_create_device, quality order on one from
+ *     usac_multi_create_device_sorted.  The first min(inliers[p], k_max) are written, every later entry is -1;
+ *     inliers[p] stays the full count, so a truncation shows.
+ *   A context created from the host has no src: its source is the identity, a column is an index local to the
+ *     problem, and n_max may be any value >= max n_p.  A context from device input demands its own n_max.
+ *   pixel_models: the bits usac_multi_pixel_models returns for the exported models (fp64, the closed-form
+ *     inverse of K, G = E K1^-1 then F = K2^-T G, three-term sums left to right, one cast to fp32), on a context
+ *     with intrinsics (usac_multi_create_essential_pixels, usac_multi_create_device with K1).  The intrinsics go
+ *     to the device once, at the first export that asks for them.
+ *   A problem with USAC_ERR_NO_MODEL exports its start model, a count of 0, a zero mask row and a row of -1: the
+ *     resident bytes.
+ * USAC_ERR_ARG before any device call: a NULL mc or o, every pointer NULL, n_max == 0 or not the context's (from
+ * the host: below max n_p), k_max == 0 with inlier_cols or k_max != 0 without, P * n_max or P * k_max >= 2^32.
+ * USAC_ERR_UNSUPPORTED before any device call: no valid resident result (the message names the call that ended
+ * it, or says that no polishing call has run); pixel_models on a context without intrinsics.  USAC_ERR_ARG before
+ * any launch, nothing written: a pointer that is not device memory of the context's device, is misaligned (4
+ * bytes for the float and int arrays), or whose allocation is too short.  The reason is what
+ * usac_multi_last_error returns. */
+int usac_multi_export_device(usac_multi *mc, const usac_multi_device_output *o);
 void usac_multi_destroy(usac_multi *mc);
 /* The message of the context's last failed call; mc == NULL: "null context", or see usac_multi_create_device. */
 const char *usac_multi_last_error(const usac_multi *mc);

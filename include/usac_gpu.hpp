@@ -682,6 +682,19 @@ public:
             throw Error(USAC_ERR_ARG, "paddedMask: N_total mask bytes");
         check(usac_multi_padded_mask(mc_, mask.data(), d_out, stream), "MultiContext::paddedMask");
     }
+    // usac_multi_set_resident (ABI 27): while on, a polishing call given no host mask still leaves its mask on
+    // the device for exportDevice, and nothing N_total-sized comes down
+    void setResident(bool on) const { check(usac_multi_set_resident(mc_, on ? 1 : 0), "MultiContext::setResident"); }
+    // usac_multi_export_device (ABI 27): the result of the last polishing call (polish, runPolished, ...) written
+    // into the device memory o names -- models, counts, statuses, the P x n_max mask, the inliers' columns padded
+    // with -1, pixel-space models -- by one launch on o.stream, which the call waits for.  Every pointer of o is
+    // nullable; o.n_max is paddedWidth() on a context from fromDevice, any width >= the largest problem on one
+    // from the host (columns are then local indices).  Throws USAC_ERR_UNSUPPORTED when no polishing call's
+    // result is resident any more (the message names what ended it), USAC_ERR_ARG for a pointer that is not
+    // device memory of the context's device, misaligned or too short.
+    void exportDevice(const usac_multi_device_output &o) const {
+        check(usac_multi_export_device(mc_, &o), "MultiContext::exportDevice");
+    }
 
     // one round of R hypotheses (a multiple of 64 in 64..8192) for the listed problems (empty: all,
     // in order), device sampler keyed by seeds[i] for problems[i]; with per_hypothesis the counts

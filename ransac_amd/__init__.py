@@ -191,6 +191,13 @@ class _MultiDeviceOrder(ctypes.Structure):
     _fields_ = [("scores", ctypes.c_void_p), ("descending", ctypes.c_int)]
 
 
+class _MultiDeviceOutput(ctypes.Structure):
+    """usac_multi_device_output (ABI 27): the widths, the output device pointers as integers, the stream"""
+    _fields_ = [("n_max", ctypes.c_uint32), ("k_max", ctypes.c_uint32), ("models", ctypes.c_void_p),
+                ("pixel_models", ctypes.c_void_p), ("inliers", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("mask", ctypes.c_void_p), ("inlier_cols", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -222,6 +229,7 @@ ABI_SYMBOLS = [
     "usac_multi_get_points",
     "usac_multi_create_device", "usac_multi_get_offsets", "usac_multi_get_source", "usac_multi_padded_mask",
     "usac_multi_create_device_sorted",
+    "usac_multi_set_resident", "usac_multi_export_device",
 ]
 
 
@@ -331,6 +339,8 @@ def lib():
         "usac_multi_get_offsets": (ctypes.c_int, [_vp, u32p]),
         "usac_multi_get_source": (ctypes.c_int, [_vp, u32p]),
         "usac_multi_padded_mask": (ctypes.c_int, [_vp, u8p, _vp, _vp]),
+        "usac_multi_set_resident": (ctypes.c_int, [_vp, ctypes.c_int]),
+        "usac_multi_export_device": (ctypes.c_int, [_vp, _P(_MultiDeviceOutput)]),
         "usac_multi_destroy": (None, [_vp]),
         "usac_multi_last_error": (ctypes.c_char_p, [_vp]),
         "usac_multi_num_problems": (ctypes.c_uint32, [_vp]),
@@ -875,12 +885,17 @@ class MultiContext:
     (P, n_max) device tensor.  With scores=(P, n_max) float32 device tensor (usac_multi_create_device_sorted) the
     device also sorts every problem's kept rows by score, the better first and ties in column order: the input
     run_prosac expects, from a matcher's output as it is.  `sorted_by_score` is then True, `source_index` is in
-    that order, and padded_mask() still lands every bit on its column."""
+    that order, and padded_mask() still lands every bit on its column.
+
+    export_device() (usac_multi_export_device) hands the result of the last polishing call over as device tensors
+    -- models, counts, the padded mask, the inliers' columns -- without a trip through the host, on any multi
+    context; with keep_on_device = True the polishing calls bring no mask down in the first place."""
 
     inlier_lists = True  # False: polish(with_inliers=True) and the polished runs return no index lists
     last_mask = None     # the N_total host mask bytes of the last call that computed inliers
     n_max = None         # the padded width of a context from device input
     sorted_by_score = False  # True: from_padded / from_matches with scores, the rows are in quality order
+    _keep_on_device = False  # keep_on_device: polishing calls leave their mask on the device (export_device)
     device = 0
 
     def __init__(self, estimator, point_sets, device=0):
@@ -1100,6 +1115,68 @@ class MultiContext:
             return out.view(torch.bool)
         return out
 
+    @property
+    def keep_on_device(self):
+        """usac_multi_set_resident: while True, polish() and the polished runs bring no mask to the host -- the
+        mask stays on the device for export_device(), `last_mask` is not set and no index lists are built."""
+        return self._keep_on_device
+
+    @keep_on_device.setter
+    def keep_on_device(self, on):
+        self._check(lib().usac_multi_set_resident(self._h, 1 if on else 0), "multi_set_resident")
+        self._keep_on_device = bool(on)
+
+    def export_device(self, mask=True, inlier_cols=None, pixel_models=False, n_max=None, out=None, stream=None):
+        """usac_multi_export_device: the result of the last polishing call (polish, or a run with polish=True) as
+        tensors on the context's device, written by one launch: "models" (P, 3, 3) float32, "inliers" (P,) int32
+        (the full counts), "status" (P,) int32, and, as asked for, "mask" (P, n_max) bool, "inlier_cols" (P, k)
+        int32 with inlier_cols=k (the inliers' columns in packed-row order, the first k of them, -1 behind the
+        last) and "pixel_models" (P, 3, 3) float32 (a context with intrinsics).  n_max: the context's padded width
+        (the default, and the only value a context from device input takes); on a context from the host any
+        width >= the largest problem, default that size, and columns are local indices.  out: a dict of caller
+        tensors under the same keys, written instead of fresh ones and returned as they are (mask: uint8 or
+        bool).  stream: as padded_mask's; the call waits for it.  UsacError(-3) when no polishing call's result
+        is resident (the message says what ended it), or for pixel_models without intrinsics."""
+        P = self.P
+        out = dict(out or {})
+        unknown = set(out) - {"models", "inliers", "status", "mask", "inlier_cols", "pixel_models"}
+        if unknown:
+            raise ValueError("export_device: unknown outputs %s" % sorted(unknown))
+        if n_max is None:
+            n_max = self.n_max if self.n_max is not None else int(self.sizes.max())
+        n_max = int(n_max)
+        k_max = None if inlier_cols is None else int(inlier_cols)
+        if k_max is None and "inlier_cols" in out:
+            k_max = _DevArray(out["inlier_cols"], "inlier_cols").need((P, None), ("i4",)).shape[1]
+        want = {"models": ((P, 3, 3), ("f4",)), "inliers": ((P,), ("i4",)), "status": ((P,), ("i4",))}
+        if mask or "mask" in out:
+            want["mask"] = ((P, n_max), ("u1", "b1"))
+        if k_max is not None:
+            want["inlier_cols"] = ((P, k_max), ("i4",))
+        if pixel_models or "pixel_models" in out:
+            want["pixel_models"] = ((P, 3, 3), ("f4",))
+        res, arrays = {}, {}
+        for key, (shape, kinds) in want.items():
+            fresh = key not in out
+            if fresh:
+                import torch
+
+                dt = {"f4": torch.float32, "i4": torch.int32, "u1": torch.uint8}[kinds[0]]
+                out[key] = torch.empty(shape, dtype=dt, device="cuda:%d" % self.device)
+            arrays[key] = _DevArray(out[key], key).need(shape, kinds)
+            res[key] = out[key].view(torch.bool) if fresh and key == "mask" else out[key]
+        if stream is None:
+            stream = 0
+            first = next(iter(arrays.values()))
+            if first.torch:
+                import torch
+
+                stream = torch.cuda.current_stream(first.obj.device).cuda_stream
+        o = _MultiDeviceOutput(n_max=n_max, k_max=k_max or 0, stream=int(stream) or None,
+                               **{key: a.ptr for key, a in arrays.items()})
+        self._check(lib().usac_multi_export_device(self._h, ctypes.byref(o)), "multi_export_device")
+        return res
+
     def resident_points(self):
         """usac_multi_get_points: the N_total x 4 rows resident on the device (a copy)."""
         out = np.zeros((int(self.offsets[-1]), 4), dtype=np.float32)
@@ -1219,6 +1296,7 @@ class MultiContext:
         model, ascending indices local to the problem."""
         m = np.ascontiguousarray(models, dtype=np.float32).reshape(self.P, 9)
         out = (_MultiPolishOutput * self.P)()
+        with_inliers = with_inliers and not self._keep_on_device  # keep_on_device: the mask stays on the device
         mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if with_inliers else None
         self._check(lib().usac_multi_polish(self._h, _ptr(m, ctypes.c_float), ctypes.c_float(thr), out,
                                             _ptr(mask, ctypes.c_uint8)), "multi_polish")
@@ -1251,7 +1329,8 @@ class MultiContext:
         ex = (own[1] * self.P)() if own and (len(own) < 3 or own[2]) else None  # own[2] False: a NULL argument
         pro = (_MultiProsacOutput * self.P)() if prosac else None
         pol = (_MultiPolishOutput * self.P)() if polish else None
-        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if polish else None
+        host_mask = polish and not self._keep_on_device  # keep_on_device: the mask stays on the device
+        mask = np.zeros(int(self.offsets[-1]), dtype=np.uint8) if host_mask else None
         args = ([ex] if own else []) + ([pro] if prosac else [])
         if name != "run":
             args += [pol, _ptr(mask, ctypes.c_uint8)]
@@ -1267,10 +1346,11 @@ class MultiContext:
                 r.update(termination_length=int(q.termination_length), largest_sample_size=int(q.largest_sample_size),
                          clock=int(q.clock), scans=int(q.scans))
         if polish:
-            self.last_mask = mask
+            if host_mask:
+                self.last_mask = mask
             for r, po in zip(res, _MultiPolishOutput.as_dicts(pol)):
                 r["polished"] = po
-        if polish and self.inlier_lists:
+        if host_mask and self.inlier_lists:
             for r, idx in zip(res, self._split_mask(mask)):
                 r["inliers"] = idx
         return res

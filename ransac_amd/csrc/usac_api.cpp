@@ -4131,6 +4131,13 @@ struct usac_multi {
     // packed row, the column it came from (N_total values on the device); else n_max is 0 and src is empty
     uint32_t n_max = 0;
     DevBuf src;
+    // Device output (ABI 27): resident_valid says that pol_out and mask hold the complete result of the last
+    // polishing call; resident_end names what ended that otherwise (nullptr: no polishing call has run).
+    // resident_on: polishing calls compute the device mask without a host mask (usac_multi_set_resident).
+    // kdev: the intrinsics of a context that has them, P x 9 of view 1 then of view 2, at the first export
+    bool resident_on = false, resident_valid = false;
+    const char *resident_end = nullptr;
+    DevBuf kdev;
     std::string err;
 };
 
@@ -4139,6 +4146,12 @@ namespace {
 int fail(usac_multi *mc, int code, const std::string &msg) {
     if (mc) mc->err = msg;
     return code;
+}
+
+// the resident result (ABI 27) ends: by, the call that wrote over it or left it incomplete
+void multi_resident_end(usac_multi *mc, const char *by) {
+    mc->resident_valid = false;
+    mc->resident_end = by;
 }
 
 bool multi_round_ok(uint32_t R) { return R >= 64 && R <= 8192 && R % 64 == 0; }
@@ -4265,13 +4278,16 @@ int multi_polish_single(usac_multi *mc, uint32_t p, const float *start, float th
 int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, const float *hstart, size_t hstride,
                         float thr, usac_multi_polish_output *out, uint8_t *mask) {
     const uint32_t P = mc->P;
+    // the device mask: for the caller's host mask, or (resident mode, ABI 27) to stay where it is
+    const bool dmask = mask || mc->resident_on;
+    multi_resident_end(mc, "a polishing call that failed");  // until this one has finished
     HIP_TRY(mc, mc->pol_lists.reserve(sizeof(int32_t) * 2 * (size_t)mc->n_total));
     HIP_TRY(mc, mc->pol_out.reserve(sizeof(usac_multi_polish_output) * (size_t)P));
-    if (mask) HIP_TRY(mc, mc->mask.reserve(mc->n_total));
+    if (dmask) HIP_TRY(mc, mc->mask.reserve(mc->n_total));
     HIP_TRY(mc, usac::launch_multi_polish(mc->stream, mc->estimator, mc->pts.as<float4>(), mc->offs.as<uint32_t>(), P,
                                           mc->n_total, dmodels, stride, thr, multi_thrs(mc), mc->pol_lists.as<int32_t>(),
                                           mc->pol_out.as<usac_multi_polish_output>(),
-                                          mask ? mc->mask.as<uint8_t>() : nullptr));
+                                          dmask ? mc->mask.as<uint8_t>() : nullptr));
     // results and mask come down through pinned staging, then into the caller's (pageable) buffers
     const size_t out_bytes = sizeof(usac_multi_polish_output) * (size_t)P, need = out_bytes + (mask ? mc->n_total : 0);
     if (!pin_grow(mc->pol_pin, need)) return fail(mc, USAC_ERR_HIP, "hipHostMalloc failed");
@@ -4281,12 +4297,25 @@ int multi_polish_device(usac_multi *mc, const float *dmodels, uint32_t stride, c
     HIP_TRY(mc, stream_wait(mc->stream));
     memcpy(out, stage, out_bytes);
     if (mask) memcpy(mask, stage + out_bytes, mc->n_total);
+    std::vector<uint8_t> tmp;  // resident mode without a host mask: a deferred problem's mask bytes
     for (uint32_t p = 0; p < P; p++) {
         if (out[p].status != usac::kMultiPolishDefer) continue;
-        const int rc = multi_polish_single(mc, p, hstart + (size_t)p * hstride, multi_thr_of(mc, p, thr), out + p,
-                                           mask ? mask + mc->offsets[p] : nullptr);
+        const uint32_t base = mc->offsets[p], n = mc->offsets[p + 1] - base;
+        uint8_t *mask_p = mask ? mask + base : nullptr;
+        if (!mask && dmask) {
+            tmp.resize(n);
+            mask_p = tmp.data();
+        }
+        const int rc = multi_polish_single(mc, p, hstart + (size_t)p * hstride, multi_thr_of(mc, p, thr), out + p, mask_p);
         if (rc) return rc;
+        if (!dmask) continue;
+        // the resident result is complete (ABI 27): what the host path computed goes back to the device
+        HIP_TRY(mc, hipMemcpy(mc->pol_out.as<usac_multi_polish_output>() + p, out + p, sizeof(usac_multi_polish_output),
+                              hipMemcpyHostToDevice));
+        HIP_TRY(mc, hipMemcpy(mc->mask.as<uint8_t>() + base, mask_p, n, hipMemcpyHostToDevice));
     }
+    if (dmask) mc->resident_valid = true;
+    else multi_resident_end(mc, "a polishing call that computed no mask (a NULL mask with resident mode off)");
     return USAC_OK;
 }
 
@@ -4727,6 +4756,8 @@ int multi_run_driver(usac_multi *mc, const usac_params *prm, const uint64_t *see
     if (sprt && !multi_sprt_cert(margin, climb))
         return fail(mc, USAC_ERR_ARG, "SPRT certificate: margin >= 1e-7 and 0 < climb <= 700");
     HIP_TRY(mc, hipSetDevice(mc->device));
+    // a polishing run has passed its checks: the resident result (ABI 27) is this run's from here on
+    if (outs.pol) multi_resident_end(mc, "a polishing call that failed");
     // the buffers; a run starts with fresh LO and PROSAC state
     int rc = napsac ? multi_grid_ensure(mc, prm->cell_size) : USAC_OK;
     const usac::MultiGrid mg = napsac ? multi_grid_args(mc) : usac::MultiGrid{};
@@ -5246,11 +5277,92 @@ int usac_multi_padded_mask(usac_multi *mc, const uint8_t *mask, uint8_t *d_out, 
     if (!why.empty()) return fail(mc, USAC_ERR_ARG, "usac_multi_padded_mask: " + why);
     hipStream_t cs = static_cast<hipStream_t>(stream);
     // every call of this context has waited for its stream: mc->mask is free to stage the upload
+    multi_resident_end(mc, "usac_multi_padded_mask (its upload staged a host mask in the mask buffer)");
     HIP_TRY(mc, mc->mask.reserve(mc->n_total));
     HIP_TRY(mc, hipMemcpyAsync(mc->mask.p, mask, mc->n_total, hipMemcpyHostToDevice, cs));
     HIP_TRY(mc, hipMemsetAsync(d_out, 0, cells, cs));
     HIP_TRY(mc, usac::launch_multi_unpack_mask(cs, mc->mask.as<uint8_t>(), mc->src.as<uint32_t>(), mc->offs.as<uint32_t>(),
                                                mc->P, mc->n_total, mc->n_max, d_out));
+    HIP_TRY(mc, stream_wait(cs));
+    return USAC_OK;
+}
+
+// ---- device output (ABI 27)
+int usac_multi_set_resident(usac_multi *mc, int on) {
+    if (!mc) return USAC_ERR_ARG;
+    mc->resident_on = on != 0;
+    return USAC_OK;
+}
+
+int usac_multi_export_device(usac_multi *mc, const usac_multi_device_output *o) {
+    const char *who = "usac_multi_export_device: ";
+    if (!mc) return USAC_ERR_ARG;
+    if (!o) return fail(mc, USAC_ERR_ARG, std::string(who) + "NULL output");
+    if (!o->models && !o->pixel_models && !o->inliers && !o->status && !o->mask && !o->inlier_cols)
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "every output pointer is NULL");
+    const uint32_t P = mc->P;
+    if (mc->n_max) {
+        if (o->n_max != mc->n_max)
+            return fail(mc, USAC_ERR_ARG, std::string(who) + "n_max must be the context's, " + std::to_string(mc->n_max));
+    } else {  // from the host: the identity is the source, and every local index must have its column
+        uint32_t widest = 0;
+        for (uint32_t p = 0; p < P; p++) widest = std::max(widest, mc->offsets[p + 1] - mc->offsets[p]);
+        if (o->n_max < widest)
+            return fail(mc, USAC_ERR_ARG, std::string(who) + "n_max must be at least the largest problem's size, " +
+                                              std::to_string(widest));
+    }
+    if ((o->inlier_cols != nullptr) != (o->k_max != 0))
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "k_max > 0 goes with inlier_cols, and 0 with a NULL inlier_cols");
+    if (!usac::export_extent_ok(P, o->n_max, o->k_max))
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "n_max must be > 0, P * n_max and P * k_max < 2^32");
+    if (!mc->resident_valid)
+        return fail(mc, USAC_ERR_UNSUPPORTED,
+                    std::string(who) + (mc->resident_end ? std::string("the result of the last polishing call is no longer "
+                                                                       "resident: ended by ") + mc->resident_end
+                                                         : std::string("no polishing call has run on this context")));
+    if (o->pixel_models && mc->k1.empty())
+        return fail(mc, USAC_ERR_UNSUPPORTED, std::string(who) + "pixel_models: the context was not created with intrinsics "
+                                                  "(usac_multi_create_essential_pixels, usac_multi_create_device with K1)");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    // a host pointer must never reach the kernel: every pointer it will write, before the launch
+    const size_t cells = (size_t)P * o->n_max;
+    struct { const void *p; const char *name; size_t bytes, align; } ptrs[] = {
+        {o->models, "models", (size_t)P * 36, 4},   {o->pixel_models, "pixel_models", (size_t)P * 36, 4},
+        {o->inliers, "inliers", (size_t)P * 4, 4},  {o->status, "status", (size_t)P * 4, 4},
+        {o->mask, "mask", cells, 1},                {o->inlier_cols, "inlier_cols", (size_t)P * o->k_max * 4, 4}};
+    for (const auto &q : ptrs) {
+        if (!q.p) continue;
+        const std::string why = device_pointer_problem(q.p, q.name, mc->device, q.bytes, q.align);
+        if (!why.empty()) return fail(mc, USAC_ERR_ARG, std::string(who) + why);
+    }
+    if (o->pixel_models && !mc->kdev.p) {  // once: the intrinsics the context kept on the host
+        const size_t half = sizeof(float) * 9 * (size_t)P;
+        HIP_TRY(mc, mc->kdev.reserve(2 * half));
+        hipError_t e = hipMemcpy(mc->kdev.p, mc->k1.data(), half, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(static_cast<char *>(mc->kdev.p) + half, mc->k2.data(), half, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            mc->kdev.release();
+            HIP_TRY(mc, e);
+        }
+    }
+    usac::MultiExport a{};
+    a.pol = mc->pol_out.as<usac_multi_polish_output>();
+    a.mask = mc->mask.as<uint8_t>();
+    a.src = mc->n_max ? mc->src.as<uint32_t>() : nullptr;
+    a.offsets = mc->offs.as<uint32_t>();
+    a.k = mc->kdev.as<float>();
+    a.P = P;
+    a.n_max = o->n_max;
+    a.k_max = o->k_max;
+    a.models = o->models;
+    a.pixel_models = o->pixel_models;
+    a.inliers = o->inliers;
+    a.status = o->status;
+    a.mask_out = o->mask;
+    a.cols = o->inlier_cols;
+    // every call of this context has waited for its streams: the resident buffers are at rest, and stay so
+    hipStream_t cs = static_cast<hipStream_t>(o->stream);
+    HIP_TRY(mc, usac::launch_multi_export(cs, a));
     HIP_TRY(mc, stream_wait(cs));
     return USAC_OK;
 }
@@ -5265,7 +5377,7 @@ void usac_multi_destroy(usac_multi *mc) {
         b->release();
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
                       &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
-                      &mc->pol_out, &mc->lo_state, &mc->e5_ws, &mc->thrs, &mc->lo_steps, &mc->src})
+                      &mc->pol_out, &mc->lo_state, &mc->e5_ws, &mc->thrs, &mc->lo_steps, &mc->src, &mc->kdev})
         b->release();
     if (mc->stream) StreamPool::get().give_back(mc->stream);
     delete mc;
@@ -5374,6 +5486,7 @@ int usac_multi_inliers(usac_multi *mc, const float *models, float thr, uint8_t *
     HIP_TRY(mc, hipSetDevice(mc->device));
     HIP_TRY(mc, mc->mmodels.reserve(sizeof(float) * 9 * (size_t)mc->P));
     HIP_TRY(mc, mc->m18.reserve(sizeof(float) * 18 * (size_t)mc->P));
+    multi_resident_end(mc, "usac_multi_inliers (it wrote another mask into the mask buffer)");
     HIP_TRY(mc, mc->mask.reserve(mc->n_total));
     HIP_TRY(mc, hipMemcpyAsync(mc->mmodels.p, models, sizeof(float) * 9 * (size_t)mc->P, hipMemcpyHostToDevice,
                                mc->stream));

@@ -507,6 +507,25 @@ struct MultiSort {
 };
 hipError_t launch_multi_sort(hipStream_t st, uint32_t P, const MultiSort &a);
 
+// Device output (kernels_multi_export.hip, ABI 27): the resident result of a polishing call (pol: P results,
+// mask: n_total bytes over the packed rows) in the consumer's layout, one launch, one workgroup per problem.
+// src: the column of every packed row, nullptr: the identity (a context created from the host).  Every output is
+// nullable: models / pixel_models P x 9, inliers / status P, mask_out P x n_max bytes, cols P x k_max.  k: the
+// problems' intrinsics, P x 9 of view 1 then P x 9 of view 2, needed with pixel_models.  The caller has checked
+// that every column is below n_max (src by construction; the identity by n_max >= max n_p).
+struct MultiExport {
+    const usac_multi_polish_output *pol;
+    const uint8_t *mask;
+    const uint32_t *src, *offsets;
+    const float *k;
+    uint32_t P, n_max, k_max;
+    float *models, *pixel_models;
+    int32_t *inliers, *status;
+    uint8_t *mask_out;
+    int32_t *cols;
+};
+hipError_t launch_multi_export(hipStream_t st, const MultiExport &a);
+
 // k nearest neighbours of every point (kernels_knn.hip, nearest_neighbors.cpp:69-128):
 // idx / d2 (nullable) n x k, self excluded, ascending distance, ties by index; 1 <= k <= 32
 constexpr uint32_t kKnnMax = 32;

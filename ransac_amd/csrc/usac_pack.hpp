@@ -19,6 +19,12 @@ inline bool pack_extent_ok(uint32_t P, uint32_t n_max) {
     return P != 0 && n_max != 0 && (uint64_t)P * n_max < (1ull << 32);
 }
 
+// the outputs of usac_multi_export_device (ABI 27) under the same rule: P x n_max mask bytes and, where a list is
+// asked for (k_max != 0), P x k_max entries
+inline bool export_extent_ok(uint32_t P, uint32_t n_max, uint32_t k_max) {
+    return pack_extent_ok(P, n_max) && (k_max == 0 || pack_extent_ok(P, k_max));
+}
+
 // sizes[P], flags[P] -> offsets[P + 1] (offsets[0] = 0, the exclusive sum).  Returns kPackOk, or what the first
 // offending problem *bad is refused for (offsets is then unspecified): a flag the kernel raised, a size above
 // n_max (no count of n_max columns is), fewer kept rows than the sample size m, or a total of 2^32 rows or more.

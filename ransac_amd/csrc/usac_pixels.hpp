@@ -1,7 +1,9 @@
-// Pixel coordinates of an essential multi context (ABI 24), the host-only part: the validation of an
-// intrinsic matrix, the threshold of a pixel tolerance and the pixel-space model of an essential matrix
-// (DESIGN.md §8b "Pixel coordinates").  No HIP call and no other header of the library, so a stand-alone
-// program can include it (tests/cpp_multi_pixels/pixels_check.cpp).
+// Pixel coordinates of an essential multi context (ABI 24): the validation of an intrinsic matrix, the
+// threshold of a pixel tolerance and the pixel-space model of an essential matrix (DESIGN.md §8b "Pixel
+// coordinates").  Host and device (ABI 27: k_multi_export writes the pixel-space models; the library is built
+// with -ffp-contract=off, so the one text gives one result on both).  No HIP call and no other header of the
+// library, so a stand-alone program built with g++ can include it (tests/cpp_multi_pixels/pixels_check.cpp,
+// tests/cpp_multi_export/export_check.cpp).
 //
 // K is row-major k[0..8] = fx, s, cx, 0, fy, cy, 0, 0, 1.  The calibrated point of a pixel (u, v) is, in fp32
 // in this order (k_multi_calibrate, kernels_multi_calib.hip):
@@ -10,20 +12,29 @@
 #include <cmath>
 #include <cstdint>
 
+#ifndef USAC_HD  // as usac_prosac.hpp
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define USAC_HD __host__ __device__ __forceinline__
+#else
+#define USAC_HD inline
+#endif
+#endif
+
 namespace usac {
 
 // what the kernel reads per problem: fx, s, cx, fy, cy of view 1, then of view 2, padded to three float4
 constexpr uint32_t kCalibFloats = 12;
 
 // an upper-triangular K with positive focal lengths, finite entries and a last row of 0 0 1
-inline bool pixel_k_ok(const float *k) {
+USAC_HD bool pixel_k_ok(const float *k) {
     for (int i = 0; i < 9; i++)
         if (!std::isfinite(k[i])) return false;
     return k[0] > 0.f && k[4] > 0.f && k[3] == 0.f && k[6] == 0.f && k[7] == 0.f && k[8] == 1.f;
 }
 
 // k1, k2 (3 x 3 each) -> the kernel's kCalibFloats values of one problem
-inline void pixel_pack(const float *k1, const float *k2, float *out) {
+USAC_HD void pixel_pack(const float *k1, const float *k2, float *out) {
     const float *ks[2] = {k1, k2};
     for (int v = 0; v < 2; v++) {
         const float *k = ks[v];
@@ -38,14 +49,14 @@ inline void pixel_pack(const float *k1, const float *k2, float *out) {
 }
 
 // (t / f)^2 with f the mean of the four focal lengths, in fp32 in this order
-inline float pixel_threshold(const float *k1, const float *k2, float t) {
+USAC_HD float pixel_threshold(const float *k1, const float *k2, float t) {
     const float f = ((k1[0] + k1[4]) + (k2[0] + k2[4])) * 0.25f;
     const float r = t / f;
     return r * r;
 }
 
 // the closed-form inverse of an upper-triangular K, from its fp32 entries widened to fp64
-inline void pixel_k_inverse(const float *k, double *inv) {
+USAC_HD void pixel_k_inverse(const float *k, double *inv) {
     const double fx = k[0], s = k[1], cx = k[2], fy = k[4], cy = k[5];
     inv[0] = 1.0 / fx;
     inv[1] = -s / (fx * fy);
@@ -60,7 +71,7 @@ inline void pixel_k_inverse(const float *k, double *inv) {
 
 // F = K2^-T E K1^-1 in fp64: G = E K1^-1, then F = K2^-T G, every entry a three-term sum taken left to
 // right, no normalisation, one cast to fp32 at the end
-inline void pixel_model(const float *k1, const float *k2, const float *e, float *f) {
+USAC_HD void pixel_model(const float *k1, const float *k2, const float *e, float *f) {
     double a[9], b[9], g[9];
     pixel_k_inverse(k1, a);
     pixel_k_inverse(k2, b);

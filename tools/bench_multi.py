@@ -77,6 +77,12 @@ column that falls with the original rank.  Three pipelines are alternated: from_
 padded_mask; from_padded + run + padded_mask; and torch.sort(stable=True) + gather + from_padded + run_prosac +
 padded_mask + the inverse permutation of the mask.  The first and the third must return equal masks and models
 (exit status 1 otherwise); the creation with and without scores is also timed alone.
+
+--device-output (with --device-input, with or without --scores) times the way out instead: creation, the polished
+run (run, or run_prosac with --scores), padded_mask() and an upload of the polished models as a (pairs, 3, 3) tensor
+against creation, keep_on_device = True, the same run and export_device(inlier_cols=n_max), alternated; then
+export_device alone against padded_mask() alone on one context.  The two masks and the two model tensors must be
+equal (exit status 1 otherwise).
 """
 import argparse
 import ctypes
@@ -668,6 +674,89 @@ def main_pixels(a, model):
     return 0 if equal and rows_equal and thr_equal else 1
 
 
+def device_output(a, n_max, create, run, scores):
+    """--device-output (inside --device-input, with or without --scores): the results of a polished run as device
+    tensors, two ways, alternated, host-timed, each ending synchronised.  A, before ABI 27: run(polish=True),
+    padded_mask() and an upload of the polished models as a (P, 3, 3) tensor.  B: keep_on_device = True, the same
+    run, export_device(inlier_cols=n_max) -- nothing N_total-sized crosses in either direction, and the inliers'
+    columns come with it.  Both create and close their context.  Then export_device alone against padded_mask()
+    alone on one context.  create() -> a context from the padded device tensors, run(mc) -> its polished run."""
+    import torch
+
+    dev = torch.device("cuda:0")
+
+    def pipe_a():
+        mc = create()
+        res = run(mc)
+        mask = mc.padded_mask()
+        models = torch.from_numpy(np.stack([r["polished"]["model"] for r in res]).reshape(-1, 3, 3)).to(dev)
+        torch.cuda.synchronize()
+        mc.close()
+        return mask, models, res
+
+    def pipe_b():
+        mc = create()
+        mc.keep_on_device = True
+        res = run(mc)
+        out = mc.export_device(inlier_cols=n_max)  # waits for its stream
+        mc.close()
+        return out, res
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        r = fn()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    for _ in range(a.warmup):
+        pipe_a()
+        pipe_b()
+    ta, tb, tmask, texp, texp_mask = [], [], [], [], []
+    for _ in range(a.reps):
+        (mask_a, models_a, res_a), ms = timed(pipe_a)
+        ta.append(ms)
+        (out_b, res_b), ms = timed(pipe_b)
+        tb.append(ms)
+        mc = create()
+        run(mc)
+        _, ms = timed(lambda: mc.export_device(inlier_cols=n_max))
+        texp.append(ms)
+        _, ms = timed(mc.export_device)  # the mask, the models, counts and statuses: what A delivers
+        texp_mask.append(ms)
+        _, ms = timed(mc.padded_mask)    # last: its upload ends the resident result
+        tmask.append(ms)
+        mc.close()
+    masks_equal = bool(torch.equal(mask_a, out_b["mask"]))
+    models_equal = bool(torch.equal(models_a.view(torch.int32), out_b["models"].view(torch.int32)))
+    counts = out_b["inliers"].cpu().numpy()
+    cols = out_b["inlier_cols"].cpu().numpy()
+    lists_fit = bool((counts == [r["polished"]["inliers"] for r in res_a]).all() and
+                     ((cols >= 0).sum(1) == np.minimum(counts, n_max)).all())
+    dicts_equal = same_bits([r["polished"] for r in res_a], [r["polished"] for r in res_b])
+
+    def summary(ms):
+        return {"min_ms": round(min(ms), 3), "median_ms": round(statistics.median(ms), 3), "max_ms": round(max(ms), 3)}
+
+    ma, mb = statistics.median(ta), statistics.median(tb)
+    line = {"bench": "multi_export", "estimator": a.estimator, "scores": bool(scores), "pairs": a.pairs,
+            "points": a.points, "n_max": n_max, "round": a.R, "max_iterations": a.max_iterations,
+            "inlier_ratio": a.inlier_ratio, "dlt": a.dlt, "reps": a.reps,
+            "pipeline_a_padded_mask_and_model_upload": summary(ta), "pipeline_b_resident_export": summary(tb),
+            "b_median_minus_a_median_ms": round(mb - ma, 3), "b_median_not_above_a_max": bool(mb <= max(ta)),
+            "b_median_below_a_median": bool(mb < ma),
+            "export_device_with_columns_alone": summary(texp), "export_device_mask_and_models_alone": summary(texp_mask),
+            "padded_mask_alone": summary(tmask),
+            "masks_equal": masks_equal, "model_tensors_bit_equal": models_equal, "polished_dicts_bit_equal": bool(dicts_equal),
+            "counts_and_columns_fit": lists_fit,
+            "mean_polished_inliers": round(float(np.mean([r["polished"]["inliers"] for r in res_b])), 2)}
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    return 0 if masks_equal and models_equal and dicts_equal and lists_fit else 1
+
+
 def main_device(a, model, est, sets):
     """--device-input: from padded device tensors to the polished inliers as a (P, n_max) bool tensor on the device,
     what a caller does today (pipeline A: down to numpy, ragged sets, MultiContext, run, mask built in numpy, up
@@ -695,6 +784,9 @@ def main_device(a, model, est, sets):
 
     def create_b():
         return usac.MultiContext.from_padded(est, rows_t, valid=valid_t)
+
+    if a.device_output:
+        return device_output(a, n_max, create_b, lambda mc: mc.run(model, polish=True), False)
 
     def pipe_a():
         mc, v = create_a()
@@ -789,6 +881,10 @@ def main_device_sorted(a, model, est, sets):
     pmodel = usac.Model(model.threshold, model.sample_size, model.desired_prob, 5, est, usac.SAMPLER.Prosac)
     pmodel.max_iterations, pmodel.batch, pmodel.seed = model.max_iterations, model.batch, model.seed
     pmodel.setDLTMode(model.dlt_mode)
+
+    if a.device_output:
+        return device_output(a, n_max, lambda: usac.MultiContext.from_padded(est, rows_t, valid=valid_t, scores=scores_t),
+                             lambda mc: mc.run_prosac(pmodel, polish=True), True)
 
     def pipe_s():
         mc = usac.MultiContext.from_padded(est, rows_t, valid=valid_t, scores=scores_t)
@@ -913,9 +1009,15 @@ def main():
                     help="--device-input: unsorted columns with a score each (a matcher's output); from_padded(scores=) + "
                          "run_prosac against from_padded + run and against torch.sort + gather + from_padded + run_prosac "
                          "+ the inverse permutation; the first and the last must return equal masks and models")
+    ap.add_argument("--device-output", action="store_true",
+                    help="--device-input, with or without --scores: the polished run's results as device tensors; run + "
+                         "padded_mask + an upload of the polished models against keep_on_device + the same run + "
+                         "export_device(inlier_cols=n_max); masks and model tensors must be equal")
     a = ap.parse_args()
     if a.scores and not a.device_input:
         ap.error("--scores goes with --device-input")
+    if a.device_output and not a.device_input:
+        ap.error("--device-output goes with --device-input")
     if a.device_input and (a.pixels or a.sprt or a.lo or a.per_problem_thr or a.sampler != "uniform" or a.polish):
         ap.error("--device-input goes with --estimator alone")
     if a.pixels and (a.estimator != "essential" or a.sprt or a.lo or a.per_problem_thr or a.sampler != "uniform"):
