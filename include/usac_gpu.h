@@ -87,7 +87,10 @@
  *                                  ABI 27: usac_multi_export_device, the result of the last polishing call --
  *                                  models, counts, the padded mask, the inliers' columns, pixel-space models --
  *                                  written into device memory on the caller's stream, and usac_multi_set_resident,
- *                                  polishing calls that bring no mask to the host
+ *                                  polishing calls that bring no mask to the host;
+ *                                  ABI 28: usac_multi_pose_device and usac_multi_pose, the rotation and translation
+ *                                  direction of an essential context's models, chosen on the device by a vote of
+ *                                  the inliers over the four decompositions
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -102,7 +105,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 27
+#define USAC_ABI_VERSION 28
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -718,6 +721,58 @@ typedef struct usac_multi_device_output {
  * bytes for the float and int arrays), or whose allocation is too short.  The reason is what
  * usac_multi_last_error returns. */
 int usac_multi_export_device(usac_multi *mc, const usac_multi_device_output *o);
+/* Pose (ABI 28): the rotation and translation direction of an essential context's models, chosen on the device.
+ * The rule, for problem p with its model E (9 fp32 values, widened to fp64), its calibrated rows (x1 y1 x2 y2,
+ * widened likewise) and a 0 / 1 mask over them:
+ *   1. U, V = the 3x3 SVD of E by row Jacobi with accumulated rotations, singular values descending, v3 = v1 x v2;
+ *      P_j = [R | t] for j = 0..3 are the four projections of ProjectionsFromEssential (five_points.cpp:336-371):
+ *      R = U W V^T for j = 0, 1 and U W^T V^T for j = 2, 3, W = [0 -1 0; 1 0 0; 0 0 1]; t = +u3 for even j, -u3
+ *      for odd j.  The convention is the reference's: P_ref = [I | 0], so x2 ~ R x1 + t.  All fp64, no
+ *      contraction, correctly rounded division and square root, in the operation order of the 5-point solver's
+ *      cheirality test: the very text that test runs.
+ *   2. count_j = the number of rows with a set mask byte that are in front of both cameras under P_j: the point
+ *      triangulated as the null vector on the first ray (TriangulatePoint) has CalcDepth > 0 for P_ref and for
+ *      P_j.  A row with a non-finite value is in front of nothing: it is skipped before the test.  (The
+ *      comparisons alone would not say so: the triangulation takes the row of x2 or the row of y2, whichever has
+ *      the larger norm, and a non-finite x2 beside a finite y2 loses that comparison and leaves a finite point.)
+ *   3. choice = the j with the largest count_j, the lowest j on ties; -1 when the largest count is 0 or the
+ *      problem's status is not USAC_OK (USAC_ERR_NO_MODEL in the resident result).
+ *   4. s = +1 if the determinant of P_choice's 3x3 block (CalcDepth's cofactor expansion along the first row) is
+ *      > 0, else -1.  R = s times that block (row-major) and t = s times the fourth column, each cast once to
+ *      fp32; front = count_choice; front_mask = 1 exactly on the rows counted in count_choice.  With choice =
+ *      -1: R the identity, t zero, front 0, the mask row zero.
+ * det R = +1: U's columns are the rows of a product of plane rotations taken in the order of the sorted singular
+ * values, so det U is the sign of that permutation -- +1 or -1 --, V's third column is the cross product of its
+ * first two (det V = +1) and det W = 1.  P and -P are one camera, CalcDepth already multiplies by the sign of the
+ * determinant so that the counts do not depend on it, and s picks the one of the two whose block is a rotation.
+ * |t| = 1; the scale of the translation is not observable.
+ * One launch, one workgroup per problem, any n_p: nothing is deferred to the host, the counts are integers and
+ * the result does not depend on the order of anything. */
+typedef struct usac_multi_pose_output {
+    uint32_t n_max;      /* columns per problem of front_mask, as usac_multi_device_output.n_max */
+    float   *R;          /* DEVICE, P x 9, row-major */
+    float   *t;          /* DEVICE, P x 3 */
+    int32_t *front;      /* DEVICE, P: count_choice */
+    int32_t *choice;     /* DEVICE, P: 0..3, or -1 */
+    uint8_t *front_mask; /* DEVICE, P x n_max bytes of 0 / 1, a row's byte at its source column */
+    void    *stream;     /* hipStream_t the launch is enqueued on; NULL: the null stream */
+} usac_multi_pose_output;
+/* The rule above over the resident result of the last polishing call (usac_multi_export_device says what is
+ * resident and what ends it): E and the status of problem p are its polished result's, the mask is the resident
+ * inlier mask.  One launch on o->stream, which the call waits for; the workgroup clears its own front_mask row,
+ * no memset comes first.  Every pointer is nullable, not all of them.  The call reads the resident result and
+ * leaves it as it is.  USAC_ERR_UNSUPPORTED before any device call on a homography or fundamental context, and
+ * when no result is resident (usac_multi_export_device's message); USAC_ERR_ARG before any device call for a NULL
+ * mc or o, every pointer NULL, or an n_max usac_multi_export_device would refuse; USAC_ERR_ARG before any launch,
+ * nothing written, for a pointer that is not device memory of the context's device, is misaligned or too short. */
+int usac_multi_pose_device(usac_multi *mc, const usac_multi_pose_output *o);
+/* The same kernel from host arrays, for models of the caller's own: E P x 9; mask N_total bytes over the packed
+ * rows, NULL: every row; every status counts as USAC_OK.  R P x 9, t P x 3, front P, choice P and front_mask
+ * (N_total bytes in packed-row order, like every host mask) are host arrays, each nullable, not all of them.
+ * The call uses buffers of its own: the resident result stays as it is.  USAC_ERR_UNSUPPORTED before any device
+ * call on a homography or fundamental context, USAC_ERR_ARG for a NULL mc or E or when every output is NULL. */
+int usac_multi_pose(usac_multi *mc, const float *E, const uint8_t *mask, float *R, float *t, int32_t *front,
+                    int32_t *choice, uint8_t *front_mask);
 void usac_multi_destroy(usac_multi *mc);
 /* The message of the context's last failed call; mc == NULL: "null context", or see usac_multi_create_device. */
 const char *usac_multi_last_error(const usac_multi *mc);

@@ -695,6 +695,37 @@ public:
     void exportDevice(const usac_multi_device_output &o) const {
         check(usac_multi_export_device(mc_, &o), "MultiContext::exportDevice");
     }
+    // usac_multi_pose_device (ABI 28, an essential context): the relative pose of every problem's polished model
+    // -- of the four [R | t] of E the one with the most inliers in front of both cameras -- written into the
+    // device memory o names by one launch on o.stream, which the call waits for: R (P x 9, row-major), t (P x 3,
+    // |t| = 1), the count in front, the choice (0..3, -1: none) and the P x n_max mask of the rows counted.
+    // Every pointer of o is nullable; o.n_max as exportDevice's.  It reads the resident result of the last
+    // polishing call and leaves it as it is; it throws what exportDevice throws, and USAC_ERR_UNSUPPORTED on a
+    // homography or fundamental context.
+    void poseDevice(const usac_multi_pose_output &o) const {
+        check(usac_multi_pose_device(mc_, &o), "MultiContext::poseDevice");
+    }
+    // usac_multi_pose (ABI 28): the same choice for the caller's own models (P x 9) and mask (N_total bytes over
+    // the packed rows; empty: every row), into host vectors; front_mask is N_total bytes in packed-row order
+    struct Pose {
+        std::vector<float> R, t;
+        std::vector<int32_t> front, choice;
+        std::vector<uint8_t> front_mask;
+    };
+    Pose pose(const std::vector<float> &E, const std::vector<uint8_t> &mask = std::vector<uint8_t>()) const {
+        const size_t P = offsets_.empty() ? 0u : offsets_.size() - 1, n = offsets_.empty() ? 0u : offsets_.back();
+        if (E.size() != 9 * P) throw Error(USAC_ERR_ARG, "pose: P x 9 model values");
+        if (!mask.empty() && mask.size() != n) throw Error(USAC_ERR_ARG, "pose: N_total mask bytes, or none");
+        Pose r;
+        r.R.resize(9 * P);
+        r.t.resize(3 * P);
+        r.front.resize(P);
+        r.choice.resize(P);
+        r.front_mask.resize(n);
+        check(usac_multi_pose(mc_, E.data(), mask.empty() ? nullptr : mask.data(), r.R.data(), r.t.data(), r.front.data(),
+                              r.choice.data(), r.front_mask.data()), "MultiContext::pose");
+        return r;
+    }
 
     // one round of R hypotheses (a multiple of 64 in 64..8192) for the listed problems (empty: all,
     // in order), device sampler keyed by seeds[i] for problems[i]; with per_hypothesis the counts

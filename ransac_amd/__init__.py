@@ -198,6 +198,13 @@ class _MultiDeviceOutput(ctypes.Structure):
                 ("mask", ctypes.c_void_p), ("inlier_cols", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
 
 
+class _MultiPoseOutput(ctypes.Structure):
+    """usac_multi_pose_output (ABI 28): the mask's width, the output device pointers as integers, the stream"""
+    _fields_ = [("n_max", ctypes.c_uint32), ("R", ctypes.c_void_p), ("t", ctypes.c_void_p),
+                ("front", ctypes.c_void_p), ("choice", ctypes.c_void_p), ("front_mask", ctypes.c_void_p),
+                ("stream", ctypes.c_void_p)]
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -230,6 +237,7 @@ ABI_SYMBOLS = [
     "usac_multi_create_device", "usac_multi_get_offsets", "usac_multi_get_source", "usac_multi_padded_mask",
     "usac_multi_create_device_sorted",
     "usac_multi_set_resident", "usac_multi_export_device",
+    "usac_multi_pose_device", "usac_multi_pose",
 ]
 
 
@@ -341,6 +349,8 @@ def lib():
         "usac_multi_padded_mask": (ctypes.c_int, [_vp, u8p, _vp, _vp]),
         "usac_multi_set_resident": (ctypes.c_int, [_vp, ctypes.c_int]),
         "usac_multi_export_device": (ctypes.c_int, [_vp, _P(_MultiDeviceOutput)]),
+        "usac_multi_pose_device": (ctypes.c_int, [_vp, _P(_MultiPoseOutput)]),
+        "usac_multi_pose": (ctypes.c_int, [_vp, f32p, u8p, f32p, f32p, i32p, i32p, u8p]),
         "usac_multi_destroy": (None, [_vp]),
         "usac_multi_last_error": (ctypes.c_char_p, [_vp]),
         "usac_multi_num_problems": (ctypes.c_uint32, [_vp]),
@@ -1176,6 +1186,66 @@ class MultiContext:
                                **{key: a.ptr for key, a in arrays.items()})
         self._check(lib().usac_multi_export_device(self._h, ctypes.byref(o)), "multi_export_device")
         return res
+
+    def export_pose(self, front_mask=False, n_max=None, out=None, stream=None):
+        """usac_multi_pose_device (an essential context): the relative pose of every problem's polished model,
+        chosen on the device from the result of the last polishing call -- of the four [R | t] of E the one that
+        puts the most inliers in front of both cameras (x2 ~ R x1 + t, |t| = 1, det R = +1).  Tensors on the
+        context's device, written by one launch: "R" (P, 3, 3) float32, "t" (P, 3) float32, "front" (P,) int32
+        (the inliers in front), "choice" (P,) int32 (0..3; -1: no inlier in front of any candidate, or a problem
+        without a model -- R is then the identity and t zero) and, with front_mask=True, "front_mask" (P, n_max)
+        bool.  n_max, out and stream: as export_device's.  The resident result stays as it is."""
+        P = self.P
+        out = dict(out or {})
+        unknown = set(out) - {"R", "t", "front", "choice", "front_mask"}
+        if unknown:
+            raise ValueError("export_pose: unknown outputs %s" % sorted(unknown))
+        if n_max is None:
+            n_max = self.n_max if self.n_max is not None else int(self.sizes.max())
+        n_max = int(n_max)
+        want = {"R": ((P, 3, 3), ("f4",)), "t": ((P, 3), ("f4",)), "front": ((P,), ("i4",)), "choice": ((P,), ("i4",))}
+        if front_mask or "front_mask" in out:
+            want["front_mask"] = ((P, n_max), ("u1", "b1"))
+        res, arrays = {}, {}
+        for key, (shape, kinds) in want.items():
+            fresh = key not in out
+            if fresh:
+                import torch
+
+                dt = {"f4": torch.float32, "i4": torch.int32, "u1": torch.uint8}[kinds[0]]
+                out[key] = torch.empty(shape, dtype=dt, device="cuda:%d" % self.device)
+            arrays[key] = _DevArray(out[key], key).need(shape, kinds)
+            res[key] = out[key].view(torch.bool) if fresh and key == "front_mask" else out[key]
+        if stream is None:
+            stream = 0
+            first = next(iter(arrays.values()))
+            if first.torch:
+                import torch
+
+                stream = torch.cuda.current_stream(first.obj.device).cuda_stream
+        o = _MultiPoseOutput(n_max=n_max, stream=int(stream) or None, **{key: a.ptr for key, a in arrays.items()})
+        self._check(lib().usac_multi_pose_device(self._h, ctypes.byref(o)), "multi_pose_device")
+        return res
+
+    def pose(self, E, mask=None):
+        """usac_multi_pose: the same choice for models of the caller's own.  E: (P, 3, 3) or (P, 9) float32; mask:
+        N_total bytes over the packed rows (None: every row).  Returns a dict of numpy arrays: "R" (P, 3, 3), "t"
+        (P, 3), "front" (P,), "choice" (P,) and "front_mask" (N_total,) uint8 in packed-row order."""
+        P, n = self.P, int(self.offsets[-1])
+        m = np.ascontiguousarray(E, dtype=np.float32).reshape(P, 9)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+            if mask.size != n:
+                raise ValueError("pose: mask must have N_total = %d bytes" % n)
+        R = np.zeros((P, 3, 3), dtype=np.float32)
+        t = np.zeros((P, 3), dtype=np.float32)
+        front = np.zeros(P, dtype=np.int32)
+        choice = np.zeros(P, dtype=np.int32)
+        fm = np.zeros(n, dtype=np.uint8)
+        self._check(lib().usac_multi_pose(self._h, _ptr(m, ctypes.c_float), _ptr(mask, ctypes.c_uint8),
+                                          _ptr(R, ctypes.c_float), _ptr(t, ctypes.c_float), _ptr(front, ctypes.c_int32),
+                                          _ptr(choice, ctypes.c_int32), _ptr(fm, ctypes.c_uint8)), "multi_pose")
+        return {"R": R, "t": t, "front": front, "choice": choice, "front_mask": fm}
 
     def resident_points(self):
         """usac_multi_get_points: the N_total x 4 rows resident on the device (a copy)."""

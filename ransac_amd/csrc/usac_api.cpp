@@ -4138,6 +4138,8 @@ struct usac_multi {
     bool resident_on = false, resident_valid = false;
     const char *resident_end = nullptr;
     DevBuf kdev;
+    // Pose (ABI 28): usac_multi_pose's own block -- the caller's models and mask up, the outputs down
+    DevBuf pose_buf;
     std::string err;
 };
 
@@ -4973,6 +4975,30 @@ std::string device_pointer_problem(const void *ptr, const char *name, int device
     return "";
 }
 
+// the width of P x n_max output bytes (usac_multi_export_device, usac_multi_pose_device): usac_pack.hpp's rule
+int multi_width_check(usac_multi *mc, const char *who, uint32_t n_max) {
+    const uint32_t widest = mc->n_max ? 0u : usac::widest_problem(mc->offsets.data(), mc->P);
+    const usac::WidthStatus st = usac::output_width(mc->n_max, widest, n_max);
+    if (st == usac::kWidthOk) return USAC_OK;
+    return fail(mc, USAC_ERR_ARG, std::string(who) + usac::width_message(st, mc->n_max, widest));
+}
+
+// the entries that read the resident result (ABI 27): refused, with what ended it, when there is none
+int multi_resident_check(usac_multi *mc, const char *who) {
+    if (mc->resident_valid) return USAC_OK;
+    return fail(mc, USAC_ERR_UNSUPPORTED,
+                std::string(who) + (mc->resident_end ? std::string("the result of the last polishing call is no longer "
+                                                                   "resident: ended by ") + mc->resident_end
+                                                     : std::string("no polishing call has run on this context")));
+}
+
+// the pose entries (ABI 28) decompose an essential matrix: refused on any other context before a device call
+int multi_pose_only_essential(usac_multi *mc, const char *who) {
+    if (multi_is_e(mc)) return USAC_OK;
+    return fail(mc, USAC_ERR_UNSUPPORTED, std::string(who) + "for the essential estimator only (a homography or a "
+                                                             "fundamental matrix has no four [R | t] to choose from)");
+}
+
 }  // namespace
 
 extern "C" {
@@ -5301,25 +5327,14 @@ int usac_multi_export_device(usac_multi *mc, const usac_multi_device_output *o) 
     if (!o->models && !o->pixel_models && !o->inliers && !o->status && !o->mask && !o->inlier_cols)
         return fail(mc, USAC_ERR_ARG, std::string(who) + "every output pointer is NULL");
     const uint32_t P = mc->P;
-    if (mc->n_max) {
-        if (o->n_max != mc->n_max)
-            return fail(mc, USAC_ERR_ARG, std::string(who) + "n_max must be the context's, " + std::to_string(mc->n_max));
-    } else {  // from the host: the identity is the source, and every local index must have its column
-        uint32_t widest = 0;
-        for (uint32_t p = 0; p < P; p++) widest = std::max(widest, mc->offsets[p + 1] - mc->offsets[p]);
-        if (o->n_max < widest)
-            return fail(mc, USAC_ERR_ARG, std::string(who) + "n_max must be at least the largest problem's size, " +
-                                              std::to_string(widest));
-    }
+    int rc = multi_width_check(mc, who, o->n_max);
+    if (rc) return rc;
     if ((o->inlier_cols != nullptr) != (o->k_max != 0))
         return fail(mc, USAC_ERR_ARG, std::string(who) + "k_max > 0 goes with inlier_cols, and 0 with a NULL inlier_cols");
     if (!usac::export_extent_ok(P, o->n_max, o->k_max))
         return fail(mc, USAC_ERR_ARG, std::string(who) + "n_max must be > 0, P * n_max and P * k_max < 2^32");
-    if (!mc->resident_valid)
-        return fail(mc, USAC_ERR_UNSUPPORTED,
-                    std::string(who) + (mc->resident_end ? std::string("the result of the last polishing call is no longer "
-                                                                       "resident: ended by ") + mc->resident_end
-                                                         : std::string("no polishing call has run on this context")));
+    rc = multi_resident_check(mc, who);
+    if (rc) return rc;
     if (o->pixel_models && mc->k1.empty())
         return fail(mc, USAC_ERR_UNSUPPORTED, std::string(who) + "pixel_models: the context was not created with intrinsics "
                                                   "(usac_multi_create_essential_pixels, usac_multi_create_device with K1)");
@@ -5367,6 +5382,94 @@ int usac_multi_export_device(usac_multi *mc, const usac_multi_device_output *o) 
     return USAC_OK;
 }
 
+// ---- pose (ABI 28)
+int usac_multi_pose_device(usac_multi *mc, const usac_multi_pose_output *o) {
+    const char *who = "usac_multi_pose_device: ";
+    if (!mc) return USAC_ERR_ARG;
+    int rc = multi_pose_only_essential(mc, who);
+    if (rc) return rc;
+    if (!o) return fail(mc, USAC_ERR_ARG, std::string(who) + "NULL output");
+    if (!o->R && !o->t && !o->front && !o->choice && !o->front_mask)
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "every output pointer is NULL");
+    const uint32_t P = mc->P;
+    rc = multi_width_check(mc, who, o->n_max);
+    if (rc) return rc;
+    if (!usac::pack_extent_ok(P, o->n_max))
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "n_max must be > 0, P * n_max < 2^32");
+    rc = multi_resident_check(mc, who);
+    if (rc) return rc;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    // a host pointer must never reach the kernel: every pointer it will write, before the launch
+    struct { const void *p; const char *name; size_t bytes, align; } ptrs[] = {
+        {o->R, "R", (size_t)P * 36, 4},         {o->t, "t", (size_t)P * 12, 4},
+        {o->front, "front", (size_t)P * 4, 4},  {o->choice, "choice", (size_t)P * 4, 4},
+        {o->front_mask, "front_mask", (size_t)P * o->n_max, 1}};
+    for (const auto &q : ptrs) {
+        if (!q.p) continue;
+        const std::string why = device_pointer_problem(q.p, q.name, mc->device, q.bytes, q.align);
+        if (!why.empty()) return fail(mc, USAC_ERR_ARG, std::string(who) + why);
+    }
+    usac::MultiPose a{};
+    a.pts = mc->pts.as<float4>();
+    a.offsets = mc->offs.as<uint32_t>();
+    a.pol = mc->pol_out.as<usac_multi_polish_output>();
+    a.mask = mc->mask.as<uint8_t>();
+    a.src = mc->n_max ? mc->src.as<uint32_t>() : nullptr;
+    a.P = P;
+    a.n_max = o->n_max;
+    a.R = o->R;
+    a.t = o->t;
+    a.front = o->front;
+    a.choice = o->choice;
+    a.front_mask = o->front_mask;
+    // every call of this context has waited for its streams: the resident buffers are at rest, and are only read
+    hipStream_t cs = static_cast<hipStream_t>(o->stream);
+    HIP_TRY(mc, usac::launch_multi_pose(cs, a));
+    HIP_TRY(mc, stream_wait(cs));
+    return USAC_OK;
+}
+
+int usac_multi_pose(usac_multi *mc, const float *E, const uint8_t *mask, float *R, float *t, int32_t *front,
+                    int32_t *choice, uint8_t *front_mask) {
+    const char *who = "usac_multi_pose: ";
+    if (!mc) return USAC_ERR_ARG;
+    const int rc = multi_pose_only_essential(mc, who);
+    if (rc) return rc;
+    if (!E) return fail(mc, USAC_ERR_ARG, std::string(who) + "NULL models");
+    if (!R && !t && !front && !choice && !front_mask)
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "every output pointer is NULL");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    // one block of the call's own: [E | R | t | front | choice] of P problems, then the mask and the front mask
+    // over the packed rows; the resident buffers (pol_out, mask) are not touched
+    const size_t P = mc->P, n = mc->n_total;
+    const size_t at_R = 36 * P, at_t = at_R + 36 * P, at_front = at_t + 12 * P, at_choice = at_front + 4 * P,
+                 at_mask = at_choice + 4 * P, at_fm = at_mask + n;
+    HIP_TRY(mc, mc->pose_buf.reserve(at_fm + n));
+    char *d = mc->pose_buf.as<char>();
+    HIP_TRY(mc, hipMemcpyAsync(d, E, 36 * P, hipMemcpyHostToDevice, mc->stream));
+    if (mask) HIP_TRY(mc, hipMemcpyAsync(d + at_mask, mask, n, hipMemcpyHostToDevice, mc->stream));
+    usac::MultiPose a{};
+    a.pts = mc->pts.as<float4>();
+    a.offsets = mc->offs.as<uint32_t>();
+    a.models = reinterpret_cast<const float *>(d);
+    a.mask = mask ? reinterpret_cast<const uint8_t *>(d + at_mask) : nullptr;
+    a.P = mc->P;
+    a.packed = true;
+    a.R = R ? reinterpret_cast<float *>(d + at_R) : nullptr;
+    a.t = t ? reinterpret_cast<float *>(d + at_t) : nullptr;
+    a.front = front ? reinterpret_cast<int32_t *>(d + at_front) : nullptr;
+    a.choice = choice ? reinterpret_cast<int32_t *>(d + at_choice) : nullptr;
+    a.front_mask = front_mask ? reinterpret_cast<uint8_t *>(d + at_fm) : nullptr;
+    HIP_TRY(mc, usac::launch_multi_pose(mc->stream, a));
+    if (R) HIP_TRY(mc, hipMemcpyAsync(R, d + at_R, 36 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (t) HIP_TRY(mc, hipMemcpyAsync(t, d + at_t, 12 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (front) HIP_TRY(mc, hipMemcpyAsync(front, d + at_front, 4 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (choice) HIP_TRY(mc, hipMemcpyAsync(choice, d + at_choice, 4 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (front_mask) HIP_TRY(mc, hipMemcpyAsync(front_mask, d + at_fm, n, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return USAC_OK;
+}
+
 void usac_multi_destroy(usac_multi *mc) {
     if (!mc) return;
     (void)hipSetDevice(mc->device);
@@ -5377,7 +5480,8 @@ void usac_multi_destroy(usac_multi *mc) {
         b->release();
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
                       &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
-                      &mc->pol_out, &mc->lo_state, &mc->e5_ws, &mc->thrs, &mc->lo_steps, &mc->src, &mc->kdev})
+                      &mc->pol_out, &mc->lo_state, &mc->e5_ws, &mc->thrs, &mc->lo_steps, &mc->src, &mc->kdev,
+                      &mc->pose_buf})
         b->release();
     if (mc->stream) StreamPool::get().give_back(mc->stream);
     delete mc;

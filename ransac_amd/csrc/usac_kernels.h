@@ -526,6 +526,28 @@ struct MultiExport {
 };
 hipError_t launch_multi_export(hipStream_t st, const MultiExport &a);
 
+// Pose (kernels_multi_pose.hip, ABI 28): per problem the [R | t] of its essential matrix that puts the most
+// masked rows in front of both cameras (include/usac_gpu.h "Pose"), one launch, one workgroup per problem.
+// The model and status of problem p come from pol[p] (the resident result) or, with pol == nullptr, from
+// models[9 p] with every status USAC_OK; exactly one of the two is given.  mask: n_total bytes over the packed
+// rows, nullptr: every row.  Every output is nullable: R P x 9, t P x 3, front / choice P.  front_mask is P x
+// n_max bytes with a set row's byte at its source column (src; nullptr: the identity, the caller has checked
+// n_max >= max n_p), or, with packed, n_total bytes in packed-row order (src must be nullptr).
+struct MultiPose {
+    const float4 *pts;
+    const uint32_t *offsets;
+    const usac_multi_polish_output *pol;
+    const float *models;
+    const uint8_t *mask;
+    const uint32_t *src;
+    uint32_t P, n_max;
+    bool packed;
+    float *R, *t;
+    int32_t *front, *choice;
+    uint8_t *front_mask;
+};
+hipError_t launch_multi_pose(hipStream_t st, const MultiPose &a);
+
 // k nearest neighbours of every point (kernels_knn.hip, nearest_neighbors.cpp:69-128):
 // idx / d2 (nullable) n x k, self excluded, ascending distance, ties by index; 1 <= k <= 32
 constexpr uint32_t kKnnMax = 32;

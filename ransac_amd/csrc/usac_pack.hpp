@@ -25,6 +25,28 @@ inline bool export_extent_ok(uint32_t P, uint32_t n_max, uint32_t k_max) {
     return pack_extent_ok(P, n_max) && (k_max == 0 || pack_extent_ok(P, k_max));
 }
 
+// The width a caller names for P x n_max output bytes (usac_multi_export_device, and usac_multi_pose_device of ABI
+// 28).  ctx_n_max: the padded width of a context from device input, 0 for a context created from the host, whose
+// source is the identity so that every local index below `widest` (the largest problem's size) needs a column.
+enum WidthStatus { kWidthOk = 0, kWidthNotTheContexts = 1, kWidthBelowWidest = 2 };
+inline uint32_t widest_problem(const uint32_t *offsets, uint32_t P) {
+    uint32_t widest = 0;
+    for (uint32_t p = 0; p < P; p++)
+        if (offsets[p + 1] - offsets[p] > widest) widest = offsets[p + 1] - offsets[p];
+    return widest;
+}
+inline WidthStatus output_width(uint32_t ctx_n_max, uint32_t widest, uint32_t n_max) {
+    if (ctx_n_max) return n_max == ctx_n_max ? kWidthOk : kWidthNotTheContexts;
+    return n_max >= widest ? kWidthOk : kWidthBelowWidest;
+}
+inline std::string width_message(WidthStatus st, uint32_t ctx_n_max, uint32_t widest) {
+    switch (st) {
+    case kWidthNotTheContexts: return "n_max must be the context's, " + std::to_string(ctx_n_max);
+    case kWidthBelowWidest: return "n_max must be at least the largest problem's size, " + std::to_string(widest);
+    default: return "";
+    }
+}
+
 // sizes[P], flags[P] -> offsets[P + 1] (offsets[0] = 0, the exclusive sum).  Returns kPackOk, or what the first
 // offending problem *bad is refused for (offsets is then unspecified): a flag the kernel raised, a size above
 // n_max (no count of n_max columns is), fewer kept rows than the sample size m, or a total of 2^32 rows or more.

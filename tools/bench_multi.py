@@ -83,6 +83,13 @@ run (run, or run_prosac with --scores), padded_mask() and an upload of the polis
 against creation, keep_on_device = True, the same run and export_device(inlier_cols=n_max), alternated; then
 export_device alone against padded_mask() alone on one context.  The two masks and the two model tensors must be
 equal (exit status 1 otherwise).
+
+--pose (with --estimator essential --device-input --device-output) goes one step further, to a pose per pair: both
+pipelines create their context from padded pixel rows with from_padded(K1=K), set keep_on_device, run(polish=True) and
+export_device(); one adds export_pose(front_mask=True), the other brings models and mask to the host, decomposes and
+votes per pair in numpy and uploads R, t and the front mask.  Alternated; export_pose is also timed alone.  On every
+pair whose host vote has a unique winner the two rotations must agree (exit status 1 otherwise); the share of such
+pairs is reported.
 """
 import argparse
 import ctypes
@@ -757,6 +764,149 @@ def device_output(a, n_max, create, run, scores):
     return 0 if masks_equal and models_equal and dicts_equal and lists_fit else 1
 
 
+def numpy_pose(E, rows, mask):
+    """what a caller does today with one pair's E (3 x 3), calibrated rows (n x 4, float64) and inlier mask: numpy's
+    SVD, the four (R, t), a vote of the inliers by the depths of the midpoint-free linear triangulation.
+    Returns (R, t, the counts of the four candidates, the chosen candidate's front flags over the n rows)."""
+    U, _, Vt = np.linalg.svd(E)
+    if np.linalg.det(U) < 0:
+        U = -U
+    if np.linalg.det(Vt) < 0:
+        Vt = -Vt
+    W = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+    idx = np.flatnonzero(mask)
+    x1 = np.c_[rows[idx, :2], np.ones(len(idx))]
+    x2 = np.c_[rows[idx, 2:], np.ones(len(idx))]
+    cands, fronts = [], []
+    for R in (U @ W @ Vt, U @ W.T @ Vt):
+        for t in (U[:, 2], -U[:, 2]):
+            a = np.cross(x2, x1 @ R.T)       # z1 (x2 x R x1) = -(x2 x t)
+            b = np.cross(x2, np.broadcast_to(t, x2.shape))
+            with np.errstate(all="ignore"):
+                z1 = -(a * b).sum(1) / (a * a).sum(1)
+            z2 = z1 * (x1 @ R[2]) + t[2]
+            cands.append((R, t))
+            fronts.append((z1 > 0) & (z2 > 0))
+    counts = np.array([int(f.sum()) for f in fronts])
+    best = int(np.argmax(counts))
+    flags = np.zeros(len(rows), dtype=bool)
+    flags[idx] = fronts[best]
+    return cands[best][0], cands[best][1], counts, flags
+
+
+def main_pose(a, model):
+    """--pose (with --estimator essential --device-input --device-output): from a polished essential run to a pose
+    per pair on the device, two ways, alternated, host-timed, each ending synchronised.  Both create their context
+    with from_padded(K1=K) from padded pixel rows, set keep_on_device, run(polish=True) and export_device().  A adds
+    export_pose(front_mask=True).  B adds what a caller does without it: models and mask to the host, a numpy loop
+    over the pairs (numpy_pose), and an upload of R, t and the front mask; the calibrated rows it needs are on the
+    host already, converted outside the timing.  A's choice must give B's rotation on every pair whose vote in B
+    has a unique winner."""
+    import torch
+
+    t_px = np.float32(45.0)
+    sets, K = pixel_pairs(a.pairs, a.points, a.inlier_ratio)
+    P, n = len(sets), a.points
+    n_max = n + n // 4
+    rng = np.random.default_rng(17)
+    rows = np.zeros((P, n_max, 4), dtype=np.float32)
+    valid = np.zeros((P, n_max), dtype=bool)
+    for p, pts in enumerate(sets):
+        cols = np.sort(rng.permutation(n_max)[:len(pts)])
+        rows[p, cols] = pts
+        valid[p, cols] = True
+    dev = torch.device("cuda:0")
+    rows_t, valid_t = torch.from_numpy(rows).to(dev), torch.from_numpy(valid).to(dev)
+    torch.cuda.synchronize()
+    cal = np.stack(numpy_calibrate(list(rows), K)).astype(np.float64)  # B's host copy of the calibrated rows
+
+    def shared():
+        mc = usac.MultiContext.from_padded(usac.ESTIMATOR.Essential, rows_t, valid=valid_t, K1=K)
+        mc.set_pixel_thresholds(t_px)
+        mc.keep_on_device = True
+        mc.run(model, polish=True)
+        return mc, mc.export_device()
+
+    def pipe_a():
+        mc, exp = shared()
+        pose = mc.export_pose(front_mask=True)  # waits for its stream
+        mc.close()
+        return exp, pose
+
+    def pipe_b():
+        mc, exp = shared()
+        models = exp["models"].cpu().numpy().astype(np.float64)
+        mask = exp["mask"].cpu().numpy()
+        R = np.zeros((P, 3, 3), dtype=np.float32)
+        t = np.zeros((P, 3), dtype=np.float32)
+        front = np.zeros((P, n_max), dtype=bool)
+        counts = np.zeros((P, 4), dtype=np.int64)
+        for p in range(P):
+            R[p], t[p], counts[p], front[p] = numpy_pose(models[p], cal[p], mask[p])
+        up = {"R": torch.from_numpy(R).to(dev), "t": torch.from_numpy(t).to(dev), "front_mask": torch.from_numpy(front).to(dev)}
+        torch.cuda.synchronize()
+        mc.close()
+        return exp, up, counts
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        r = fn()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    for _ in range(a.warmup):
+        pipe_a()
+        pipe_b()
+    ta, tb, tpose, tpose_nomask = [], [], [], []
+    for _ in range(a.reps):
+        (exp_a, pose_a), ms = timed(pipe_a)
+        ta.append(ms)
+        (exp_b, up_b, counts_b), ms = timed(pipe_b)
+        tb.append(ms)
+        mc, _ = shared()
+        _, ms = timed(lambda: mc.export_pose(front_mask=True))
+        tpose.append(ms)
+        _, ms = timed(mc.export_pose)
+        tpose_nomask.append(ms)
+        mc.close()
+    models_equal = bool(torch.equal(exp_a["models"].view(torch.int32), exp_b["models"].view(torch.int32)))
+    top = np.sort(counts_b, axis=1)
+    unique = (top[:, -1] > top[:, -2]) & (top[:, -1] > 0)
+    Ra, Rb = pose_a["R"].cpu().numpy().astype(np.float64), up_b["R"].cpu().numpy().astype(np.float64)
+    ta_, tb_ = pose_a["t"].cpu().numpy().astype(np.float64), up_b["t"].cpu().numpy().astype(np.float64)
+    choice = pose_a["choice"].cpu().numpy()
+    r_err = np.abs(Ra - Rb).reshape(P, -1).max(1)
+    t_err = np.abs(ta_ - tb_).max(1)
+    # the rotation decides: the two triangulations differ (B's is not the rule's), and on a poor model whose
+    # inliers split almost evenly between +t and -t their votes may pick opposite signs of t for one R
+    agree = (choice >= 0) & (r_err < 1e-4)
+    rotations_agree = bool(agree[unique].all())
+    translations_agree = int((agree & (t_err < 1e-4))[unique].sum())
+    front_a = pose_a["front"].cpu().numpy()
+
+    def summary(ms):
+        return {"min_ms": round(min(ms), 3), "median_ms": round(statistics.median(ms), 3), "max_ms": round(max(ms), 3)}
+
+    ma, mb = statistics.median(ta), statistics.median(tb)
+    line = {"bench": "multi_pose", "estimator": a.estimator, "pairs": a.pairs, "points": a.points, "n_max": n_max,
+            "round": a.R, "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio, "reps": a.reps,
+            "pipeline_a_export_pose": summary(ta), "pipeline_b_host_decomposition": summary(tb),
+            "a_median_minus_b_median_ms": round(ma - mb, 3), "b_median_over_a_median": round(mb / ma, 3),
+            "export_pose_with_front_mask_alone": summary(tpose), "export_pose_without_front_mask_alone": summary(tpose_nomask),
+            "model_tensors_bit_equal": models_equal, "pairs_with_a_unique_vote": int(unique.sum()),
+            "share_of_pairs_checked": round(float(unique.mean()), 4), "rotations_agree_on_checked_pairs": rotations_agree,
+            "max_rotation_difference_on_checked_pairs": float(r_err[unique].max()) if unique.any() else None,
+            "checked_pairs_with_the_same_translation_too": translations_agree,
+            "pairs_with_a_choice": int((choice >= 0).sum()), "mean_front": round(float(front_a.mean()), 2),
+            "front_counts_equal_on_checked_pairs": bool((front_a[unique] == top[unique, -1]).all())}
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    return 0 if models_equal and rotations_agree and unique.any() else 1
+
+
 def main_device(a, model, est, sets):
     """--device-input: from padded device tensors to the polished inliers as a (P, n_max) bool tensor on the device,
     what a caller does today (pipeline A: down to numpy, ragged sets, MultiContext, run, mask built in numpy, up
@@ -1013,7 +1163,13 @@ def main():
                     help="--device-input, with or without --scores: the polished run's results as device tensors; run + "
                          "padded_mask + an upload of the polished models against keep_on_device + the same run + "
                          "export_device(inlier_cols=n_max); masks and model tensors must be equal")
+    ap.add_argument("--pose", action="store_true",
+                    help="--estimator essential --device-input --device-output: from_padded(K1=K) + keep_on_device + "
+                         "run(polish=True) + export_device, then export_pose(front_mask=True) against models and mask to "
+                         "the host, a numpy decomposition and vote per pair, and an upload of R, t and the front mask")
     a = ap.parse_args()
+    if a.pose and not (a.device_input and a.device_output and a.estimator == "essential" and not a.scores):
+        ap.error("--pose goes with --estimator essential --device-input --device-output")
     if a.scores and not a.device_input:
         ap.error("--scores goes with --device-input")
     if a.device_output and not a.device_input:
@@ -1046,6 +1202,8 @@ def main():
     seeds = [model.seed + p for p in range(a.pairs)]
     if a.pixels:
         return main_pixels(a, model)
+    if a.pose:
+        return main_pose(a, model)
     if a.device_input and a.scores:
         return main_device_sorted(a, model, est, sets)
     if a.device_input:
