@@ -90,7 +90,10 @@
  *                                  polishing calls that bring no mask to the host;
  *                                  ABI 28: usac_multi_pose_device and usac_multi_pose, the rotation and translation
  *                                  direction of an essential context's models, chosen on the device by a vote of
- *                                  the inliers over the four decompositions
+ *                                  the inliers over the four decompositions;
+ *                                  ABI 29: usac_multi_refine_pose_device and usac_multi_refine_pose, a pose (R, t)
+ *                                  refined on the device by Levenberg-Marquardt steps on its five parameters over
+ *                                  the inliers' Sampson distances
  *
  * Threading: a context is bound to one device and one HIP stream and is not
  * thread-safe (one host thread / process per GPU).  Calls are synchronous with respect
@@ -105,7 +108,7 @@
 extern "C" {
 #endif
 
-#define USAC_ABI_VERSION 28
+#define USAC_ABI_VERSION 29
 
 /* = enum ESTIMATOR (usac/model.hpp:10) */
 enum { USAC_LINE2D = 1, USAC_HOMOGRAPHY = 2, USAC_FUNDAMENTAL = 3, USAC_ESSENTIAL = 4 };
@@ -773,6 +776,92 @@ int usac_multi_pose_device(usac_multi *mc, const usac_multi_pose_output *o);
  * call on a homography or fundamental context, USAC_ERR_ARG for a NULL mc or E or when every output is NULL. */
 int usac_multi_pose(usac_multi *mc, const float *E, const uint8_t *mask, float *R, float *t, int32_t *front,
                     int32_t *choice, uint8_t *front_mask);
+/* Pose refinement (ABI 29): a pose (R, t) of an essential context's problem refined on the device, a few
+ * Levenberg-Marquardt steps on its five parameters over the Sampson distances of the masked rows.  All arithmetic
+ * is fp64, no contraction, correctly rounded division and square root and no other library function (DESIGN.md
+ * §4); every expression below is evaluated as it is bracketed, left to right otherwise.
+ * Inputs, for problem p: a start R0 (9 fp32, row-major) and t0 (3 fp32), widened to fp64; its calibrated rows
+ * (x1 y1 x2 y2, fp32, widened); a 0 / 1 mask over the rows; a status.  A row is USED when its mask byte is set and
+ * its four values are finite.  The problem is SKIPPED when its status is not USAC_OK, a value of R0 or t0 is not
+ * finite, t0 is the zero vector, or fewer than 5 rows are used: R and t are then the inputs' bits, E is zero, cost0
+ * and cost are 0, iterations is -1, used is the number of used rows.  (usac_multi_pose_device's choice = -1 output,
+ * R the identity and t zero, is skipped by this without a special case.)
+ *   Helpers.  unit(v) = v / sqrt((v0 v0 + v1 v1) + v2 v2), one division per entry.  u x v = (u1 v2 - u2 v1,
+ *     u2 v0 - u0 v2, u0 v1 - u1 v0).  [v]x M is the matrix whose column c is v x (column c of M).  [e_j]x M is
+ *     exact: rows (0, -M2, M1) for j = 0, (M2, 0, -M0) for j = 1, (-M1, M0, 0) for j = 2, M0..M2 the rows of M.
+ *   Start.  t = unit(t0); R = R0 as given.  R is not re-orthonormalised: an fp32 rotation has det R - 1 of about
+ *     2e-8, and left multiplication by exact rotations keeps it there.
+ *   Frame at (R, t).  k = the lowest index of the smallest |t_k|; c = t x e_k written out -- (0, t2, -t1), (-t2, 0,
+ *     t0) or (t1, -t0, 0) --; b1 = unit(c), b2 = t x b1.  E = [t]x R.  D_j = [t]x ([e_j]x R) for j = 0, 1, 2 (a
+ *     left perturbation of R), D_3 = [b1]x R, D_4 = [b2]x R.
+ *   Per used row.  For a matrix M: M x1 has the entries (M_r0 x1 + M_r1 y1) + M_r2, and (M^T x2)_c = (M_0c x2 +
+ *     M_1c y2) + M_2c.  a = E x1; b = the first two entries of E^T x2; C = (x2 a0 + y2 a1) + a2; S = ((a0 a0 +
+ *     a1 a1) + b0 b0) + b1 b1.  A row whose S is not > 0 contributes nothing in that pass.  s = sqrt(S), r = C / s:
+ *     the signed Sampson distance (the standard one, not EssentialEstimator::GetError, which the inlier test uses;
+ *     the mask is an input and is never re-evaluated).  For j = 0..4, with u = D_j x1 and v = the first two
+ *     entries of D_j^T x2: num = (x2 u0 + y2 u1) + u2, q = ((a0 u0 + a1 u1) + b0 v0) + b1 v1 and
+ *     J_j = num / s - (r q) / S, the full derivative, the denominator's included.
+ *   One pass gives 21 sums over the contributing rows: H_jk = sum J_j J_k for j <= k (H is symmetric), g_j = sum
+ *     J_j r, c = sum r r.  The order of summation is part of the rule: thread T of 256 adds its rows i = T, T +
+ *     256, ... in ascending order into an accumulator that starts at +0; the 64 lane values of a wave are combined
+ *     by the xor butterfly with offsets 32, 16, 8, 4, 2, 1 (v = v[:32] + v[32:], then v[:16] + v[16:], ...); the
+ *     four wave totals as (w0 + w1) + (w2 + w3).  No atomics.
+ *   Loop.  lambda = 1e-3.  The first pass, at the start pose, gives (H, g, c) and cost0 = c; iterations = 0.  While
+ *     iterations < max_iters:
+ *       Solve (H + lambda diag H) d = -g: A_jj = H_jj + lambda H_jj, the rest of A is H; Cholesky A = L L^T by
+ *       columns j = 0..4: p = A_jj - L_j0 L_j0 - ... (k ascending), a pivot p that is not > 0 REJECTS without a
+ *       pass; L_jj = sqrt(p), L_ij = (A_ij - L_i0 L_j0 - ...) / L_jj for i > j.  y_i = (-g_i - L_i0 y_0 - ...) /
+ *       L_ii for i = 0..4, then d_i = (y_i - L_(i+1)i d_(i+1) - ...) / L_ii (k ascending) for i = 4..0.
+ *       Trial pose: q = (d0 / 2, d1 / 2, d2 / 2) (a multiplication by 0.5), w = 1 / sqrt(((1 + qx qx) + qy qy) +
+ *       qz qz), x = qx w, y = qy w, z = qz w, Q = [1 - 2 (y y + z z), 2 (x y - w z), 2 (x z + w y); 2 (x y + w z),
+ *       1 - 2 (x x + z z), 2 (y z - w x); 2 (x z - w y), 2 (y z + w x), 1 - 2 (x x + y y)]; R'_rc = (Q_r0 R_0c +
+ *       Q_r1 R_1c) + Q_r2 R_2c; t' = unit((t_k + d3 b1_k) + d4 b2_k).
+ *       One pass at (R', t'), with the frame rebuilt there, gives (H', g', c'); iterations += 1.
+ *       ACCEPT if c' < c (a NaN c' rejects): the primed values and their frame become the current ones, lambda =
+ *       max(lambda / 10, 1e-12); stop if c - c' <= 1e-12 c or max |d_j| < 1e-10, c the old cost.
+ *       REJECT otherwise: lambda = 10 lambda, stop if lambda > 1e8; the kept (H, g) are solved again, no pass is
+ *       repeated.
+ *     So a call runs iterations + 1 passes; a rejection by the pivot runs none and is bounded by lambda alone.
+ *     With max_iters = 0 the outputs are the normalised start, cost = cost0 and iterations = 0.
+ *   Outputs.  R and t, each cast once to fp32; E, the nine entries of [t]x R in fp64 cast once (a model
+ *     usac_multi_inliers or usac_multi_pose takes); cost0 and cost, fp64, cost <= cost0 by construction; iterations
+ *     and used, int32.
+ * On 5 or 6 noisy rows a 5-parameter fit follows the noise, as any does: the cost falls, the pose need not improve.
+ * One launch, one 256-thread workgroup per problem, any n_p, the whole loop inside the kernel. */
+typedef struct usac_multi_refine_io {
+    uint32_t n_max;        /* columns per problem of mask_in, as usac_multi_device_output.n_max */
+    uint32_t max_iters;    /* 0..100 trial steps; 10 is the documented default */
+    const float   *R_in;   /* DEVICE, P x 9, row-major: the start rotations */
+    const float   *t_in;   /* DEVICE, P x 3: the start translations, any non-zero length */
+    const uint8_t *mask_in;/* DEVICE, P x n_max bytes of 0 / 1, a row's byte at its source column (front_mask of
+                            * usac_multi_pose_output); NULL: the resident inlier mask */
+    float   *R;            /* DEVICE, P x 9; may be R_in */
+    float   *t;            /* DEVICE, P x 3; may be t_in */
+    float   *E;            /* DEVICE, P x 9: [t]x R */
+    double  *cost0;        /* DEVICE, P doubles, 8-byte aligned: the cost at the start */
+    double  *cost;         /* DEVICE, P doubles, 8-byte aligned: the cost at the output */
+    int32_t *iterations;   /* DEVICE, P: the trial poses evaluated, -1: skipped */
+    int32_t *used;         /* DEVICE, P: the used rows */
+    void    *stream;       /* hipStream_t the launch is enqueued on; NULL: the null stream */
+} usac_multi_refine_io;
+/* The rule above for every problem of an essential context, the status of problem p being that of the resident
+ * result of the last polishing call (usac_multi_export_device says what is resident and what ends it), the mask
+ * mask_in or, with NULL, the resident inlier mask.  One launch on o->stream, which the call waits for.  The inputs
+ * R_in and t_in may be the very pointers R and t: a workgroup reads its problem's start before it writes anything.
+ * Every output pointer is nullable, not all of them.  The call reads the resident result and leaves it as it is.
+ * USAC_ERR_UNSUPPORTED before any device call on a homography or fundamental context, and when no result is
+ * resident; USAC_ERR_ARG before any device call for a NULL mc, o, R_in or t_in, max_iters > 100, every output
+ * NULL, or an n_max usac_multi_export_device would refuse; USAC_ERR_ARG before any launch, nothing written, for a
+ * pointer that is not device memory of the context's device, is misaligned or too short. */
+int usac_multi_refine_pose_device(usac_multi *mc, const usac_multi_refine_io *o);
+/* The same kernel from host arrays: R P x 9, t P x 3; mask N_total bytes over the packed rows, NULL: every row;
+ * every status counts as USAC_OK.  R_out P x 9, t_out P x 3, E_out P x 9, cost0 P, cost P, iterations P and used P
+ * are host arrays, each nullable, not all of them; R_out may be R and t_out may be t.  The call uses buffers of its
+ * own: the resident result stays as it is.  USAC_ERR_UNSUPPORTED before any device call on a homography or
+ * fundamental context, USAC_ERR_ARG for a NULL mc, R or t, max_iters > 100 or when every output is NULL. */
+int usac_multi_refine_pose(usac_multi *mc, const float *R, const float *t, const uint8_t *mask, uint32_t max_iters,
+                           float *R_out, float *t_out, float *E_out, double *cost0, double *cost, int32_t *iterations,
+                           int32_t *used);
 void usac_multi_destroy(usac_multi *mc);
 /* The message of the context's last failed call; mc == NULL: "null context", or see usac_multi_create_device. */
 const char *usac_multi_last_error(const usac_multi *mc);

@@ -726,6 +726,41 @@ public:
                               r.choice.data(), r.front_mask.data()), "MultiContext::pose");
         return r;
     }
+    // usac_multi_refine_pose_device (ABI 29, an essential context): the poses o.R_in (P x 9) and o.t_in (P x 3) in
+    // device memory refined by up to o.max_iters (0..100) Levenberg-Marquardt trial steps over the Sampson
+    // distances of the rows o.mask_in marks (P x n_max bytes at source columns, poseDevice's front_mask; NULL: the
+    // resident inlier mask), by one launch on o.stream, which the call waits for: R, t, E = [t]x R, the cost at the
+    // start and at the output (doubles), the trial steps evaluated (-1: the problem was skipped) and the rows used.
+    // Every output pointer of o is nullable; o.R may be o.R_in and o.t may be o.t_in.  It reads the resident result
+    // of the last polishing call and leaves it as it is; it throws what poseDevice throws.
+    void refinePoseDevice(const usac_multi_refine_io &o) const {
+        check(usac_multi_refine_pose_device(mc_, &o), "MultiContext::refinePoseDevice");
+    }
+    // usac_multi_refine_pose (ABI 29): the same refinement of the caller's own poses (R P x 9, t P x 3) over the
+    // mask (N_total bytes over the packed rows; empty: every row), into host vectors
+    struct Refined {
+        std::vector<float> R, t, E;
+        std::vector<double> cost0, cost;
+        std::vector<int32_t> iterations, used;
+    };
+    Refined refinePose(const std::vector<float> &R, const std::vector<float> &t,
+                       const std::vector<uint8_t> &mask = std::vector<uint8_t>(), uint32_t max_iters = 10) const {
+        const size_t P = offsets_.empty() ? 0u : offsets_.size() - 1, n = offsets_.empty() ? 0u : offsets_.back();
+        if (R.size() != 9 * P || t.size() != 3 * P) throw Error(USAC_ERR_ARG, "refinePose: P x 9 and P x 3 pose values");
+        if (!mask.empty() && mask.size() != n) throw Error(USAC_ERR_ARG, "refinePose: N_total mask bytes, or none");
+        Refined r;
+        r.R.resize(9 * P);
+        r.t.resize(3 * P);
+        r.E.resize(9 * P);
+        r.cost0.resize(P);
+        r.cost.resize(P);
+        r.iterations.resize(P);
+        r.used.resize(P);
+        check(usac_multi_refine_pose(mc_, R.data(), t.data(), mask.empty() ? nullptr : mask.data(), max_iters, r.R.data(),
+                                     r.t.data(), r.E.data(), r.cost0.data(), r.cost.data(), r.iterations.data(),
+                                     r.used.data()), "MultiContext::refinePose");
+        return r;
+    }
 
     // one round of R hypotheses (a multiple of 64 in 64..8192) for the listed problems (empty: all,
     // in order), device sampler keyed by seeds[i] for problems[i]; with per_hypothesis the counts

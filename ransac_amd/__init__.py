@@ -205,6 +205,15 @@ class _MultiPoseOutput(ctypes.Structure):
                 ("stream", ctypes.c_void_p)]
 
 
+class _MultiRefineIO(ctypes.Structure):
+    """usac_multi_refine_io (ABI 29): the mask's width, the step limit, the input and output device pointers as
+    integers, the stream"""
+    _fields_ = [("n_max", ctypes.c_uint32), ("max_iters", ctypes.c_uint32), ("R_in", ctypes.c_void_p),
+                ("t_in", ctypes.c_void_p), ("mask_in", ctypes.c_void_p), ("R", ctypes.c_void_p), ("t", ctypes.c_void_p),
+                ("E", ctypes.c_void_p), ("cost0", ctypes.c_void_p), ("cost", ctypes.c_void_p),
+                ("iterations", ctypes.c_void_p), ("used", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
+
+
 # every symbol include/usac_gpu.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "usac_create", "usac_destroy", "usac_last_error", "usac_abi_version", "usac_set_dlt_mode", "usac_sample_size",
@@ -238,6 +247,7 @@ ABI_SYMBOLS = [
     "usac_multi_create_device_sorted",
     "usac_multi_set_resident", "usac_multi_export_device",
     "usac_multi_pose_device", "usac_multi_pose",
+    "usac_multi_refine_pose_device", "usac_multi_refine_pose",
 ]
 
 
@@ -260,6 +270,7 @@ def lib():
         raise RuntimeError("ransac_amd: %s is missing -- run ransac_amd.build() (hipcc, gfx950)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     f32p, i32p, u32p, u8p = _P(ctypes.c_float), _P(ctypes.c_int32), _P(ctypes.c_uint32), _P(ctypes.c_uint8)
+    f64p = _P(ctypes.c_double)
     sig = {
         "usac_create": (ctypes.c_int, [_P(_vp), ctypes.c_int, ctypes.c_int, f32p, ctypes.c_uint32, ctypes.c_uint32]),
         "usac_destroy": (None, [_vp]),
@@ -351,6 +362,9 @@ def lib():
         "usac_multi_export_device": (ctypes.c_int, [_vp, _P(_MultiDeviceOutput)]),
         "usac_multi_pose_device": (ctypes.c_int, [_vp, _P(_MultiPoseOutput)]),
         "usac_multi_pose": (ctypes.c_int, [_vp, f32p, u8p, f32p, f32p, i32p, i32p, u8p]),
+        "usac_multi_refine_pose_device": (ctypes.c_int, [_vp, _P(_MultiRefineIO)]),
+        "usac_multi_refine_pose": (ctypes.c_int, [_vp, f32p, f32p, u8p, ctypes.c_uint32, f32p, f32p, f32p, f64p, f64p,
+                                                  i32p, i32p]),
         "usac_multi_destroy": (None, [_vp]),
         "usac_multi_last_error": (ctypes.c_char_p, [_vp]),
         "usac_multi_num_problems": (ctypes.c_uint32, [_vp]),
@@ -417,7 +431,8 @@ class _DevArray:
     the object that owns the memory.  A torch tensor (data_ptr()) or anything with __cuda_array_interface__;
     TypeError for host memory, ValueError for a layout that is not C-contiguous."""
 
-    _TORCH = {"torch.float32": "f4", "torch.int32": "i4", "torch.int64": "i8", "torch.uint8": "u1", "torch.bool": "b1"}
+    _TORCH = {"torch.float32": "f4", "torch.float64": "f8", "torch.int32": "i4", "torch.int64": "i8", "torch.uint8": "u1",
+              "torch.bool": "b1"}
 
     def __init__(self, obj, name):
         self.obj, self.name = obj, name
@@ -1246,6 +1261,80 @@ class MultiContext:
                                           _ptr(R, ctypes.c_float), _ptr(t, ctypes.c_float), _ptr(front, ctypes.c_int32),
                                           _ptr(choice, ctypes.c_int32), _ptr(fm, ctypes.c_uint8)), "multi_pose")
         return {"R": R, "t": t, "front": front, "choice": choice, "front_mask": fm}
+
+    def refine_pose(self, R, t, mask=None, max_iters=10, n_max=None, out=None, stream=None):
+        """usac_multi_refine_pose_device (an essential context): the poses R (P, 3, 3) and t (P, 3), float32 device
+        tensors such as export_pose's, refined on the device by up to max_iters Levenberg-Marquardt trial steps on
+        the five pose parameters over the Sampson distances of the masked rows (include/usac_gpu.h "Pose
+        refinement").  mask: a (P, n_max) bool or uint8 device tensor with a row's byte at its source column, such
+        as export_pose's "front_mask"; None: the resident inlier mask.  The status of a problem is the resident
+        result's.  Tensors on the context's device, written by one launch: "R" (P, 3, 3), "t" (P, 3) and "E"
+        (P, 3, 3) float32 (E = [t]x R), "cost0" and "cost" (P,) float64 (cost <= cost0), "iterations" (P,) int32
+        (-1: the problem was skipped and R, t are the inputs) and "used" (P,) int32.  out may name R and t
+        themselves as outputs: the refinement is then in place.  n_max, out and stream: as export_device's.  The
+        resident result stays as it is."""
+        import torch
+
+        P = self.P
+        out = dict(out or {})
+        spec = {"R": ((P, 3, 3), "f4"), "t": ((P, 3), "f4"), "E": ((P, 3, 3), "f4"), "cost0": ((P,), "f8"),
+                "cost": ((P,), "f8"), "iterations": ((P,), "i4"), "used": ((P,), "i4")}
+        unknown = set(out) - set(spec)
+        if unknown:
+            raise ValueError("refine_pose: unknown outputs %s" % sorted(unknown))
+        if n_max is None:
+            n_max = self.n_max if self.n_max is not None else int(self.sizes.max())
+        n_max = int(n_max)
+        max_iters = int(max_iters)
+        if not 0 <= max_iters <= 100:
+            raise ValueError("refine_pose: max_iters must be 0..100")
+        ins = {"R_in": _DevArray(R, "R").need((P, 3, 3), ("f4",)), "t_in": _DevArray(t, "t").need((P, 3), ("f4",))}
+        if mask is not None:
+            ins["mask_in"] = _DevArray(mask, "mask").need((P, n_max), ("u1", "b1"))
+        arrays = {}
+        for key, (shape, kind) in spec.items():
+            if key not in out:
+                dt = {"f4": torch.float32, "f8": torch.float64, "i4": torch.int32}[kind]
+                out[key] = torch.empty(shape, dtype=dt, device="cuda:%d" % self.device)
+            arrays[key] = _DevArray(out[key], key).need(shape, (kind,))
+        res = {key: out[key] for key in spec}
+        if stream is None:
+            stream = 0
+            first = ins["R_in"]
+            if first.torch:
+                stream = torch.cuda.current_stream(first.obj.device).cuda_stream
+        o = _MultiRefineIO(n_max=n_max, max_iters=max_iters, stream=int(stream) or None,
+                           **{key: a.ptr for key, a in list(ins.items()) + list(arrays.items())})
+        self._check(lib().usac_multi_refine_pose_device(self._h, ctypes.byref(o)), "multi_refine_pose_device")
+        return res
+
+    def refine(self, R, t, mask=None, max_iters=10):
+        """usac_multi_refine_pose: the same refinement from numpy arrays.  R: (P, 3, 3) or (P, 9) float32, t: (P, 3);
+        mask: N_total bytes over the packed rows (None: every row); every status counts as OK.  Returns a dict of
+        numpy arrays: "R" (P, 3, 3), "t" (P, 3), "E" (P, 3, 3) float32, "cost0", "cost" (P,) float64, "iterations"
+        and "used" (P,) int32."""
+        P, n = self.P, int(self.offsets[-1])
+        R = np.ascontiguousarray(R, dtype=np.float32).reshape(P, 9)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(P, 3)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+            if mask.size != n:
+                raise ValueError("refine: mask must have N_total = %d bytes" % n)
+        max_iters = int(max_iters)
+        if not 0 <= max_iters <= 100:
+            raise ValueError("refine: max_iters must be 0..100")
+        Ro = np.zeros((P, 3, 3), dtype=np.float32)
+        to = np.zeros((P, 3), dtype=np.float32)
+        E = np.zeros((P, 3, 3), dtype=np.float32)
+        cost0 = np.zeros(P, dtype=np.float64)
+        cost = np.zeros(P, dtype=np.float64)
+        iterations = np.zeros(P, dtype=np.int32)
+        used = np.zeros(P, dtype=np.int32)
+        self._check(lib().usac_multi_refine_pose(
+            self._h, _ptr(R, ctypes.c_float), _ptr(t, ctypes.c_float), _ptr(mask, ctypes.c_uint8), max_iters,
+            _ptr(Ro, ctypes.c_float), _ptr(to, ctypes.c_float), _ptr(E, ctypes.c_float), _ptr(cost0, ctypes.c_double),
+            _ptr(cost, ctypes.c_double), _ptr(iterations, ctypes.c_int32), _ptr(used, ctypes.c_int32)), "multi_refine_pose")
+        return {"R": Ro, "t": to, "E": E, "cost0": cost0, "cost": cost, "iterations": iterations, "used": used}
 
     def resident_points(self):
         """usac_multi_get_points: the N_total x 4 rows resident on the device (a copy)."""

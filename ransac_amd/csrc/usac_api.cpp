@@ -4140,6 +4140,8 @@ struct usac_multi {
     DevBuf kdev;
     // Pose (ABI 28): usac_multi_pose's own block -- the caller's models and mask up, the outputs down
     DevBuf pose_buf;
+    // Pose refinement (ABI 29): usac_multi_refine_pose's own block -- the caller's poses and mask up, the outputs down
+    DevBuf refine_buf;
     std::string err;
 };
 
@@ -5470,6 +5472,117 @@ int usac_multi_pose(usac_multi *mc, const float *E, const uint8_t *mask, float *
     return USAC_OK;
 }
 
+// ---- pose refinement (ABI 29)
+int usac_multi_refine_pose_device(usac_multi *mc, const usac_multi_refine_io *o) {
+    const char *who = "usac_multi_refine_pose_device: ";
+    if (!mc) return USAC_ERR_ARG;
+    int rc = multi_pose_only_essential(mc, who);
+    if (rc) return rc;
+    if (!o) return fail(mc, USAC_ERR_ARG, std::string(who) + "NULL arguments");
+    if (!o->R_in || !o->t_in) return fail(mc, USAC_ERR_ARG, std::string(who) + "NULL R_in or t_in");
+    if (!usac::refine_iters_ok(o->max_iters))
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "max_iters must be 0..100");
+    if (!o->R && !o->t && !o->E && !o->cost0 && !o->cost && !o->iterations && !o->used)
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "every output pointer is NULL");
+    const uint32_t P = mc->P;
+    rc = multi_width_check(mc, who, o->n_max);
+    if (rc) return rc;
+    if (!usac::pack_extent_ok(P, o->n_max))
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "n_max must be > 0, P * n_max < 2^32");
+    rc = multi_resident_check(mc, who);
+    if (rc) return rc;
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    // a host pointer must never reach the kernel: every pointer it will read or write, before the launch
+    struct { const void *p; const char *name; size_t bytes, align; } ptrs[] = {
+        {o->R_in, "R_in", (size_t)P * 36, 4},   {o->t_in, "t_in", (size_t)P * 12, 4},
+        {o->mask_in, "mask_in", (size_t)P * o->n_max, 1},
+        {o->R, "R", (size_t)P * 36, 4},         {o->t, "t", (size_t)P * 12, 4},
+        {o->E, "E", (size_t)P * 36, 4},         {o->cost0, "cost0", (size_t)P * 8, 8},
+        {o->cost, "cost", (size_t)P * 8, 8},    {o->iterations, "iterations", (size_t)P * 4, 4},
+        {o->used, "used", (size_t)P * 4, 4}};
+    for (const auto &q : ptrs) {
+        if (!q.p) continue;
+        const std::string why = device_pointer_problem(q.p, q.name, mc->device, q.bytes, q.align);
+        if (!why.empty()) return fail(mc, USAC_ERR_ARG, std::string(who) + why);
+    }
+    usac::MultiRefine a{};
+    a.pts = mc->pts.as<float4>();
+    a.offsets = mc->offs.as<uint32_t>();
+    a.pol = mc->pol_out.as<usac_multi_polish_output>();
+    a.R_in = o->R_in;
+    a.t_in = o->t_in;
+    // the caller's mask is padded, a row's byte at its source column; the resident one lies over the packed rows
+    a.mask = o->mask_in ? o->mask_in : mc->mask.as<uint8_t>();
+    a.mask_packed = o->mask_in == nullptr;
+    a.src = (o->mask_in && mc->n_max) ? mc->src.as<uint32_t>() : nullptr;
+    a.P = P;
+    a.n_max = o->n_max;
+    a.max_iters = o->max_iters;
+    a.R = o->R;
+    a.t = o->t;
+    a.E = o->E;
+    a.cost0 = o->cost0;
+    a.cost = o->cost;
+    a.iterations = o->iterations;
+    a.used = o->used;
+    // every call of this context has waited for its streams: the resident buffers are at rest, and are only read
+    hipStream_t cs = static_cast<hipStream_t>(o->stream);
+    HIP_TRY(mc, usac::launch_multi_refine(cs, a));
+    HIP_TRY(mc, stream_wait(cs));
+    return USAC_OK;
+}
+
+int usac_multi_refine_pose(usac_multi *mc, const float *R, const float *t, const uint8_t *mask, uint32_t max_iters,
+                           float *R_out, float *t_out, float *E_out, double *cost0, double *cost, int32_t *iterations,
+                           int32_t *used) {
+    const char *who = "usac_multi_refine_pose: ";
+    if (!mc) return USAC_ERR_ARG;
+    const int rc = multi_pose_only_essential(mc, who);
+    if (rc) return rc;
+    if (!R || !t) return fail(mc, USAC_ERR_ARG, std::string(who) + "NULL R or t");
+    if (!usac::refine_iters_ok(max_iters)) return fail(mc, USAC_ERR_ARG, std::string(who) + "max_iters must be 0..100");
+    if (!R_out && !t_out && !E_out && !cost0 && !cost && !iterations && !used)
+        return fail(mc, USAC_ERR_ARG, std::string(who) + "every output pointer is NULL");
+    HIP_TRY(mc, hipSetDevice(mc->device));
+    // one block of the call's own (usac_pack.hpp's refine_block): the poses are refined in place in it, the
+    // resident buffers are not touched
+    const size_t P = mc->P, n = mc->n_total;
+    const usac::RefineBlock blk = usac::refine_block(P, n);
+    const size_t at_cost0 = blk.cost0, at_cost = blk.cost, at_R = blk.R, at_t = blk.t, at_E = blk.E, at_iter = blk.iterations,
+                 at_used = blk.used, at_mask = blk.mask;
+    HIP_TRY(mc, mc->refine_buf.reserve(blk.bytes));
+    char *d = mc->refine_buf.as<char>();
+    HIP_TRY(mc, hipMemcpyAsync(d + at_R, R, 36 * P, hipMemcpyHostToDevice, mc->stream));
+    HIP_TRY(mc, hipMemcpyAsync(d + at_t, t, 12 * P, hipMemcpyHostToDevice, mc->stream));
+    if (mask) HIP_TRY(mc, hipMemcpyAsync(d + at_mask, mask, n, hipMemcpyHostToDevice, mc->stream));
+    usac::MultiRefine a{};
+    a.pts = mc->pts.as<float4>();
+    a.offsets = mc->offs.as<uint32_t>();
+    a.R_in = reinterpret_cast<const float *>(d + at_R);
+    a.t_in = reinterpret_cast<const float *>(d + at_t);
+    a.mask = mask ? reinterpret_cast<const uint8_t *>(d + at_mask) : nullptr;
+    a.mask_packed = true;
+    a.P = mc->P;
+    a.max_iters = max_iters;
+    a.R = reinterpret_cast<float *>(d + at_R);
+    a.t = reinterpret_cast<float *>(d + at_t);
+    a.E = E_out ? reinterpret_cast<float *>(d + at_E) : nullptr;
+    a.cost0 = cost0 ? reinterpret_cast<double *>(d + at_cost0) : nullptr;
+    a.cost = cost ? reinterpret_cast<double *>(d + at_cost) : nullptr;
+    a.iterations = iterations ? reinterpret_cast<int32_t *>(d + at_iter) : nullptr;
+    a.used = used ? reinterpret_cast<int32_t *>(d + at_used) : nullptr;
+    HIP_TRY(mc, usac::launch_multi_refine(mc->stream, a));
+    if (R_out) HIP_TRY(mc, hipMemcpyAsync(R_out, d + at_R, 36 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (t_out) HIP_TRY(mc, hipMemcpyAsync(t_out, d + at_t, 12 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (E_out) HIP_TRY(mc, hipMemcpyAsync(E_out, d + at_E, 36 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (cost0) HIP_TRY(mc, hipMemcpyAsync(cost0, d + at_cost0, 8 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (cost) HIP_TRY(mc, hipMemcpyAsync(cost, d + at_cost, 8 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (iterations) HIP_TRY(mc, hipMemcpyAsync(iterations, d + at_iter, 4 * P, hipMemcpyDeviceToHost, mc->stream));
+    if (used) HIP_TRY(mc, hipMemcpyAsync(used, d + at_used, 4 * P, hipMemcpyDeviceToHost, mc->stream));
+    HIP_TRY(mc, stream_wait(mc->stream));
+    return USAC_OK;
+}
+
 void usac_multi_destroy(usac_multi *mc) {
     if (!mc) return;
     (void)hipSetDevice(mc->device);
@@ -5481,7 +5594,7 @@ void usac_multi_destroy(usac_multi *mc) {
     for (DevBuf *b : {&mc->pts, &mc->offs, &mc->items, &mc->samples, &mc->models, &mc->counts, &mc->sums, &mc->list,
                       &mc->list_n, &mc->out, &mc->running, &mc->mmodels, &mc->m18, &mc->mask, &mc->pol_lists,
                       &mc->pol_out, &mc->lo_state, &mc->e5_ws, &mc->thrs, &mc->lo_steps, &mc->src, &mc->kdev,
-                      &mc->pose_buf})
+                      &mc->pose_buf, &mc->refine_buf})
         b->release();
     if (mc->stream) StreamPool::get().give_back(mc->stream);
     delete mc;

@@ -548,6 +548,28 @@ struct MultiPose {
 };
 hipError_t launch_multi_pose(hipStream_t st, const MultiPose &a);
 
+// Pose refinement (kernels_multi_refine.hip, ABI 29): per problem a pose (R, t) refined by Levenberg-Marquardt
+// steps over the Sampson distances of its masked rows (include/usac_gpu.h "Pose refinement"), one launch, one
+// workgroup per problem, the whole loop in the kernel.  The status of problem p is pol[p].status, or USAC_OK for
+// every problem with pol == nullptr.  mask (nullptr: every row) is n_total bytes over the packed rows when
+// mask_packed is set; otherwise P x n_max bytes with a row's byte at its source column (src; nullptr: the identity,
+// the caller has checked n_max >= max n_p).  R_in / t_in may be R / t.  Every output is nullable: R P x 9, t P x 3,
+// E P x 9, cost0 / cost P doubles, iterations / used P.
+struct MultiRefine {
+    const float4 *pts;
+    const uint32_t *offsets;
+    const usac_multi_polish_output *pol;
+    const float *R_in, *t_in;
+    const uint8_t *mask;
+    const uint32_t *src;
+    uint32_t P, n_max, max_iters;
+    bool mask_packed;
+    float *R, *t, *E;
+    double *cost0, *cost;
+    int32_t *iterations, *used;
+};
+hipError_t launch_multi_refine(hipStream_t st, const MultiRefine &a);
+
 // k nearest neighbours of every point (kernels_knn.hip, nearest_neighbors.cpp:69-128):
 // idx / d2 (nullable) n x k, self excluded, ascending distance, ties by index; 1 <= k <= 32
 constexpr uint32_t kKnnMax = 32;

@@ -47,6 +47,28 @@ inline std::string width_message(WidthStatus st, uint32_t ctx_n_max, uint32_t wi
     }
 }
 
+// Pose refinement (ABI 29).  The step limit both entries take, and the one device block usac_multi_refine_pose
+// stages its host arrays through: P problems, n packed rows.  The doubles come first so that they are 8-byte
+// aligned at any P; R and t are refined in place; the mask's n bytes come last.
+constexpr uint32_t kRefineIterLimit = 100;
+inline bool refine_iters_ok(uint32_t max_iters) { return max_iters <= kRefineIterLimit; }
+struct RefineBlock {
+    size_t cost0, cost, R, t, E, iterations, used, mask, bytes;
+};
+inline RefineBlock refine_block(size_t P, size_t n) {
+    RefineBlock b;
+    b.cost0 = 0;
+    b.cost = b.cost0 + 8 * P;
+    b.R = b.cost + 8 * P;
+    b.t = b.R + 36 * P;
+    b.E = b.t + 12 * P;
+    b.iterations = b.E + 36 * P;
+    b.used = b.iterations + 4 * P;
+    b.mask = b.used + 4 * P;
+    b.bytes = b.mask + n;
+    return b;
+}
+
 // sizes[P], flags[P] -> offsets[P + 1] (offsets[0] = 0, the exclusive sum).  Returns kPackOk, or what the first
 // offending problem *bad is refused for (offsets is then unspecified): a flag the kernel raised, a size above
 // n_max (no count of n_max columns is), fewer kept rows than the sample size m, or a total of 2^32 rows or more.

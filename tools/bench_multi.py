@@ -90,6 +90,11 @@ export_device(); one adds export_pose(front_mask=True), the other brings models 
 votes per pair in numpy and uploads R, t and the front mask.  Alternated; export_pose is also timed alone.  On every
 pair whose host vote has a unique winner the two rotations must agree (exit status 1 otherwise); the share of such
 pairs is reported.
+
+--refine (with --pose) measures the pose refinement behind that: the pipeline ending in export_pose(front_mask=True)
+against the same pipeline plus refine_pose(R, t, front_mask), alternated in one process; refine_pose is also timed
+alone.  The median rotation and translation-direction errors of both poses against the pose the pairs were
+generated with are reported.  There is no threshold; exit status 1 only if a cost rose.
 """
 import argparse
 import ctypes
@@ -907,6 +912,116 @@ def main_pose(a, model):
     return 0 if models_equal and rotations_agree and unique.any() else 1
 
 
+def pose_errors(R, t):
+    """per pair the rotation angle between R and the generator's rotation and the angle between t and the
+    generator's translation direction, in degrees (every pair of make_pairs has the pose of two_view_geometry)"""
+    _, R_gt, t_gt, _, _ = synthetic.two_view_geometry()
+    t_gt = t_gt / np.linalg.norm(t_gt)
+    R, t = R.astype(np.float64), t.astype(np.float64)
+    tr = np.einsum("pij,ij->p", R, R_gt)
+    rot = np.degrees(np.arccos(np.clip((tr - 1.0) / 2.0, -1.0, 1.0)))
+    nt = np.linalg.norm(t, axis=1)
+    with np.errstate(all="ignore"):
+        tra = np.degrees(np.arccos(np.clip((t @ t_gt) / nt, -1.0, 1.0)))
+    return rot, tra
+
+
+def main_refine(a, model):
+    """--pose --refine: the pipeline of main_pose that ends in export_pose(front_mask=True) (A), and the same plus
+    refine_pose(R, t, front_mask) (R), alternated, host-timed, each ending synchronised; refine_pose alone on one
+    context.  Quality: the errors of both poses against the generator's."""
+    import torch
+
+    t_px = np.float32(45.0)
+    sets, K = pixel_pairs(a.pairs, a.points, a.inlier_ratio)
+    P, n = len(sets), a.points
+    n_max = n + n // 4
+    rng = np.random.default_rng(17)
+    rows = np.zeros((P, n_max, 4), dtype=np.float32)
+    valid = np.zeros((P, n_max), dtype=bool)
+    for p, pts in enumerate(sets):
+        cols = np.sort(rng.permutation(n_max)[:len(pts)])
+        rows[p, cols] = pts
+        valid[p, cols] = True
+    dev = torch.device("cuda:0")
+    rows_t, valid_t = torch.from_numpy(rows).to(dev), torch.from_numpy(valid).to(dev)
+    torch.cuda.synchronize()
+
+    def shared():
+        mc = usac.MultiContext.from_padded(usac.ESTIMATOR.Essential, rows_t, valid=valid_t, K1=K)
+        mc.set_pixel_thresholds(t_px)
+        mc.keep_on_device = True
+        mc.run(model, polish=True)
+        mc.export_device()
+        return mc, mc.export_pose(front_mask=True)  # waits for its stream
+
+    def pipe_a():
+        mc, pose = shared()
+        mc.close()
+        return pose
+
+    def pipe_r():
+        mc, pose = shared()
+        ref = mc.refine_pose(pose["R"], pose["t"], pose["front_mask"], max_iters=a.refine_iters)  # waits for its stream
+        mc.close()
+        return pose, ref
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        r = fn()
+        return r, (time.perf_counter() - t0) * 1e3
+
+    for _ in range(a.warmup):
+        pipe_a()
+        pipe_r()
+    ta, tr, talone = [], [], []
+    for _ in range(a.reps):
+        pose_a, ms = timed(pipe_a)
+        ta.append(ms)
+        (pose_r, ref), ms = timed(pipe_r)
+        tr.append(ms)
+        mc, pose = shared()
+        _, ms = timed(lambda: mc.refine_pose(pose["R"], pose["t"], pose["front_mask"], max_iters=a.refine_iters))
+        talone.append(ms)
+        mc.close()
+    same_start = bool(torch.equal(pose_a["R"].view(torch.int32), pose_r["R"].view(torch.int32)))
+    choice = pose_r["choice"].cpu().numpy()
+    it = ref["iterations"].cpu().numpy()
+    cost0, cost = ref["cost0"].cpu().numpy(), ref["cost"].cpu().numpy()
+    done = it >= 0
+    rot0, tra0 = pose_errors(pose_r["R"].cpu().numpy()[done], pose_r["t"].cpu().numpy()[done])
+    rot1, tra1 = pose_errors(ref["R"].cpu().numpy()[done], ref["t"].cpu().numpy()[done])
+    never_rose = bool((cost <= cost0).all())
+
+    def summary(ms):
+        return {"min_ms": round(min(ms), 3), "median_ms": round(statistics.median(ms), 3), "max_ms": round(max(ms), 3)}
+
+    def med(v):
+        return round(float(np.median(v)), 4) if len(v) else None
+
+    line = {"bench": "multi_refine", "estimator": a.estimator, "pairs": a.pairs, "points": a.points, "n_max": n_max,
+            "round": a.R, "max_iterations": a.max_iterations, "inlier_ratio": a.inlier_ratio, "reps": a.reps,
+            "refine_max_iters": a.refine_iters,
+            "pipeline_a_export_pose": summary(ta), "pipeline_r_export_pose_refine_pose": summary(tr),
+            "r_median_minus_a_median_ms": round(statistics.median(tr) - statistics.median(ta), 3),
+            "refine_pose_alone": summary(talone), "same_start_in_both_pipelines": same_start,
+            "pairs_with_a_choice": int((choice >= 0).sum()), "pairs_refined": int(done.sum()),
+            "mean_used_rows": round(float(ref["used"].cpu().numpy()[done].mean()), 2) if done.any() else None,
+            "iterations_min_median_max": [int(it[done].min()), float(np.median(it[done])), int(it[done].max())] if done.any() else None,
+            "median_rotation_error_deg": {"export_pose": med(rot0), "refine_pose": med(rot1)},
+            "median_translation_error_deg": {"export_pose": med(tra0), "refine_pose": med(tra1)},
+            "pairs_whose_rotation_error_fell": int((rot1 < rot0).sum()),
+            "pairs_whose_translation_error_fell": int((tra1 < tra0).sum()),
+            "median_cost_ratio": med(cost[done] / cost0[done]), "cost_never_rose": never_rose}
+    text = json.dumps(line)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(text + "\n")
+    return 0 if never_rose and done.any() else 1
+
+
 def main_device(a, model, est, sets):
     """--device-input: from padded device tensors to the polished inliers as a (P, n_max) bool tensor on the device,
     what a caller does today (pipeline A: down to numpy, ragged sets, MultiContext, run, mask built in numpy, up
@@ -1167,7 +1282,13 @@ def main():
                     help="--estimator essential --device-input --device-output: from_padded(K1=K) + keep_on_device + "
                          "run(polish=True) + export_device, then export_pose(front_mask=True) against models and mask to "
                          "the host, a numpy decomposition and vote per pair, and an upload of R, t and the front mask")
+    ap.add_argument("--refine", action="store_true",
+                    help="--pose: the pipeline ending in export_pose(front_mask=True) against the same pipeline plus "
+                         "refine_pose(R, t, front_mask); the errors of both poses against the generator's")
+    ap.add_argument("--refine-iters", type=int, default=10, help="--refine: max_iters of refine_pose (0..100)")
     a = ap.parse_args()
+    if a.refine and not a.pose:
+        ap.error("--refine goes with --pose")
     if a.pose and not (a.device_input and a.device_output and a.estimator == "essential" and not a.scores):
         ap.error("--pose goes with --estimator essential --device-input --device-output")
     if a.scores and not a.device_input:
@@ -1202,6 +1323,8 @@ def main():
     seeds = [model.seed + p for p in range(a.pairs)]
     if a.pixels:
         return main_pixels(a, model)
+    if a.pose and a.refine:
+        return main_refine(a, model)
     if a.pose:
         return main_pose(a, model)
     if a.device_input and a.scores:
